@@ -2,7 +2,7 @@
 """Headline benchmark: sentences/sec of the chart hot path (inside + outside, forward +
 backward) on synthetic length-20, d=400, batch-64 batches (BASELINE.json config 2).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One step = DioraMLP.forward (leaf transform, inside pass, outside pass) + the hand-written
 backward for random cotangents on all four chart outputs, all HIP kernels behind the C ABI;
@@ -21,6 +21,7 @@ import os
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -293,6 +294,31 @@ def timed_steps(torch, step, fence, n):
     return dt, sorted(a.elapsed_time(b) for a, b in evs)
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, named):
+    """--dump-outputs: write what the timed path handed its caller in its last step, one DIR/<name>.npy per array, float32 (float64 stays
+    float64).  If the arrays together exceed DUMP_LIMIT bytes, every array is cut to the same fraction of its elements: a flat sample at
+    sorted indices drawn from a generator seeded by the array's name, so equal arguments give equal samples from run to run."""
+    import numpy as np
+    arrs = []
+    for name, t in named:
+        a = t.detach().contiguous().cpu().numpy()
+        arrs.append((name.replace('.', '__'), a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)))
+    total = sum(a.nbytes for _, a in arrs)
+    keep = min(1.0, (DUMP_LIMIT - 256 * len(arrs)) / max(total, 1))          # 256 bytes per file for the .npy header
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs:
+        k = max(1, int(a.size * keep))
+        if k < a.size:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+    print('dump-outputs: %d arrays (%s) in %s' % (len(arrs), 'all elements' if keep >= 1.0 else 'sampled to %.4f of %d bytes' % (keep, total), path),
+          file=sys.stderr, flush=True)
+
+
 def pct(sorted_ms, q):
     return sorted_ms[min(len(sorted_ms) - 1, int(q * len(sorted_ms)))]
 
@@ -439,8 +465,10 @@ def cliora_training_workload(args, torch, dist, _lib, dev, world, rank, local, u
     bm = dict(sentences=torch.randint(0, V, (B, L), generator=g).to(dev), neg_samples=torch.randperm(V, generator=torch.Generator().manual_seed(99))[:K].to(dev),
               obj_feats=torch.relu(torch.randn(B, Rg, 2048, generator=g)).to(dev))
 
+    last = {}
+
     def step():
-        tr.step(bm, train=True, sync=False)
+        last['out'] = tr.step(bm, train=True, sync=False)
 
     def fence():
         torch.cuda.synchronize()
@@ -451,6 +479,8 @@ def cliora_training_workload(args, torch, dist, _lib, dev, world, rank, local, u
         step()
     dt, step_ms = timed_steps(torch, step, fence, args.steps)
     dt, ranks = rank_view(torch, dist, dev, dt, args.steps, use_dist, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [('total_loss', last['out']['total_loss'])] + [('param__' + n, p) for n, p in net.named_parameters()])
     if rank == 0:
         plan = _lib.get_plan(B, L, D, True, 'unit', Rg, local)
         step_bytes, _ = algorithmic_bytes(plan, B, D)
@@ -520,6 +550,10 @@ def main():
     ap.add_argument('--share-device', action='store_true',
                     help='self-test of the N > 1 path on a box with ONE GPU: every rank uses cuda:0 (use with --backend gloo: RCCL refuses two ranks on '
                          'one device); the value is not a scaling figure')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (c2: the four chart outputs and every parameter '
+                         'gradient; c3: the loss and every parameter after the update) as DIR/<name>.npy, float32, at most 64 MB in all; '
+                         'inputs are seeded, so equal arguments give equal inputs on every run')
     args = ap.parse_args()
 
     if (args.gpus > 1 or args.via_launcher) and 'WORLD_SIZE' not in os.environ:
@@ -583,6 +617,9 @@ def main():
     events = (rank == 0) and not args.no_kernel_events
     dt, step_ms = timed_steps(torch, step, fence, args.steps)
     dt, ranks = rank_view(torch, dist, dev, dt, args.steps, use_dist, world)
+    if args.dump_outputs and rank == 0:           # before the passes below run the step again
+        dump_outputs(args.dump_outputs, [(k, getattr(model, k)) for k in keys] +
+                     [('grad__' + n, p.grad) for n, p in model.named_parameters() if p.grad is not None])
     # Second pass of the same K steps with a HIP event pair around every launch of the three GEMM classes (on the
     # launch stream), for the roofline object.  It is separate from the timed region above because the event records
     # serialise neighbouring launches; every rank runs the steps so the all-reduces stay matched, only rank 0 records events.

@@ -15,6 +15,7 @@ What is captured (inputs + expected outputs only -- no reference source):
                         parse.jsonl trees  [net/trainer.py, analysis/utils.py, scripts/parse.py helpers]
   interchange_run.npz   the reference Net AFTER Trainer.load_model of ref_model_{noemb,ddp}.pt, run on a fixture batch:
                         charts, loss, trees (what a native module that loaded the same file must reproduce)
+  shim_selection.npz    module name + state_dict keys of the chart module build_net constructs, --obj_feats off / on  [net/trainer.py]
 """
 import os
 import sys
@@ -500,9 +501,29 @@ def interchange_run_case(name):
     save(name, **arrs)
 
 
+def shim_selection_case(name):
+    """The chart module the reference's own build_net constructs (trainer.py:518-526, 552) for --obj_feats off / on: its
+    module name and state_dict keys, so tests/test_selection_shim.py can check the shim's selection without the reference."""
+    import argparse
+    arrs = {}
+    for obj_feats in (False, True):
+        opt = argparse.Namespace(lr=1e-3, hidden_dim=16, k_neg=3, normalize='unit', cuda=False, local_rank=0, share=True, arch='mlp',
+                                 obj_feats=obj_feats, multigpu=False, emb='none', margin=1.0, vl_margin=0.2, hinge_margin=1.0,
+                                 alpha_contr=1.0, vg_loss=obj_feats, alpha_vg=1.0, use_contr=obj_feats, use_contr_ce=False,
+                                 visualize=False, load_model_path=None, experiment_name='shim-fixture')
+        diora = ref_trainer.build_net(opt, torch.nn.Embedding(20, 8)).net.diora
+        tag = 'vl' if obj_feats else 'text'
+        arrs['module__' + tag] = np.array(type(diora).__module__)
+        arrs['keys__' + tag] = np.array(sorted(diora.state_dict()))
+    save(name, meta=np.array(json.dumps(META)), **arrs)
+
+
 if __name__ == '__main__':
     if sys.argv[1:] == ['interchange_run']:          # one new fixture without rewriting the others
         interchange_run_case('interchange_run.npz')
+        sys.exit(0)
+    if sys.argv[1:] == ['shim_selection']:
+        shim_selection_case('shim_selection.npz')
         sys.exit(0)
     index_tables()
     diora_case('diora_c1.npz', D=50, B=8, L=10, seed=1234)                       # BASELINE config 1
@@ -522,3 +543,4 @@ if __name__ == '__main__':
     sampler_case('sampler_batches.npz')
     interchange_case('interchange.npz')
     interchange_run_case('interchange_run.npz')
+    shim_selection_case('shim_selection.npz')

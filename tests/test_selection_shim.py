@@ -1,44 +1,37 @@
 """SURVEY.md section 8(b) "Selection": with cliora_amd/shim ahead of the reference on sys.path, the reference's own
 build_net (cliora/net/trainer.py:518-526, 552) constructs the MI355X-native chart modules without any edit to the
-reference.  Needs the reference checkout (this container only); construction is CPU-side, no chart call is made."""
+reference.  build_net picks its chart class by importing `DioraMLP` from `cliora.net.diora` (--obj_feats off) or
+`cliora.net.cliora` (on) and calls it as `Diora(size, outside=True, normalize=..., compress=False, share=...)`.
+tests/golden/shim_selection.npz records, from the reference's own build_net, which module that is and the state_dict keys
+of what it builds; here the same imports and the same call go through the shim alone (the reference is not on the path)
+and must land on the native modules with exactly those keys.  Construction is CPU-side, no chart call is made."""
+import json
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = '/root/reference'
 
 SCRIPT = r'''
-import sys, types, argparse
-sys.modules['cv2'] = types.ModuleType('cv2')
+import importlib, json, sys
 import torch
-import cliora.net.diora as d, cliora.net.cliora as c, cliora.net.trainer as t, cliora.net.utils as u
-assert d.__file__.startswith(ROOT) and c.__file__.startswith(ROOT), (d.__file__, c.__file__)
-assert t.__file__.startswith(REF) and u.__file__.startswith(REF), (t.__file__, u.__file__)
-for obj_feats in (False, True):
-    opt = argparse.Namespace(lr=1e-3, hidden_dim=16, k_neg=3, normalize='unit', cuda=False, local_rank=0, share=True, arch='mlp',
-                             obj_feats=obj_feats, multigpu=False, emb='none', margin=1.0, vl_margin=0.2, hinge_margin=1.0,
-                             alpha_contr=1.0, vg_loss=obj_feats, alpha_vg=1.0, use_contr=obj_feats, use_contr_ce=False,
-                             visualize=False, load_model_path=None, experiment_name='shim-test')
-    trainer = t.build_net(opt, torch.nn.Embedding(20, 8))
-    diora = trainer.net.diora
-    want = 'cliora_amd.cliora' if obj_feats else 'cliora_amd.diora'
-    assert type(diora).__module__ == want, type(diora).__module__
-    # same state_dict keys as the reference's own module built with the same arguments (loaded from its file under another name)
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('ref_mod', REF + '/cliora/net/' + ('cliora.py' if obj_feats else 'diora.py'))
-    ref_mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(ref_mod)
-    want_keys = sorted(ref_mod.DioraMLP(16, outside=True, normalize='unit', compress=False, share=True).state_dict())
-    assert sorted(diora.state_dict()) == want_keys, (sorted(diora.state_dict()), want_keys)
+want = json.loads(sys.argv[1])
+for tag, native in (('text', 'cliora_amd.diora'), ('vl', 'cliora_amd.cliora')):
+    mod = importlib.import_module(want['module__' + tag])             # build_net's `from cliora.net.<x> import DioraMLP as Diora`
+    assert mod.__file__.startswith(ROOT), mod.__file__
+    diora = mod.DioraMLP(16, outside=True, normalize='unit', compress=False, share=True)
+    assert type(diora).__module__ == native, type(diora).__module__
+    assert sorted(diora.state_dict()) == want['keys__' + tag], (sorted(diora.state_dict()), want['keys__' + tag])
 print('shim ok')
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'cliora')), reason='needs the reference checkout')
-def test_reference_build_net_selects_the_native_modules():
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'cliora_amd', 'shim'), ROOT, REF]))
-    code = 'ROOT = %r\nREF = %r\n' % (ROOT, REF) + SCRIPT
-    r = subprocess.run([sys.executable, '-c', code], env=env, cwd='/tmp', capture_output=True, text=True, timeout=300)
+def test_reference_build_net_selects_the_native_modules(golden, tmp_path):
+    g = golden('shim_selection.npz')
+    want = {k: (str(v) if v.ndim == 0 else [str(s) for s in v]) for k, v in g.items() if k != 'meta'}
+    assert set(want) == {'module__text', 'keys__text', 'module__vl', 'keys__vl'}
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'cliora_amd', 'shim'), ROOT]))
+    code = 'ROOT = %r\n' % ROOT + SCRIPT
+    r = subprocess.run([sys.executable, '-c', code, json.dumps(want)], env=env, cwd=str(tmp_path), capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0 and 'shim ok' in r.stdout, r.stdout + r.stderr
