@@ -220,6 +220,9 @@ class VLMaxObj(torch.autograd.Function):
         if d_max is None:
             return None, None, None, None, None, None
         d_max = d_max.contiguous().float()
+        lane = torch.cuda.current_stream(inside_h.device)
+        for t in (inside_h, outside_h, obj_span, arg, d_max):       # made on the current stream, read here on the lane (see forward)
+            t.record_stream(lane)
         d_obj = torch.empty_like(obj_span)
         ws = torch.empty(ctx.nbytes, device=inside_h.device, dtype=torch.uint8)
         rc = _lib.lib().cliora_vl_scores_max_backward(plan.handle, _ptr(inside_h), _ptr(outside_h), _ptr(obj_span), _ptr(d_max), _ptr(arg),
@@ -402,6 +405,9 @@ class DioraMLP(DioraBase):
                 cur = torch.cuda.current_stream(x_span.device)
                 if not self.word_inputs_on_lane:      # inputs produced on this stream: the lane waits for them (and for the whole chart before them)
                     lane.wait_stream(cur)
+                    for t in (x_word, obj_embed_word):      # ... and their memory is not reused before the scorer's backward there is done
+                        if t is not None:
+                            t.record_stream(lane)
                 with torch.cuda.stream(lane):
                     _, vg = VLScoreFunction.apply(plan, True, ih.detach(), oh.detach(), obj_embed_span.detach(), x_word, obj_embed_word, False)
                 cur.wait_stream(lane)                 # whoever reads vg next on this stream (the VG loss) finds it complete

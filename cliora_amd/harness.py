@@ -32,6 +32,15 @@ def _normal_(module):
             p.data.normal_()
 
 
+def _lane_reads(lane, t, made_here):
+    """`t` is about to be read on `lane`.  When it was made here, on the current stream, after the lane forked (a copy of non-contiguous
+    tokens, the fp32 conversion of the region features), the lane waits for it, and its memory is not reused before the lane's reads
+    (the word projection's forward and backward) are done."""
+    if made_here:
+        lane.wait_stream(torch.cuda.current_stream(t.device))
+        t.record_stream(lane)
+
+
 class Embed(nn.Module):
     """Two bias-free projections of the word embedding: span input and word input."""
 
@@ -44,14 +53,19 @@ class Embed(nn.Module):
 
     def forward(self, tokens, word_lane=None):
         """word_lane: a stream for the WORD projection (the second output), whose only reader is then the word-region scorer on the same
-        stream (cliora_amd.cliora.DioraMLP.word_lane); None: both on the current stream."""
+        stream (cliora_amd.cliora.DioraMLP.word_lane); None: both on the current stream.  Afterwards `word_on_lane` says whether the word
+        projection was produced on word_lane (the native path only: a table width that is not a multiple of 16 takes the torch path, on
+        the current stream)."""
         B, L = tokens.shape
         w = self.embeddings.weight
+        self.word_on_lane = False
         if _native(w, tokens) and w.shape[1] % 16 == 0:
             idx = tokens.reshape(-1)
             span = heads.proj(w, idx, self.mat).view(B, L, -1)
             if word_lane is None:
                 return span, heads.proj(w, idx, self.mat1).view(B, L, -1)
+            _lane_reads(word_lane, idx, not tokens.is_contiguous())
+            self.word_on_lane = True
             with torch.cuda.stream(word_lane):
                 return span, heads.proj(w, idx, self.mat1).view(B, L, -1)
         e = self.embeddings(tokens.reshape(-1))
@@ -69,12 +83,15 @@ class ImageEncoder(nn.Module):
 
     def forward(self, obj_feats, word_lane=None):
         x = obj_feats.float()
+        self.word_on_lane = False                         # see Embed.forward
         if _native(x) and x.shape[-1] % 16 == 0:
             lead = x.shape[:-1]
             span = heads.proj(x, None, self.fc.weight, self.fc.bias).view(*lead, -1)
             if word_lane is None:
                 return span, heads.proj(x, None, self.fc_vis.weight, self.fc_vis.bias).view(*lead, -1)
-            with torch.cuda.stream(word_lane):          # see Embed.forward
+            _lane_reads(word_lane, x, x is not obj_feats)
+            self.word_on_lane = True
+            with torch.cuda.stream(word_lane):
                 return span, heads.proj(x, None, self.fc_vis.weight, self.fc_vis.bias).view(*lead, -1)
         return self.fc(x), self.fc_vis(x)
 
@@ -170,17 +187,38 @@ class VGLoss(nn.Module):
 
 class LossDict(dict):
     """What Net.forward returns: the named losses, plus -- built only when somebody asks for it -- the reference's `total_loss`, the (1, n)
-    row of the losses (trainer.py:300-303).  `total()` is the scalar the reference roots its backward at,
-    `total_loss.mean(dim=0).sum()` (trainer.py:487), as the plain sum of the parts: the same value and the same gradients without the
-    cat / mean / sum launches and their four backward launches per step."""
+    row of the losses (trainer.py:300-303).  Asking includes `in`, get(), keys(), items() and values(): they show the reference's `ret`
+    (the named losses, then total_loss), which its prepare_result walks (trainer.py:457-461).  Plain iteration lists what is built.  `total()` is the scalar
+    the reference roots its backward at, `total_loss.mean(dim=0).sum()` (trainer.py:487), as the plain sum of the parts: the same value
+    and the same gradients without the cat / mean / sum launches and their four backward launches per step."""
     parts = ()
 
     def __missing__(self, key):
-        if key != 'total_loss':
+        if key != 'total_loss' or not self.parts:
             raise KeyError(key)
         v = torch.cat([p.view(1, 1) for p in self.parts], 1)
         self[key] = v
         return v
+
+    def _full(self):
+        if self.parts and not dict.__contains__(self, 'total_loss'):
+            self.__missing__('total_loss')
+        return self
+
+    def __contains__(self, key):
+        return dict.__contains__(self._full() if key == 'total_loss' else self, key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def keys(self):
+        return dict.keys(self._full())
+
+    def items(self):
+        return dict.items(self._full())
+
+    def values(self):
+        return dict.values(self._full())
 
     def total(self):
         t = self.parts[0]
@@ -211,19 +249,34 @@ class Net(nn.Module):
         if (self.overlap_word_branch and self.obj_feats and self.training and torch.is_grad_enabled() and tokens.is_cuda and heads.NATIVE_LANES
                 and getattr(self.diora, 'lazy_region_scores', False)):
             from . import _lib
+            # the lane reads the tokens (word projection) and the fp32 region features (fc_vis): make them final BEFORE the fork, so
+            # that the lane's wait below covers a copy of non-contiguous tokens and the conversion of fp16 / fp64 features
+            t1, f1 = tokens.contiguous(), obj_feats.float()
+            made = [t for t, t0 in ((t1, tokens), (f1, obj_feats)) if t is not t0]
+            tokens, obj_feats = t1, f1
             lane = _lib.side_stream(tokens.device)
             lane.wait_stream(torch.cuda.current_stream(tokens.device))     # the step's inputs and the parameters of the last update
-        if hasattr(self.diora, 'word_lane'):
-            self.diora.word_lane = lane
-            self.diora.word_inputs_on_lane = lane is not None
+            for t in made:              # freed in the backward, while the lane may still read them
+                t.record_stream(lane)
         if lane is not None:
             x_span, x_word = self.embed(tokens, word_lane=lane)
         else:
             x_span, x_word = self.embed(tokens)
+        # the scorer skips its wait for the current stream only when EVERY word input was produced on the lane (Embed / ImageEncoder
+        # take the torch path, on the current stream, at widths that are not multiples of 16)
+        on_lane = lane is not None and getattr(self.embed, 'word_on_lane', False)
         o_span = o_word = None
         if self.obj_feats:
             o_span, o_word = self.img_encoder(obj_feats, word_lane=lane) if lane is not None else self.img_encoder(obj_feats)
-        self.diora(x_span, x_word, o_span, o_word)
+            on_lane = on_lane and getattr(self.img_encoder, 'word_on_lane', False)
+        flags = hasattr(self.diora, 'word_lane')
+        if flags:
+            self.diora.word_lane, self.diora.word_inputs_on_lane = lane, on_lane
+        try:
+            self.diora(x_span, x_word, o_span, o_word)
+        finally:                        # per call: a later direct call of the chart module must not inherit them
+            if flags:
+                self.diora.word_lane, self.diora.word_inputs_on_lane = None, False
         if not compute_loss:
             return {'total_loss': torch.ones(1, 1, device=x_span.device)}
         ret, parts = LossDict(), []

@@ -47,13 +47,22 @@ class DeferredTableGrads(object):
     def offer(self, d_rows, index, table):
         """True when the contribution was taken (the caller then returns None as the table's gradient)."""
         pv = self.arena.lookup(table)
-        if pv is None or pv[0].grad is not None or pv[1].shape != table.shape:
+        if pv is None or pv[1].shape != table.shape:
             return False
-        ent = self.pending.setdefault(id(pv[0]), (pv[0], pv[1], []))
+        ent = self.pending.get(id(pv[0]))
+        if ent is None:
+            if pv[0].grad is not None:      # a gradient already in place: autograd accumulates into it
+                return False
+            ent = self.pending[id(pv[0])] = (pv[0], pv[1], [])
         if len(ent[2]) >= 4:                # cliora_rows_scatter_add_segments takes four segments
             return False
         ent[2].append((d_rows.contiguous(), index.contiguous().reshape(-1)))
         return True
+
+    def holds(self, table):
+        """True once a contribution to `table` was taken: flush() then writes its arena slice, so no other producer may take the slice."""
+        pv = self.arena.lookup(table)
+        return pv is not None and id(pv[0]) in self.pending
 
     def flush(self):
         for param, view, segs in self.pending.values():
@@ -64,6 +73,9 @@ class DeferredTableGrads(object):
             with torch.cuda.device(view.device):
                 _lib.check(_lib.lib().cliora_rows_scatter_add_segments(rows, idx, cnt, n, int(view.shape[1]), _p(view), int(view.shape[0]), _st()),
                            'cliora_rows_scatter_add_segments')
+            # what reached the table outside offer() -- a refused producer's own tensor, a torch-autograd lookup -- is in param.grad
+            if param.grad is not None and param.grad.data_ptr() != view.data_ptr():
+                view.add_(param.grad)
             param.grad = view.detach()      # an alias of the arena slice: the reducer / FusedClipAdam see a gradient already in place
         self.pending = {}
 
@@ -91,15 +103,27 @@ def scatter_rows(d_rows, index, table, producer_lane=None):
     autograd adds).  Replaces zeros_like + index_add_ (round 3's last ATen op on the step), deterministic for repeated ids.
     Inside harness.Trainer.step the contribution is deferred instead (DeferredTableGrads) and None is returned.
     producer_lane: the stream d_rows is produced on when that is not the current one."""
-    if _deferred is not None and _deferred.offer(d_rows, index, table):
-        return None
-    if producer_lane is not None:           # d_rows is still being written on another stream and the scatter runs here, now
+    held = False
+    if _deferred is not None:
+        if _deferred.offer(d_rows, index, table):
+            if producer_lane is not None and _step_lanes is not None:
+                _step_lanes.add(producer_lane)      # the flush after the backward reads d_rows: the step joins the lane first
+            return None
+        held = _deferred.holds(table)
+    if producer_lane is not None and producer_lane.cuda_stream != torch.cuda.current_stream(table.device).cuda_stream:
+        # d_rows is still being written on another stream and the scatter runs here, now
         torch.cuda.current_stream(table.device).wait_stream(producer_lane)
-    out = _grad_out(table)
+    out = torch.empty_like(table) if held else _grad_out(table)      # held: the arena slice belongs to the deferred flush
     with torch.cuda.device(table.device):
         _lib.check(_lib.lib().cliora_rows_scatter_add(_p(d_rows.contiguous()), _p(index.contiguous()), int(index.numel()), int(table.shape[1]), _p(out),
                                                       int(table.shape[0]), _st()), 'cliora_rows_scatter_add')
     return out
+
+
+def _current_lane(device):
+    """The library's caller lane when it is the current stream (a backward node whose forward ran there), else None."""
+    lane = _lib._side_streams.get(device.index)
+    return lane if lane is not None and lane.cuda_stream == torch.cuda.current_stream(device).cuda_stream else None
 
 
 class Proj(torch.autograd.Function):
@@ -145,7 +169,7 @@ class Proj(torch.autograd.Function):
                 if index is None:
                     d_x = d_rows.view(ctx.x_shape)
                 else:       # the embedding table's gradient: rows of repeated tokens add up (in place in the flat gradient buffer when there is one)
-                    d_x = scatter_rows(d_rows, index.reshape(-1), x2)
+                    d_x = scatter_rows(d_rows, index.reshape(-1), x2, producer_lane=_current_lane(d_y.device))
                     d_x = d_x.view(ctx.x_shape) if d_x is not None else None
         return d_x, None, d_w, d_b
 
@@ -203,6 +227,10 @@ class ReconLoss(torch.autograd.Function):
                 _lib.check(lib.cliora_recon_backward(*args(d_cell, None, None)), 'cliora_recon_backward')
                 cur = torch.cuda.current_stream(emb.device)
                 lane.wait_stream(cur)
+                # made on this stream, read on the lane: not reused before the lane is done with them (the cotangent, and the padded
+                # copies of the table and the projection, are freed when this node returns)
+                for t in (g, ctx.ws, emb, mat, tokens, neg):
+                    t.record_stream(lane)
                 with torch.cuda.stream(lane):
                     _lib.check(lib.cliora_recon_backward(*args(None, d_mat, d_rows)), 'cliora_recon_backward')
             d_oh = None

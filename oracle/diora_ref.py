@@ -281,8 +281,9 @@ def embed_forward(emb_weight, mat, mat1, sentences):
 
 
 def image_encoder_forward(Wf, bf, Wv, bv, obj_feats):
-    """ImageEncoder.forward, utils.py:52-55."""
-    x = obj_feats.float()
+    """ImageEncoder.forward, utils.py:52-55.  The features are rounded to fp32 like the reference's, then computed at the parameters'
+    precision (fp64 parameters: a float64 oracle of the same step)."""
+    x = obj_feats.float().to(Wf.dtype)
     return F.linear(x, Wf, bf), F.linear(x, Wv, bv)
 
 

@@ -27,6 +27,16 @@ def test_loss_dict_and_cpu_trainer_step():
     row = out['total_loss']                                   # built now, (1, n) like the reference's
     assert row.shape == (1, 1) and 'total_loss' in out
     assert torch.equal(row.mean(dim=0).sum(), total)
+    # the reference's key set through in / get / keys / items / values (trainer.py:302: ret['total_loss'] = loss; :457-461 walks items()),
+    # built on demand by each of them
+    for ask in (lambda o: 'total_loss' in o, lambda o: o.get('total_loss') is not None, lambda o: 'total_loss' in o.keys(),
+                lambda o: 'total_loss' in dict(o.items()), lambda o: len(o.values()) == 2,
+                lambda o: list(o.keys()) == ['reconstruct_softmax_loss', 'total_loss']):
+        fresh = net(bm['sentences'], None, bm['neg_samples'])
+        assert not dict.__contains__(fresh, 'total_loss') and ask(fresh) and torch.equal(dict.__getitem__(fresh, 'total_loss'), row)
+    assert out.get('no_such_loss') is None and 'no_such_loss' not in out
+    result = {k: v.mean(dim=0).sum().item() for k, v in out.items() if 'loss' in k}         # prepare_result
+    assert set(result) == {'reconstruct_softmax_loss', 'total_loss'} and result['total_loss'] == float(total)
     tr = H.Trainer(net, lr=1e-2)
     assert not tr.fused                                       # CPU parameters: torch.optim.Adam + clip_grad_norm_
     before = {k: p.detach().clone() for k, p in net.named_parameters()}
