@@ -121,6 +121,7 @@ extern "C" size_t cliora_plan_device_bytes(const cliora_plan* plan) {
 // Side streams and fork / join / level events of one device, created at the first call there and kept for the life of the process.
 struct DeviceLanes {
     hipStream_t side = nullptr, side2 = nullptr;
+    bool side2_beside = false;              // the probe found side2 concurrent with the caller's stream and side (not queued behind either)
     hipStream_t side3 = nullptr;            // the callers' lane (cliora_device_side_stream), created at its first request
     hipEvent_t fork[3], join[3], level[CLIORA_MAX_L + 1];
     unsigned long long* trace = nullptr;    // TRACE_BYTES of device words for the diagnostic stamps of the resident kernels (CLIORA_RES_TRACE)
@@ -135,7 +136,9 @@ static __global__ void lane_probe(long long ticks) {
 // HIP deals streams round-robin onto a few hardware queues; two streams on one queue run one after the other.  Create streams until
 // one runs a probe kernel CONCURRENTLY with every stream of `busy` (the caller's stream, lanes picked before), measured once:
 // 40 us probes on all of them take ~40 us together when they overlap and n x 40 us when any two share a queue.
-static int pick_concurrent_stream(hipStream_t* busy, int nbusy, hipStream_t* out) {
+// `concurrent` (optional): whether the stream picked does run beside them -- false when every candidate shared a queue with one of
+// them (the runtime's hardware queues are fewer than the streams: GPU_MAX_HW_QUEUES) and the last candidate was taken anyway.
+static int pick_concurrent_stream(hipStream_t* busy, int nbusy, hipStream_t* out, bool* concurrent = nullptr) {
     hipEvent_t e0 = nullptr, e1 = nullptr, ej = nullptr;
     HIPOK(hipEventCreate(&e0)); HIPOK(hipEventCreate(&e1)); HIPOK(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
     int clk_khz = 100000;
@@ -174,6 +177,7 @@ static int pick_concurrent_stream(hipStream_t* busy, int nbusy, hipStream_t* out
         if (best < base + 0.020f) pick = c;      // one more 40 us probe costs nothing when it overlaps, 40 us when it shares a queue
         else rejected.push_back(c);
     }
+    if (concurrent) *concurrent = pick != nullptr;
     if (!pick && !rejected.empty()) { pick = rejected.back(); rejected.pop_back(); }     // no concurrent queue found: still correct, only slower
     for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(ej);
@@ -193,7 +197,7 @@ static int device_lanes(int dev, hipStream_t st, DeviceLanes** out) {
         hipStream_t busy[3] = {st, nullptr, nullptr};
         OKR(pick_concurrent_stream(busy, 1, &ln->side));
         busy[1] = ln->side;
-        OKR(pick_concurrent_stream(busy, 2, &ln->side2));
+        OKR(pick_concurrent_stream(busy, 2, &ln->side2, &ln->side2_beside));
         // The fork / join / level events order kernels of ONE device against each other, so a device-scope release at the record
         // would do (CLIORA_EVENT_SCOPE=device: hipEventReleaseToDevice instead of the default system-scope release).  Measured on
         // MI355X at c2 (round 4, tools/ab/env_ab.sh, three alternations): 3.512 / 3.547 / 3.528 ms (system) against 3.526 / 3.549 /
@@ -258,7 +262,7 @@ int cliora_plan_ready(cliora_plan* plan, hipStream_t st) {
     plan->p.d_tables_count = flat.size();
     DeviceLanes* ln = nullptr;
     OKR(device_lanes(dev, st, &ln));
-    plan->side = ln->side; plan->side2 = ln->side2;
+    plan->side = ln->side; plan->side2 = ln->side2; plan->side2_beside = ln->side2_beside;
     for (int k = 0; k < 3; ++k) { plan->ev_fork[k] = ln->fork[k]; plan->ev_join[k] = ln->join[k]; }
     plan->ev_level = ln->level;
     plan->lanes_mu = &ln->mu;
