@@ -118,6 +118,10 @@ def lib():
     L.cliora_cky_decode.restype = i32
     L.cliora_cky_spans.argtypes = [vp, vp, vp, vp, vp]
     L.cliora_cky_spans.restype = i32
+    if hasattr(L, 'cliora_ground_eval'):                        # (absent from older builds loaded through CLIORA_CHART_LIB)
+        i64 = C.c_int64
+        L.cliora_ground_eval.argtypes = [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cliora_ground_eval.restype = i32
     L.cliora_prof_enable.argtypes = [i32, i32]
     L.cliora_prof_enable.restype = i32
     L.cliora_prof_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]

@@ -356,16 +356,33 @@ class DioraBase(nn.Module):
         host with ``get_spans(get_actions(tree))`` (analysis/utils.py:3-49) and scores F1 on (scripts/train.py:184-204).  One
         device-to-host copy, no recursion."""
         plan = self._plan
-        parts = []
         if plan.L < 2:                                   # one word: no constituent
             import numpy as np
             return np.zeros((plan.B * len(self._wss), 0, 2), dtype=np.int32)
-        for ws in self._wss:
+        return self.cky_spans_device().cpu().numpy()
+
+    def cky_spans_device(self, out=None):
+        """cky_spans left on the device: an int32 tensor (B, L-1, 2) on the chart's GPU, written into `out` when given (a contiguous
+        int32 tensor of that shape; cliora_amd.evaluate decodes into its batch's output buffer)."""
+        plan = self._plan
+        parts = []
+        for i, ws in enumerate(self._wss):
             with torch.cuda.device(ws.device):
-                spans = torch.empty((plan.B, plan.L - 1, 2), device=ws.device, dtype=torch.int32)
-                _lib.check(_lib.lib().cliora_cky_spans(plan.handle, _ptr(ws), None, _ptr(spans), _stream()), 'cliora_cky_spans')
+                if out is not None and len(self._wss) == 1:
+                    spans = out
+                    assert spans.shape == (plan.B, plan.L - 1, 2) and spans.dtype == torch.int32 and spans.is_contiguous()
+                else:
+                    spans = torch.empty((plan.B, plan.L - 1, 2), device=ws.device, dtype=torch.int32)
+                if plan.L > 1:
+                    _lib.check(_lib.lib().cliora_cky_spans(plan.handle, _ptr(ws), None, _ptr(spans), _stream()), 'cliora_cky_spans')
             parts.append(spans)
-        return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)).cpu().numpy()
+        if len(parts) == 1:
+            return parts[0]
+        res = torch.cat(parts, 0)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
 
     @staticmethod
     def trees_from_spans(spans):

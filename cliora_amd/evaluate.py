@@ -1,0 +1,242 @@
+"""Evaluation of a trained net the way the reference's parse script reports it (cliora/scripts/parse.py:101-291, run by
+test_cliora.sh): corpus and sentence span F1, phrase grounding accuracy, CCRA (gold noun phrases grounded correctly AND
+constituents of the predicted tree), the mean eval losses, and ``parse.jsonl`` with a ``pred_boxes`` field.
+
+The reference does the grounding as a host loop over every phrase and predicted span, each a ``.max()`` over a CPU copy of
+``atten_score`` plus a ``box_iou``.  Here one launch per batch does it on the device (include/cliora_chart.h: cliora_ground_eval),
+reading ``atten_score`` in place and the tree spans of the CKY decode where they were written; the host gets ONE copy of every
+output.  What stays on the host is what must be bitwise the reference's: the float formulas of the metrics (Python doubles,
+``SpanF1`` semantics, ``np.mean`` of the sentence F1s) and the order of the span sets in ``parse.jsonl``.
+
+    from cliora_amd.evaluate import evaluate
+    m = evaluate(net, batches, idx2word, out_path='parse.jsonl')     # net: harness.Net; batches: batch_map dicts
+    m['corpus_f1'], m['sent_f1'], m['ground_acc'], m['ccra']
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .interchange import SpanF1, parse_record
+
+METRICS = ('corpus_f1', 'sent_f1', 'ground_acc', 'ccra', 'recon_loss', 'vg_loss', 'contr_loss', 'total_loss')
+LOSS_NAMES = ('reconstruct_softmax_loss', 'vg_loss', 'contrastive_loss')     # harness.Net's loss names, as in the reference's Net
+
+
+# ---- inputs: VG_GT / GT as CSR tables -------------------------------------------------------------------------------
+class Targets(object):
+    """The gold phrases (VG_GT) and gold constituents (GT[b][:-1]) of one batch as CSR tables.
+
+    phrases: (sentence, start, end) per phrase, ``end`` exclusive, in the reference's order (the items of each sentence's dict);
+    phr_off (B+1), phr_span (P, 2), phr_box (P, 4) float32; gold_off (B+1), gold_span (G, 2); gold: the Python list per sentence."""
+
+    def __init__(self, vg_gt, gt, B, L):
+        self.B, self.L = B, L
+        self.phrases, spans, boxes = [], [], []
+        phr_off = [0]
+        for b in range(B):
+            if vg_gt is not None:
+                target, _noun_mask = vg_gt[b]
+                for _, anno in target.items():
+                    start, end, box = anno
+                    start, end = int(start), int(end)
+                    if not (0 <= start < end <= L):
+                        raise ValueError('sentence %d: phrase [%d, %d) is empty or outside the sentence of length %d' % (b, start, end, L))
+                    if len(box) != 4:
+                        raise ValueError('sentence %d: gold box %r is not (x1, y1, x2, y2)' % (b, box))
+                    self.phrases.append((b, start, end))
+                    spans.append((start, end))
+                    boxes.append([float(v) for v in box])
+            phr_off.append(len(spans))
+        self.gold = [list(gt[b][:-1]) for b in range(B)] if gt is not None else [[] for _ in range(B)]
+        gold_off, gold_span = [0], []
+        for g in self.gold:
+            gold_span.extend((int(s), int(e)) for s, e in g)
+            gold_off.append(len(gold_span))
+        self.phr_off = np.array(phr_off, dtype=np.int32)
+        self.phr_span = np.array(spans, dtype=np.int32).reshape(-1, 2)
+        self.phr_box = np.array(boxes, dtype=np.float32).reshape(-1, 4)
+        self.gold_off = np.array(gold_off, dtype=np.int32)
+        self.gold_span = np.array(gold_span, dtype=np.int32).reshape(-1, 2)
+
+    @property
+    def P(self):
+        return len(self.phrases)
+
+    @property
+    def G(self):
+        return len(self.gold_span)
+
+    def packed(self):
+        """The five tables as one int32 array (the boxes' bits included): one host-to-device copy."""
+        return np.concatenate([self.phr_off, self.phr_span.ravel(), self.phr_box.view(np.int32).ravel(), self.gold_off,
+                               self.gold_span.ravel()])
+
+
+# ---- outputs ------------------------------------------------------------------------------------------------------------
+class GroundResult(object):
+    """Host view of one batch's outputs: spans (B, L-1, 2) the tree spans, root last; per phrase word / box / hit / ccr (P,);
+    sent (B, 3) = |pred & gold|, |pred|, |gold| over span sets (pred without its root); span_xyxy (B, L-1, 4) float32, the box of
+    every predicted span, or None (text-only DIORA)."""
+
+    def __init__(self, targets, spans, phr, sent, span_xyxy):
+        self.targets, self.phrases = targets, targets.phrases
+        self.spans, self.sent, self.span_xyxy = spans, sent, span_xyxy
+        phr = np.asarray(phr, dtype=np.int32).reshape(-1, 4)
+        self.word, self.box, self.hit, self.ccr = phr[:, 0], phr[:, 1], phr[:, 2], phr[:, 3]
+
+
+def ground_batch(diora, batch_map, spans=None):
+    """cliora_ground_eval for the batch the chart module last ran on: packs batch_map's VG_GT / GT into CSR tables, launches once
+    on the current stream and copies every output back in one transfer.  `spans`: the (B, L-1, 2) int32 device spans of
+    ``diora.cky_spans_device()``; None decodes them here, into the output buffer.  Text-only DIORA (``atten_score`` None): F1 counts
+    only, the phrases are not read (the reference skips them too)."""
+    plan = diora._plan
+    B, L = plan.B * len(diora._wss), plan.L
+    atten = getattr(diora, 'atten_score', None)
+    tg = Targets(batch_map.get('VG_GT') if atten is not None else None, batch_map.get('GT'), B, L)
+    boxes = batch_map['boxes'] if atten is not None else None
+    return ground(atten, boxes, tg, spans if spans is not None else diora.cky_spans_device, device=diora._wss[0].device)
+
+
+def ground(atten, boxes, targets, spans, device=None):
+    """One cliora_ground_eval launch.  atten: (B, L, R) fp32 CUDA tensor, any strides (None: counts only); boxes (B, R, 4); targets:
+    a Targets; spans: (B, L-1, 2) int32 device tensor, or a callable that writes them into the tensor it is given (the decode)."""
+    B, L = targets.B, targets.L
+    P, G, NS = targets.P, targets.G, L - 1
+    R = atten.shape[2] if atten is not None else 0
+    dev = atten.device if atten is not None else device
+    lib = _lib.lib()
+    if not hasattr(lib, 'cliora_ground_eval'):
+        raise _lib.ChartLibError('%s has no cliora_ground_eval: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
+    # output buffer: [status | sent B*3 | phrases P*4 | spans B*NS*2 | span boxes B*NS*4 (fp32 bits)]
+    sizes = [1, B * 3, P * 4, B * NS * 2, B * NS * 4 if atten is not None else 0]
+    offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+    with torch.cuda.device(dev):
+        out = torch.empty(offs[-1], device=dev, dtype=torch.int32)
+        sec = [out[offs[i]:offs[i + 1]] for i in range(len(sizes))]
+        d_spans = sec[3].view(B, NS, 2)
+        if callable(spans):
+            spans(out=d_spans)
+        else:
+            d_spans.copy_(spans)
+        tab = torch.from_numpy(targets.packed()).to(dev)
+        o = np.cumsum([0, B + 1, P * 2, P * 4, B + 1, G * 2]).tolist()
+        phr_off, phr_span, phr_box, gold_off, gold_span = (tab[o[i]:o[i + 1]] for i in range(5))
+        if atten is not None:
+            boxes = boxes.to(device=dev, dtype=torch.float32).contiguous()
+            if atten.shape != (B, L, R) or atten.dtype != torch.float32 or boxes.shape != (B, R, 4):
+                raise ValueError('atten_score %s / boxes %s do not match B %d, L %d' % (tuple(atten.shape), tuple(boxes.shape), B, L))
+            sb, sl, sr = atten.stride()
+        else:
+            boxes, sb, sl, sr = None, 0, 0, 0
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+        _lib.check(lib.cliora_ground_eval(B, L, R, p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span), p(phr_box), p(d_spans), G,
+                                          p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]), p(sec[1]), p(sec[0]),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cliora_ground_eval')
+        host = out.cpu().numpy()
+    h = [host[offs[i]:offs[i + 1]] for i in range(len(sizes))]
+    if h[0][0]:
+        raise _lib.ChartLibError('cliora_ground_eval rejected %d phrase(s) / span(s) outside their sentence' % int(h[0][0]))
+    xyxy = h[4].view(np.float32).reshape(B, NS, 4) if atten is not None else None
+    return GroundResult(targets, h[3].reshape(B, NS, 2), h[2], h[1].reshape(B, 3), xyxy)
+
+
+# ---- accumulation and the reference's formulas --------------------------------------------------------------------------
+class Evaluator(object):
+    """Accumulates the numbers parse.py:run reports (parse.py:146-264) over batches; ``result()`` applies its formulas (:282-291)."""
+
+    def __init__(self):
+        self.f1 = SpanF1()
+        self.recall_num = self.ccr_num = self.total_num = 0.
+        self.num_data = 0
+        self._loss = None            # float64 device sums: recon, vg, contrastive, total
+
+    def add_losses(self, out):
+        """One batch's Net.forward(..., compute_loss=True) output: summed on the device, read once by result()."""
+        if not hasattr(out, 'parts'):
+            raise TypeError('add_losses wants the LossDict of harness.Net.forward(..., compute_loss=True)')
+        tot = out.total()
+        zero = torch.zeros((), device=tot.device, dtype=torch.float32)
+        row = torch.stack([out[n].reshape(()) if n in out else zero for n in LOSS_NAMES] + [tot.reshape(())]).double()
+        self._loss = row if self._loss is None else self._loss + row
+        self.num_data += 1
+
+    def add_counts(self, sent, hit=(), ccr=()):
+        """Per sentence (tp, |pred|, |gold|); per phrase the hit and ccr flags."""
+        for tp, npred, ngold in np.asarray(sent).reshape(-1, 3).tolist():
+            self.f1.add_counts(tp, npred, ngold)
+        hit = np.asarray(hit).reshape(-1)
+        self.recall_num += int(hit.sum())
+        self.ccr_num += int(np.asarray(ccr).sum())
+        self.total_num += hit.size
+
+    def add(self, res):
+        self.add_counts(res.sent, res.hit, res.ccr)
+
+    def losses(self):
+        if self._loss is None:
+            return [float('nan')] * 4
+        return [v / self.num_data for v in self._loss.cpu().tolist()]
+
+    def result(self):
+        tp, fp, fn = self.f1.tp, self.f1.fp, self.f1.fn
+        prec = tp / (tp + fp) if tp + fp else 0.
+        recall = tp / (tp + fn) if tp + fn else 0.
+        corpus_f1 = 2 * prec * recall / (prec + recall) if prec + recall > 0 else 0.
+        sent_f1 = float(np.mean(np.array(self.f1.sentence))) if self.f1.sentence else float('nan')
+        ground_acc = self.recall_num / (self.total_num + 1e-8)
+        ccra = self.ccr_num / (self.total_num + 1e-8)
+        return dict(zip(METRICS, [corpus_f1, sent_f1, ground_acc, ccra] + self.losses()))
+
+
+def batch_records(res, trees, sentences, example_ids, idx2word, with_boxes, post=False):
+    """The batch's parse.jsonl lines (parse.py:215-280).  pred_spans / gold_spans in the iteration order of the reference's Python
+    sets, built the same way (from the span list in reduce order, from GT[b][:-1]); pred_boxes in the order of pred_spans."""
+    lines = []
+    spans = res.spans.tolist()
+    for b, tree in enumerate(trees):
+        order = [tuple(s) for s in spans[b][:-1]]
+        pred = set(order)
+        gold = set(res.targets.gold[b])
+        boxes = []
+        if with_boxes:
+            first = {}
+            for k, s in enumerate(order):
+                first.setdefault(s, k)
+            boxes = [res.span_xyxy[b, first[s]].tolist() for s in pred]
+        words = [idx2word[i] for i in sentences[b]]
+        lines.append(parse_record(example_ids[b], tree, words, gold, pred, boxes, post=post))
+    return lines
+
+
+def evaluate(net, batches, idx2word, out_path=None, postprocess=False):
+    """parse.py:run (lines 101-291) on a harness.Net: eval mode, outside pass on, batches of length <= 2 skipped; returns the eight
+    numbers it prints (METRICS) and writes parse.jsonl to `out_path` when given."""
+    diora = net.diora
+    diora.outside = True
+    net.eval()
+    ev = Evaluator()
+    dev = next(net.parameters()).device
+    f = open(out_path, 'w') if out_path else None
+    try:
+        with torch.no_grad():
+            for bm in batches:
+                sentences = bm['sentences']
+                if sentences.shape[1] <= 2:
+                    continue
+                obj = bm.get('obj_feats') if net.obj_feats else None
+                out = net(sentences.to(dev), obj.to(dev) if obj is not None else None, bm['neg_samples'].to(dev), compute_loss=True)
+                ev.add_losses(out)
+                res = ground_batch(diora, bm)
+                ev.add(res)
+                if f is not None:
+                    trees = diora.trees_from_spans(res.spans)
+                    with_boxes = getattr(diora, 'all_atten_score', None) is not None
+                    for line in batch_records(res, trees, sentences.cpu().tolist(), bm['example_ids'], idx2word, with_boxes, postprocess):
+                        f.write(line + '\n')
+    finally:
+        if f is not None:
+            f.close()
+    return ev.result()

@@ -144,18 +144,21 @@ class SpanF1(object):
     def add(self, tree, gold_spans):
         pred = set(tree_spans(tree)[:-1])
         gold = set(gold_spans)
-        hit = len(pred & gold)
+        self.add_counts(len(pred & gold), len(pred), len(gold))
+        return pred
+
+    def add_counts(self, hit, npred, ngold):
+        """One sentence given |pred & gold|, |pred| and |gold| (cliora_ground_eval's per-sentence counts)."""
         self.tp += hit
-        self.fp += len(pred) - hit
-        self.fn += len(gold) - hit
-        prec = float(hit) / (len(pred) + 1e-8)
-        reca = float(hit) / (len(gold) + 1e-8)
-        if not gold:
+        self.fp += npred - hit
+        self.fn += ngold - hit
+        prec = float(hit) / (npred + 1e-8)
+        reca = float(hit) / (ngold + 1e-8)
+        if not ngold:
             reca = 1.
-            if not pred:
+            if not npred:
                 prec = 1.
         self.sentence.append(2 * prec * reca / (prec + reca + 1e-8))
-        return pred
 
     @property
     def corpus_f1(self):

@@ -288,6 +288,29 @@ int cliora_cky_decode(cliora_plan* plan, void* fwd_workspace, int32_t* split_out
  * device-to-host copy of B*(L-1)*2 ints and no recursion over a split table.  split_out: as cliora_cky_decode, or NULL. */
 int cliora_cky_spans(cliora_plan* plan, void* fwd_workspace, int32_t* split_out, int32_t* spans_out, void* stream);
 
+/* Grounding evaluation (cliora/scripts/parse.py:176-264, the host loop over every phrase and predicted span): ONE launch for a batch,
+ * one workgroup per sentence.  All pointers are device memory.
+ *   atten (B, L, R) fp32 at element strides (sb, sl, sr) -- DioraMLP.atten_score, a permuted diagonal of vg_atten_score, read in
+ *     place; boxes (B, R, 4) fp32 xyxy, contiguous.  atten == NULL (text-only DIORA): counts only, P must be 0.
+ *   gold phrases, CSR: phr_off (B+1), phr_span (P, 2) = (start, end) with `end` exclusive as VG_GT stores it, phr_box (P, 4) gold box.
+ *   spans (B, L-1, 2): cliora_cky_spans' output, the root last.  gold constituents, CSR: gold_off (B+1), gold_span (G, 2)
+ *     (batch_map['GT'][b][:-1]; duplicates allowed).
+ * Box of a word range [s, e): the first word whose maximum over the regions is the largest, then the first region of that word's row
+ * attaining it (torch's CPU max(dim); a NaN is larger than every number).  IoU: torchvision's box_iou in fp32 and in its operation
+ * order; hit = IoU > 0.5 (a 0/0 is NaN: no hit).  CCRA flag = hit and (end - 1 == start, or (start, end - 1) is a predicted span other
+ * than the root).
+ *   phr_out (P, 4) int32: selected word, selected box, hit, ccr.  A phrase outside 0 <= start < end <= L is not read (the reference
+ *     raises on its empty slice): it gets (-1, -1, 0, 0) and is counted in *status, which the caller must check (an int32 the call
+ *     zeroes first; predicted spans outside the sentence count there too).
+ *   span_box (B, L-1) int32 / span_xyxy (B, L-1, 4) fp32, either NULL: the box id / coordinates chosen for each predicted span
+ *     over its words (the root's too; the reference writes boxes for the non-root spans only).
+ *   sent_out (B, 3) int32: |pred & gold|, |pred|, |gold| over span SETS, pred without the root -- the integers of the span F1; its
+ *     float formulas stay with the caller (SpanF1 semantics, parse.py:215-234). */
+int cliora_ground_eval(int B, int L, int R, const float* atten, int64_t atten_sb, int64_t atten_sl, int64_t atten_sr,
+                       const float* boxes, int P, const int32_t* phr_off, const int32_t* phr_span, const float* phr_box,
+                       const int32_t* spans, int G, const int32_t* gold_off, const int32_t* gold_span, int32_t* phr_out,
+                       int32_t* span_box, float* span_xyxy, int32_t* sent_out, int32_t* status, void* stream);
+
 /* Optional HIP-event timing of one kernel class (used by bench.py for the roofline
  * line): enable, run steps, then read the accumulated device time and launch count. */
 int cliora_prof_enable(int kernel_class, int on);
