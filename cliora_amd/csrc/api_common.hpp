@@ -79,11 +79,6 @@ static inline int fail(int code, const std::string& msg) { g_cliora_err = msg; r
         if (ev) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, nullptr, ev, 0, __VA_ARGS__);          \
         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                \
     } while (0)
-// CLIORA_STOP_EVENT=0: every event by hipEventRecord
-static bool stop_events_on() {
-    static const bool on = [] { const char* e = getenv("CLIORA_STOP_EVENT"); return !e || atoi(e) != 0; }();
-    return on;
-}
 
 // kernels that need more than 64 KiB of dynamic LDS: the attribute is per device, so it is set once per (function, device)
 int cliora_ensure_max_lds(const void* fn);
@@ -215,13 +210,13 @@ static int launch_ksplit_tile(hipStream_t st, const float* W, int K, int nt, int
     LAUNCHOK("rows_gemm_ksplit");
     return CLIORA_OK;
 }
-static int g_ksplit_min_blocks = -1;   // per translation unit (read from the environment once each)
+// blocks a split-K launch must have to take the wider tile: MI355X sweep 0..2000: 5.61 ms/step at 0, 5.44 at 160, 5.37 at 1000
+constexpr int KSPLIT_MIN_BLOCKS = 1000;
 template <int CT, bool FRAG, class AP, class EP>
 static int launch_ksplit_ct(hipStream_t st, const float* W, int K, int nt, int nrows, AP ap, EP ep) {
-    if (g_ksplit_min_blocks < 0) { const char* e = getenv("CLIORA_KSPLIT_MIN_BLOCKS"); g_ksplit_min_blocks = e ? atoi(e) : 1000; }   // MI355X sweep 0..2000: 5.61 ms/step at 0, 5.44 at 160, 5.37 at 1000
     const int nrt = (nrows + 15) / 16;
-    if (((nrt + 1) / 2) * (nt / CT) >= g_ksplit_min_blocks) return launch_ksplit_tile<2, CT, FRAG>(st, W, K, nt, nrows, ap, ep);
-    if (CT == 1 || nrt * (nt / CT) >= g_ksplit_min_blocks) return launch_ksplit_tile<1, CT, FRAG>(st, W, K, nt, nrows, ap, ep);
+    if (((nrt + 1) / 2) * (nt / CT) >= KSPLIT_MIN_BLOCKS) return launch_ksplit_tile<2, CT, FRAG>(st, W, K, nt, nrows, ap, ep);
+    if (CT == 1 || nrt * (nt / CT) >= KSPLIT_MIN_BLOCKS) return launch_ksplit_tile<1, CT, FRAG>(st, W, K, nt, nrows, ap, ep);
     return launch_ksplit_tile<1, 1, FRAG>(st, W, K, nt, nrows, ap, ep);
 }
 template <bool FRAG, class AP, class EP>
@@ -332,28 +327,22 @@ static int launch_tn_pairs_inst(hipStream_t st, const float* DZ, const float* X,
     const size_t lds3 = (size_t)2 * TN3_RS * (Dp + NJT * 16) * sizeof(float) + (size_t)NJT * 2048;   // two fp32 stages + the split column fragments
     const bool strided = ldz != Dp || ldx != Dp;           // operands that are column blocks of wider matrices: the eight-wave kernel only
     if (split_bf16() && lds3 <= 160 * 1024 && (Dp + NJT * 16) / 32 <= TN3_NP) {
-        OKR(cliora_ensure_max_lds((const void*)tn_gemm_dma3<NIT, NJT, true>));
         // whole groups of 8 slices (one per XCD), all resident at once: one workgroup per CU, no second round -- and a tenth of the CUs
         // left to the small weight-gradient GEMMs of the side stream, which otherwise queue up behind this kernel (a workgroup of it fills
         // a CU's registers): measured at c2 with 80 / 72 / 64 / 56 slices: 3.566 / 3.538 / 3.539 / 3.576 ms per step
-        static const int cap_env = [] { const char* e = getenv("CLIORA_WGRAD_SLICES"); return e ? atoi(e) : 0; }();
-        const int nsl_cap = slices_cap > 0 ? slices_cap : cap_env > 0 ? cap_env : std::max(1, 230 / (8 * nkb)) * 8;
+        const int nsl_cap = slices_cap > 0 ? slices_cap : std::max(1, 230 / (8 * nkb)) * 8;
         if (nsl > nsl_cap) { nsl = nsl_cap; rps = (nrows + nsl - 1) / nsl; }
         rps = (rps + TN3_RS - 1) / TN3_RS * TN3_RS;
         nsl = (nrows + rps - 1) / rps;
         csl = slab + (size_t)nsl * Dp * Dp;
-        static const bool eight = [] { const char* e = getenv("CLIORA_WGRAD_WAVES"); return !e || atoi(e) != 4; }();
-        bool launched = false;
         if constexpr (NIT == 7 && NJT == 9) {              // d = 400: two waves per SIMD, each with half of the block's j-tiles
-            if (eight) {                                   // (the second half has at most NJT - 5 = 4 of its 5 slots taken: the spare one holds the ones-tile)
-                OKR(cliora_ensure_max_lds((const void*)tn_gemm_dma3x<NIT, NJT, 5, true>));
-                hipLaunchKernelGGL((tn_gemm_dma3x<NIT, NJT, 5, true>), dim3(8 * nkb * ((nsl + 7) / 8)), dim3(512), lds3, st, DZ, ldz, X, ldx, nrows, rps, nsl, Dp, Dp, nkb, slab, csl);
-                LAUNCHOK("tn_gemm_dma3x");
-                launched = true;
-            }
-        }
-        if (!launched) {
+            // (the second half has at most NJT - 5 = 4 of its 5 slots taken: the spare one holds the ones-tile)
+            OKR(cliora_ensure_max_lds((const void*)tn_gemm_dma3x<NIT, NJT, 5, true>));
+            hipLaunchKernelGGL((tn_gemm_dma3x<NIT, NJT, 5, true>), dim3(8 * nkb * ((nsl + 7) / 8)), dim3(512), lds3, st, DZ, ldz, X, ldx, nrows, rps, nsl, Dp, Dp, nkb, slab, csl);
+            LAUNCHOK("tn_gemm_dma3x");
+        } else {
             if (strided) return fail(CLIORA_EINVAL, "strided operands need the eight-wave weight-gradient kernel (tn_pairs_strided_ok)");
+            OKR(cliora_ensure_max_lds((const void*)tn_gemm_dma3<NIT, NJT, true>));
             hipLaunchKernelGGL((tn_gemm_dma3<NIT, NJT, true>), dim3(8 * nkb * ((nsl + 7) / 8)), dim3(256), lds3, st, DZ, X, nrows, rps, nsl, Dp, Dp, nkb, slab, csl);
             LAUNCHOK("tn_gemm_dma3");
         }
@@ -373,10 +362,8 @@ static int launch_tn_pairs_inst(hipStream_t st, const float* DZ, const float* X,
 // The eight-wave d = 400 kernel over TWO row ranges of the pair rows in one launch (rows [0, n1) and n2 rows from row `start2`): one
 // slab and one reduction.  false: this shape has no such kernel (the caller launches the ranges one after the other).
 static bool tn_pairs_two_ranges_ok(int Dp) {
-    static const bool eight = [] { const char* e = getenv("CLIORA_WGRAD_WAVES"); return !e || atoi(e) != 4; }();
-    static const bool off = [] { const char* e = getenv("CLIORA_WGRAD_TAIL_MERGED"); return e && atoi(e) == 0; }();
     const int NT = Dp / 16;
-    return split_bf16() && eight && !off && NT > 20 && NT <= 27;
+    return split_bf16() && NT > 20 && NT <= 27;
 }
 static int launch_tn_pairs_two_ranges(hipStream_t st, const float* DZ, const float* X, int n1, long long start2, int n2, int Dp, float* slab,
                                       size_t slab_floats, float* out, float* colsum_out, int slices_cap) {
@@ -400,13 +387,12 @@ static int launch_tn_pairs_two_ranges(hipStream_t st, const float* DZ, const flo
     return CLIORA_OK;
 }
 
-// out[i][j] (+)= sum over the cells [off, off + hi) of every sentence of A[cell][acol0 + i] * Bm[cell][j] (i, j < Dp; A of row stride lda,
-// Bm of row stride Dp; colsum_out (+)= the column sums of that A block): one block of the projections' weight gradient on the
-// eight-wave split-bf16 kernel, the rows remapped inside it.  Only where tn_pairs_strided_ok(Dp).
-// nblk > 1 (round 4): the blocks acol0, acol0 + Dp, ... of A in ONE launch (gridDim.y) and one reduction -- out / colsum_out are then
-// nblk consecutive Dp x Dp / Dp outputs.
-static int launch_tn_level_block(hipStream_t st, const float* A, int lda, int acol0, const float* Bm, int nsent, int C, int off, int hi, int Dp,
-                                 float* slab, size_t slab_floats, float* out, float* colsum_out, int accumulate, int slices_cap, int nblk = 1) {
+// For each of the nblk column blocks k of A: out_k[i][j] (+)= sum over the cells [off, off + hi) of every sentence of A[cell][k Dp + i] *
+// Bm[cell][j] (i, j < Dp; A of row stride lda, Bm of row stride Dp; colsum_out_k (+)= the column sums of that A block) -- the
+// projections' weight gradient on the eight-wave split-bf16 kernel, the rows remapped inside it, every block in ONE launch (gridDim.y)
+// and one reduction (round 4); out / colsum_out are nblk consecutive Dp x Dp / Dp outputs.  Only where tn_pairs_strided_ok(Dp).
+static int launch_tn_level_block(hipStream_t st, const float* A, int lda, const float* Bm, int nsent, int C, int off, int hi, int Dp,
+                                 float* slab, size_t slab_floats, float* out, float* colsum_out, int accumulate, int slices_cap, int nblk) {
     constexpr int NIT = 7, NJT = 9, nkb = 3;
     const int nrows = nsent * hi;
     if (nrows <= 0) return CLIORA_OK;
@@ -419,7 +405,7 @@ static int launch_tn_level_block(hipStream_t st, const float* A, int lda, int ac
     const int nsl = (nrows + rps - 1) / rps;
     float* csl = slab + (size_t)nsl * nblk * Dp * Dp;
     OKR(cliora_ensure_max_lds((const void*)tn_gemm_dma3x<NIT, NJT, 5, true>));
-    hipLaunchKernelGGL((tn_gemm_dma3x<NIT, NJT, 5, true>), dim3(8 * nkb * ((nsl + 7) / 8), nblk), dim3(512), lds3, st, A + acol0, lda, Bm, Dp, nrows, rps, nsl,
+    hipLaunchKernelGGL((tn_gemm_dma3x<NIT, NJT, 5, true>), dim3(8 * nkb * ((nsl + 7) / 8), nblk), dim3(512), lds3, st, A, lda, Bm, Dp, nrows, rps, nsl,
                        Dp, Dp, nkb, slab, csl, 0x7fffffff, 0, 0LL, hi, C, off, (long long)Dp);
     LAUNCHOK("tn_gemm_dma3x(level rows)");
     launch_slab_reduce(st, slab, nsl, (size_t)nblk * Dp * Dp, out, accumulate, csl, (size_t)nblk * Dp, colsum_out);
@@ -430,8 +416,7 @@ static int launch_tn_level_block(hipStream_t st, const float* A, int lda, int ac
 // The pair rows' weight gradient from the TILED split-bf16 operands (wgrad_tiles.hpp): tiles [tile0, tile0 + ntiles) and, in the same
 // launch, [tile0b, tile0b + ntilesb).  Only where pair_tiles_ok(Dp).
 static bool pair_tiles_ok(int Dp) {
-    static const bool off = [] { const char* e = getenv("CLIORA_PAIR_TILES"); return e && atoi(e) == 0; }();
-    return !off && split_bf16() && Dp == 400;      // the <7, 9, 5> instance and level_compose_bwd's <5, 25> instance
+    return split_bf16() && Dp == 400;      // the <7, 9, 5> instance and level_compose_bwd's <5, 25> instance
 }
 static int launch_tn_tiles(hipStream_t st, const float* DZt, const float* Xt, long long tile0, long long ntiles, long long tile0b, long long ntilesb,
                            int Dp, float* slab, size_t slab_floats, float* out, float* colsum_out, int accumulate, int slices_cap) {
@@ -455,12 +440,9 @@ static int launch_tn_tiles(hipStream_t st, const float* DZt, const float* Xt, lo
     const int nsl = (int)(s1 + s2);
     float* csl = slab + (size_t)nsl * Dp * Dp;
     const size_t lds = (size_t)2 * 2048 * (NT + NJT) + 1024;  // two stage buffers + the spare KiB the last X slot reads into
-    // the next stage's LDS-DMA: 0 = two pieces beside each row tile's MFMAs, 1 = all of it right behind the barrier (the kernel alone at
-    // L 40: 2.30 / 2.48 ms; c2 step 3.21 / 3.24 ms)
-    static const int issue_mode = [] { const char* e = getenv("CLIORA_TILES_ISSUE"); return e ? atoi(e) : 0; }();
     OKR(cliora_ensure_max_lds((const void*)tn_gemm_tiles<NTc, NIT, NJT, NJW, true>));
     hipLaunchKernelGGL((tn_gemm_tiles<NTc, NIT, NJT, NJW, true>), dim3(8 * nkb * ((nsl + 7) / 8)), dim3(512), lds, st, reinterpret_cast<const uint32_t*>(DZt),
-                       reinterpret_cast<const uint32_t*>(Xt), tile0, (int)ntiles, (int)tps, nsl, nkb, slab, csl, (int)s1, tile0b, (int)ntilesb, issue_mode);
+                       reinterpret_cast<const uint32_t*>(Xt), tile0, (int)ntiles, (int)tps, nsl, nkb, slab, csl, (int)s1, tile0b, (int)ntilesb);
     LAUNCHOK("tn_gemm_tiles");
     launch_slab_reduce(st, slab, nsl, (size_t)Dp * Dp, out, accumulate, csl, (size_t)Dp, colsum_out);
     LAUNCHOK("slab_reduce");
@@ -470,9 +452,8 @@ static int launch_tn_tiles(hipStream_t st, const float* DZt, const float* Xt, lo
 // accumulate: add to out / colsum_out instead of overwriting; slices_cap > 0: at most that many row slices (= workgroups / nkb)
 // ldz / ldx: row strides of DZ / X when they are Dp-wide column blocks of wider matrices (0: Dp); only where tn_pairs_strided_ok()
 static bool tn_pairs_strided_ok(int Dp) {
-    static const bool eight = [] { const char* e = getenv("CLIORA_WGRAD_WAVES"); return !e || atoi(e) != 4; }();
     const int NT = Dp / 16;
-    return split_bf16() && eight && NT > 20 && NT <= 27;       // the <7, 9> instance: d = 400
+    return split_bf16() && NT > 20 && NT <= 27;       // the <7, 9> instance: d = 400
 }
 static int launch_tn_pairs(hipStream_t st, const float* DZ, const float* X, int nrows, int Dp, float* slab, size_t slab_floats,
                            float* out, float* colsum_out, int accumulate = 0, int slices_cap = 0, int ldz = 0, int ldx = 0) {
@@ -667,11 +648,8 @@ static Dev dev_views(const Plan& p) {
     return d;
 }
 
-// sentence-affine block order of the one-workgroup-per-cell kernels (chart_kernels.hpp: cell_of_block); CLIORA_XCD_AFFINE=0: off
-static int xcd_affine() { static const int v = [] { const char* e = getenv("CLIORA_XCD_AFFINE"); return e ? atoi(e) : 1; }(); return v; }
 static LevelArgs level_args(const Plan& p, int level, bool outside_pass) {
     LevelArgs g;
-    g.affine = xcd_affine();
     g.B = p.B; g.C = p.C; g.Dp = p.Dp; g.Lc = p.L - level;
     g.N = outside_pass ? p.Nout(level) : p.Nin(level);
     g.off = p.level_offset[level];

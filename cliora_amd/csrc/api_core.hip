@@ -199,13 +199,9 @@ static int device_lanes(int dev, hipStream_t st, DeviceLanes** out) {
         busy[1] = ln->side;
         OKR(pick_concurrent_stream(busy, 2, &ln->side2, &ln->side2_beside));
         // The fork / join / level events order kernels of ONE device against each other, so a device-scope release at the record
-        // would do (CLIORA_EVENT_SCOPE=device: hipEventReleaseToDevice instead of the default system-scope release).  Measured on
-        // MI355X at c2 (round 4, tools/ab/env_ab.sh, three alternations): 3.512 / 3.547 / 3.528 ms (system) against 3.526 / 3.549 /
-        // 3.567 (device) -- no gain, so the default stays.
-        static const unsigned ev_flags = [] {
-            const char* e = getenv("CLIORA_EVENT_SCOPE");
-            return (unsigned)hipEventDisableTiming | ((e && !strcmp(e, "device")) ? (unsigned)hipEventReleaseToDevice : 0u);
-        }();
+        // would do (hipEventReleaseToDevice instead of the default system-scope release).  Measured on MI355X at c2 (round 4, three
+        // alternations): 3.512 / 3.547 / 3.528 ms (system) against 3.526 / 3.549 / 3.567 (device) -- no gain, so the default stays.
+        constexpr unsigned ev_flags = hipEventDisableTiming;
         for (int k = 0; k < 3; ++k) {
             HIPOK(hipEventCreateWithFlags(&ln->fork[k], ev_flags));
             HIPOK(hipEventCreateWithFlags(&ln->join[k], ev_flags));

@@ -137,39 +137,28 @@ static int launch_level_project(hipStream_t st, int SP, const float* Wfrag, int 
                                 size_t hp_stride, int normalize, const float* bias, float* P, int ldp, float* H, float* nrm, const ScoreArgs& sc,
                                 hipEvent_t stop = nullptr) {
     const int nt = ncols / 16, nrt = (ncell + 15) / 16;
-    if (g_ksplit_min_blocks < 0) { const char* e = getenv("CLIORA_KSPLIT_MIN_BLOCKS"); g_ksplit_min_blocks = e ? atoi(e) : 1000; }
     // a block's MFMA work and operand bytes are fixed by its tile: wide tiles only when the launch still covers the chip
-    if (nt % 5 == 0 && nrt * (nt / 5) >= g_ksplit_min_blocks)
+    if (nt % 5 == 0 && nrt * (nt / 5) >= KSPLIT_MIN_BLOCKS)
         return launch_level_project_sp<5>(st, SP, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
     return launch_level_project_sp<1>(st, SP, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
 }
 
 // ---- the two passes' launches of one wavefront step as ONE grid each (level_compose_fwd2 / level_project2), on the caller's stream
-// CLIORA_COMPOSE_DUAL = ring depth of the two-splits-per-wave compose (level_kernels.hpp: compose_fwd_tasks_dual), 0: one split per wave
-static int compose_dual_pd() { static const int d = [] { const char* e = getenv("CLIORA_COMPOSE_DUAL"); return e ? atoi(e) : 2; }(); return d; }
 template <int CT, int K16, bool F32>
 static int launch_level_compose2_inst(hipStream_t st, const ComposeSeg& a, const ComposeSeg& b, int S, int K, int ncb, const float* Pp,
                                       size_t hp_stride, int Dp, uint32_t* ymask, float* Y) {
     int gx = a.gx + b.gx;
     if (gx >= 8) gx = (gx + 7) / 8 * 8;            // padding blocks return at once; column blocks of one x share an XCD (linear id = x + y * gx)
-    if constexpr (K16 == 25 && !F32) {             // the d = 400 split-bf16 instance only
+    if constexpr (K16 == 25 && !F32) {             // the d = 400 split-bf16 instance: two splits per wave, two ring slots each (compose_fwd_tasks_dual)
         const size_t lds_dual = compose_lds_bytes(CT, S, true) + (size_t)CT * 16 * sizeof(float);
-        if (compose_dual_pd() == 2) {
-            OKR(cliora_ensure_max_lds((const void*)level_compose_fwd2<CT, K16, F32, 2>));
-            hipLaunchKernelGGL((level_compose_fwd2<CT, K16, F32, 2>), dim3(gx, ncb), dim3(512), lds_dual, st, a, b, S, K, Pp, hp_stride, Dp, ymask, Y);
-            LAUNCHOK("level_compose_fwd2(dual 2)");
-            return CLIORA_OK;
-        }
-        if (compose_dual_pd() == 3) {
-            OKR(cliora_ensure_max_lds((const void*)level_compose_fwd2<CT, K16, F32, 3>));
-            hipLaunchKernelGGL((level_compose_fwd2<CT, K16, F32, 3>), dim3(gx, ncb), dim3(512), lds_dual, st, a, b, S, K, Pp, hp_stride, Dp, ymask, Y);
-            LAUNCHOK("level_compose_fwd2(dual 3)");
-            return CLIORA_OK;
-        }
+        OKR(cliora_ensure_max_lds((const void*)level_compose_fwd2<CT, K16, F32, 2>));
+        hipLaunchKernelGGL((level_compose_fwd2<CT, K16, F32, 2>), dim3(gx, ncb), dim3(512), lds_dual, st, a, b, S, K, Pp, hp_stride, Dp, ymask, Y);
+        LAUNCHOK("level_compose_fwd2(dual)");
+    } else {
+        OKR(cliora_ensure_max_lds((const void*)level_compose_fwd2<CT, K16, F32>));
+        hipLaunchKernelGGL((level_compose_fwd2<CT, K16, F32>), dim3(gx, ncb), dim3(512), compose_lds_bytes(CT, S, true), st, a, b, S, K, Pp, hp_stride, Dp, ymask, Y);
+        LAUNCHOK("level_compose_fwd2");
     }
-    OKR(cliora_ensure_max_lds((const void*)level_compose_fwd2<CT, K16, F32>));
-    hipLaunchKernelGGL((level_compose_fwd2<CT, K16, F32>), dim3(gx, ncb), dim3(512), compose_lds_bytes(CT, S, true), st, a, b, S, K, Pp, hp_stride, Dp, ymask, Y);
-    LAUNCHOK("level_compose_fwd2");
     return CLIORA_OK;
 }
 // a.Wimg / b.Wimg: the pass's plain fp32 W2 in the exact mode, its split-bf16 image otherwise (the caller picks by split_bf16())
@@ -190,23 +179,11 @@ static int launch_level_compose2(hipStream_t st, const ComposeSeg& a, const Comp
 #undef LC2_CASE
 #undef LC2_ARGS
 }
-// diagnostics (timing experiments, WRONG results; only in a build with -DCLIORA_DIAG_P2, tools/ab/build_variant.sh -- the shipped library
-// ignores the variable): CLIORA_P2_DIAG bit 0: no score blocks, bit 1: no projection blocks
-#ifdef CLIORA_DIAG_P2
-static int p2_diag() { static const int d = [] { const char* e = getenv("CLIORA_P2_DIAG"); return e ? atoi(e) : 0; }(); return d; }
-#else
-static constexpr int p2_diag() { return 0; }
-#endif
 template <int SP0, int SP1>
-static int launch_level_project2_inst(hipStream_t st, const ProjSeg& a_, const ProjSeg& b_) {
-    ProjSeg a = a_, b = b_;
-    if (p2_diag() & 1) { a.sc.nscore = 0; b.sc.nscore = 0; }
-    if (p2_diag() & 2) { a.nproj = 0; b.nproj = 0; }
+static int launch_level_project2_inst(hipStream_t st, const ProjSeg& a, const ProjSeg& b) {
     const int n = a.sc.nscore + b.sc.nscore + a.nproj + b.nproj + a.nfin + b.nfin;
     if (n <= 0) return CLIORA_OK;
-    // block order: 1 = the projection blocks first, the score blocks behind them (measured 24.05 -> 22.97 us per launch at c2; 0 = scores first)
-    static const int order = [] { const char* e = getenv("CLIORA_P2_ORDER"); return e ? atoi(e) : 1; }();
-    hipLaunchKernelGGL((level_project2<SP0, SP1>), dim3(n), dim3(256), 0, st, a, b, order);
+    hipLaunchKernelGGL((level_project2<SP0, SP1>), dim3(n), dim3(256), 0, st, a, b);
     LAUNCHOK("level_project2");
     return CLIORA_OK;
 }
@@ -620,9 +597,8 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
             q.nrg = ((q.ncell + 15) / 16 + P2_RT - 1) / P2_RT;          // row groups of P2_RT sixteen-row tiles
             q.nrgp = q.nrg >= 8 ? (q.nrg + 7) / 8 * 8 : q.nrg;
             const int ncols = outside_pass ? Dp : ldpi;
-            const int ctb = outside_pass ? P2_CTB : P2_CTA;                // column tiles per block of this segment
             q.ntc = ncols / 16;
-            q.nproj = q.nrgp * ((q.ntc + ctb - 1) / ctb);
+            q.nproj = q.nrgp * ((q.ntc + P2_CT - 1) / P2_CT);
             q.Wfrag = ws + (outside_pass ? f.w1ro3 : f.wcat3);
             q.bias = outside_pass ? nullptr : ws + f.bcat;
             q.P = ws + (outside_pass ? f.po : f.pi); q.ldp = ncols;
@@ -639,24 +615,6 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
                 ProfScope ps(CLIORA_KCLASS_COMPOSE_FWD, st);
                 OKR(launch_level_compose2(st, ca, cb, f.S3, Dp, f.ct3, f.ncb3, ws + f.pp, hp_stride, YM, PH));
             }
-#ifdef CLIORA_DIAG_BG
-            // Timing proxy for the "old / new pairs" pipeline (profiles/r06_notes.md section 5): what does a BACKGROUND compose grid cost the
-            // critical chain?  Step k's compose is launched a second time on the side stream, behind the first (same inputs, the same values
-            // written again: results unchanged), so that it runs beside this step's projection / score grid and the next step's compose --
-            // where the background composition of the next level's old splits would run.  CLIORA_BG=1: every step; 2: the share (k-1)/(k+1)
-            // of its tasks, which is what the old splits are.
-            {
-                static const int bg = [] { const char* e = getenv("CLIORA_BG"); return e ? atoi(e) : 0; }();
-                if (bg && k >= 2 && k <= L - 1) {
-                    HIPOK(hipEventRecord(plan->ev_level[k], st));
-                    HIPOK(hipStreamWaitEvent(plan->side, plan->ev_level[k], 0));
-                    ComposeSeg ba = ca, bb = cb;
-                    if (bg == 2) { ba.ntask = std::max(1, ba.ntask * (k - 1) / (k + 1)); ba.gx = std::min(ba.gx, ba.ntask); if (bb.gx) { bb.ntask = std::max(1, bb.ntask * (k - 1) / (k + 1)); bb.gx = std::min(bb.gx, bb.ntask); } }
-                    OKR(launch_level_compose2(plan->side, ba, bb, f.S3, Dp, f.ct3, f.ncb3, ws + f.pp, hp_stride, YM, PH));
-                    fork_guard.arm(0, plan->side, plan->ev_join[0]);
-                }
-            }
-#endif
             if (vl && k <= L - 1) {   // cliora.py:140-157: the attention residual between the aggregate and the second unit norm (inside cells only)
                 const LevelArgs g = level_args(p, k, false);
                 ATTEND_LAUNCH(cell_attend_fwd, p.R, dim3(B * g.Lc), st, g, L, HPi, hp_stride, ca.SP, (const float*)nullptr, OBJ, p.R, drop_mask, p.normalize, IH,
@@ -668,7 +626,7 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
     }
     for (int k = 1; k <= L && !resident && !merged; ++k) {
         if (k <= L - 1) {
-            const bool by_kernel = two_streams && stop_events_on() && !vl && k < L - 1;      // the step ends with a level_project launch
+            const bool by_kernel = two_streams && !vl && k < L - 1;      // the step ends with a level_project launch
             OKR(inside_step(k, by_kernel ? plan->ev_level[k] : nullptr));
             if (two_streams && !by_kernel) HIPOK(hipEventRecord(plan->ev_level[k], sa));
         }
@@ -765,19 +723,18 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     hipStream_t sa = st, sb = two_streams ? plan->side : st, sw = plan->side2;
     float *VHo = wb + bw.vh_o, *dGo = wb + bw.dg_o, *dStoto = wb + bw.dstot_o;
     // unit-norm backward in the projection-backward GEMM's epilogue (chart_kernels.hpp: NormBwdLevelE): text-only charts without compress
-    // (CLIORA normalises around the attention residual; compress keeps per-sentence root gradients in dGo).  CLIORA_FUSE_DNORM=0: off.
-    static const bool fuse_off = [] { const char* e = getenv("CLIORA_FUSE_DNORM"); return e && atoi(e) == 0; }();
+    // (CLIORA normalises around the attention residual; compress keeps per-sentence root gradients in dGo).
     // (the OUTSIDE chart has no attention residual: its chain keeps the fusion in CLIORA plans too -- round 4, c3 chart step)
-    const bool fuse_dnorm = !fuse_off && !compress && !resident;
+    const bool fuse_dnorm = !compress && !resident;
     // the projection-backward GEMMs on split-bf16 products with RT x CT tiles (rows_gemm_ksplit3x): CLIORA_BWD_GEMM3 = 10 RT + CT
     // Round 5: these GEMMs sat on two limits at once -- what a CU pulls from L2 (a 16 x 16 block streams 150 KB for one tile) and the
     // fp32-input MFMA (16 x 16 x 4 in 32 cycles) -- and each remedy alone lost (profiles/r05_notes.md section 14); split-bf16 products on
     // 32 x 48 tiles take both: c2 3.005 -> 2.905 ms, L 40 16.37 -> 16.19.  Shapes 22 / 32 / 24: 2.95-2.96; 42 / 33 / 25 / 13 / 15: 3.0-3.14.
     // CLIORA_BWD_GEMM3=0: the fp32 16 x 16 kernel (always in the exact-fp32 arithmetic mode).
     static const int bwd_gemm3 = gemm3_shape_env("CLIORA_BWD_GEMM3", true);
-    static const int bwd_gemm3_min = [] { const char* e = getenv("CLIORA_BWD_GEMM3_MIN"); return e ? atoi(e) : 0; }();     // 0 / 128 / 256 / 512 / 768 cells: 2.905 / 2.91 / 2.92 / 2.92 / 2.94
-    auto gemm3_pays = [&](int ncell) { return bwd_gemm3 > 0 && split_bf16() && ncell >= bwd_gemm3_min; };
-    // X / DZ of the pair rows as tiled split-bf16 operands (wgrad_tiles.hpp) instead of fp32 rows.  CLIORA_PAIR_TILES=0: off.
+    // at every level (the fp32 kernel below a floor of 128 / 256 / 512 / 768 cells: 2.91 / 2.92 / 2.92 / 2.94 ms against 2.905)
+    const bool gemm3 = bwd_gemm3 > 0 && split_bf16();
+    // X / DZ of the pair rows as tiled split-bf16 operands (wgrad_tiles.hpp) instead of fp32 rows.
     const bool tiled = pair_tiles_ok(Dp) && !resident;
 
     // Sibling uses of inside level s in the outside pass (cell_gather_bwd_sib), on the OUTSIDE chain's stream: they are complete once
@@ -789,10 +746,8 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     // most pair rows, the inside levels L-1, L-2, ... the fewest cells), later the inside chain (its low levels' cells have the most
     // uses): the inside levels below `sib_split` (reached in the later steps) get their sibling sums from the outside chain, the others
     // walk the list themselves.  Measured per step at c2 (profiles/r04_notes.md): inside / outside chain 57-84 / 75-103 us in steps
-    // 0-11 with everything on the outside chain, 100 / 60-99 in steps 12-19.  CLIORA_SIB_SPLIT = 0 (never) .. L - 1 (always).
-    static const int sib_env = [] { const char* e = getenv("CLIORA_SIB_SPLIT"); return e ? atoi(e) : -1; }();
-    // (at most L - 1: the root level L - 1 has no sibling use, and no cell_gather_bwd_sib launch ever writes its rows)
-    const int sib_split = !two_streams ? 0 : sib_env >= 0 ? std::min(sib_env, L - 1) : (L * 2) / 5;
+    // 0-11 with everything on the outside chain, 100 / 60-99 in steps 12-19.
+    const int sib_split = two_streams ? (L * 2) / 5 : 0;
     auto sib_on_outside_chain = [&](int s_level) { return s_level < sib_split; };
     auto sibling_runs = [&](int s_level) { return s_level >= 0 && s_level <= L - 1 && ran_outside && sib_on_outside_chain(s_level); };
     auto sibling_gather = [&](int s_level, hipEvent_t done) -> int {
@@ -813,13 +768,13 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
                            level == L - 1 ? nullptr : d_outside_s, dv.use[ROLE_OUTB], DA, DS, PI, ldpi, p.blk_qlo, dPO, VHo, dStoto,
                            OH, ws + f.po, fused_norm ? wb + bw.dots_o : nullptr);
         LAUNCHOK("cell_gather_bwd_out");
-        if (fused_norm && gemm3_pays(ncell))
+        if (fused_norm && gemm3)
             OKR(launch_rows_direct3x(sb, ws + f.w1roT3s, Dp, Dp, ncell, LevelRowsA{dPO, Dp, C, g.off, g.Lc},
                               NormBwdLevelE{dGo, VHo, OH, ws + f.nrmo, wb + bw.dots_o, Dp, C, g.off, g.Lc, p.normalize}, bwd_gemm3));
         else if (fused_norm)
             OKR(launch_rows_direct(sb, ws + f.w1roT, PROJ_IMG(f.w1roT3), Dp, Dp, ncell, LevelRowsA{dPO, Dp, C, g.off, g.Lc},
                             NormBwdLevelE{dGo, VHo, OH, ws + f.nrmo, wb + bw.dots_o, Dp, C, g.off, g.Lc, p.normalize}));
-        else if (level >= 1 && gemm3_pays(ncell))
+        else if (level >= 1 && gemm3)
             OKR(launch_rows_direct3x(sb, ws + f.w1roT3s, Dp, Dp, ncell, LevelRowsA{dPO, Dp, C, g.off, g.Lc},
                               StoreLevelE{VHo, Dp, C, g.off, g.Lc, nullptr, 1}, bwd_gemm3));
         else if (level >= 1)
@@ -869,31 +824,20 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     const bool sw_beside = plan->side2_beside;
     const int ksplit = ksplit_env >= 0 ? ksplit_env : !sw_beside ? 0
                      : wcat_split_path ? std::max(1, std::min(2 * L / 5, L - 1)) : std::min(2, L - 1);
-    // ... optionally a second part (the levels below the first part down to ksplit2, CLIORA_WGRAD_SPLIT_LEVEL2): three more launches
-    // beside the inside chain's heaviest steps cost more than they take from the tail
-    static const int ksplit2_env = [] { const char* e = getenv("CLIORA_WGRAD_SPLIT_LEVEL2"); return e ? atoi(e) : -1; }();
-    const int ksplit2 = ksplit2_env > 0 ? ksplit2_env : -1;         // measured at c2: 3.32 (none) vs 3.37 (levels 2-5): off
+    // (a second mid-chain part, levels 2-5 below the first one, measured 3.37 against 3.32 ms per step at c2 without it: three more
+    // launches beside the inside chain's heaviest steps cost more than they take from the tail)
     int tail_cells = C;                                         // chart rows per sentence still to be covered by the tail launch
     bool dpi_done_recorded = false;                             // ev_fork[2] marks "every row of dPI is final" on the caller's stream
-    // d Wcat (+)= dPI^T IH over the cells [off, off + hi) of every sentence.  Split mode at d = 400 (round 4): one launch per projection
-    // block on the eight-wave split-bf16 kernel with the rows remapped inside it; else the fp32 element-load kernel over all blocks.
-    static const bool wcat_f32 = [] { const char* e = getenv("CLIORA_WCAT_GRAD"); return e && !strcmp(e, "f32"); }();
-    static const int wcat_slices = [] { const char* e = getenv("CLIORA_WCAT_SLICES"); return e ? atoi(e) : 48; }();
+    // d Wcat (+)= dPI^T IH over the cells [off, off + hi) of every sentence.  Split mode at d = 400 (round 4): the eight-wave split-bf16
+    // kernel with the rows remapped inside it; else the fp32 element-load kernel over all blocks.
     auto wcat_grad = [&](hipStream_t s_, int off, int hi, int accumulate) -> int {
         // (the kernel's row remap floors (r + 0.5) / hi in fp32: exact below 2^22 rows -- beyond, the element-load kernel)
-        if (!wcat_f32 && tn_pairs_strided_ok(Dp) && (long long)B * hi >= 512 && (long long)B * hi < (1LL << 22)) {
-            // all projection blocks in one launch + one reduction (CLIORA_WCAT_FUSED=0: a launch and a reduction per block, 48 slices each):
-            // the three launches + three reductions of the low levels' part ended the step ~120 us after the inside chain.  Slices per block
-            // (x 3 column blocks x nb workgroups), c2: 8 / 12 / 16 / 20 / 24 / 28 -> 3.17 / 3.14 / 3.11 / 3.11 / 3.11 / 3.15 ms (unfused 3.195)
-            static const bool fused = [] { const char* e = getenv("CLIORA_WCAT_FUSED"); return !e || atoi(e) != 0; }();
-            static const int fused_slices = [] { const char* e = getenv("CLIORA_WCAT_FUSED_SLICES"); return e ? atoi(e) : 0; }();
-            if (fused)
-                return launch_tn_level_block(s_, dPI, ldpi, 0, IH, B, C, off, hi, Dp, wb + bw.slab2, bw.slab_floats, wb + bw.gwcat, wb + bw.gbcat, accumulate,
-                                             fused_slices > 0 ? fused_slices : std::max(8, (180 / (3 * nb)) / 4 * 4), nb);
-            for (int blk = 0; blk < nb; ++blk)
-                OKR(launch_tn_level_block(s_, dPI, ldpi, blk * Dp, IH, B, C, off, hi, Dp, wb + bw.slab2, bw.slab_floats,
-                                          wb + bw.gwcat + (size_t)blk * Dp * Dp, wb + bw.gbcat + (size_t)blk * Dp, accumulate, wcat_slices));
-            return CLIORA_OK;
+        if (tn_pairs_strided_ok(Dp) && (long long)B * hi >= 512 && (long long)B * hi < (1LL << 22)) {
+            // all projection blocks in one launch + one reduction: a launch and a reduction per block ended the step ~120 us after the inside
+            // chain.  Slices per block (x 3 column blocks x nb workgroups), c2:
+            // 8 / 12 / 16 / 20 / 24 / 28 -> 3.17 / 3.14 / 3.11 / 3.11 / 3.11 / 3.15 ms (a launch per block: 3.195)
+            return launch_tn_level_block(s_, dPI, ldpi, IH, B, C, off, hi, Dp, wb + bw.slab2, bw.slab_floats, wb + bw.gwcat, wb + bw.gbcat, accumulate,
+                                         std::max(8, (180 / (3 * nb)) / 4 * 4), nb);
         }
         return launch_tn(s_, B * hi, ldpi, Dp, Dp, LevelRowsA{dPI, ldpi, C, off, hi}, LevelRowsA{IH, Dp, C, off, hi}, wb + bw.slab2,
                          bw.slab_floats, wb + bw.gwcat, wb + bw.gbcat, accumulate);
@@ -912,13 +856,13 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
             HIPOK(hipEventRecord(plan->ev_fork[2], sa));
             dpi_done_recorded = true;
         }
-        if (fused_norm && gemm3_pays(ncell))
+        if (fused_norm && gemm3)
             OKR(launch_rows_direct3x(sa, ws + f.wcatT3s, ldpi, Dp, ncell, LevelRowsA{dPI, ldpi, C, g.off, g.Lc},
                               NormBwdLevelE{dG, VH, IH, ws + f.nrmi, wb + bw.dots, Dp, C, g.off, g.Lc, p.normalize}, bwd_gemm3));
         else if (fused_norm)
             OKR(launch_rows_direct(sa, ws + f.wcatT, PROJ_IMG(f.wcatT3), ldpi, Dp, ncell, LevelRowsA{dPI, ldpi, C, g.off, g.Lc},
                             NormBwdLevelE{dG, VH, IH, ws + f.nrmi, wb + bw.dots, Dp, C, g.off, g.Lc, p.normalize}));
-        else if (level <= L - 2 && gemm3_pays(ncell))
+        else if (level <= L - 2 && gemm3)
             OKR(launch_rows_direct3x(sa, ws + f.wcatT3s, ldpi, Dp, ncell, LevelRowsA{dPI, ldpi, C, g.off, g.Lc},
                               StoreLevelE{VH, Dp, C, g.off, g.Lc, nullptr, 1}, bwd_gemm3));
         else if (level <= L - 2)
@@ -933,7 +877,7 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
                                drop_mask, ws + f.att_pk, wb + bw.dctx, wb + bw.pmo, wb + bw.dsc, IHn, nrmIn, level >= 1 ? dG : (float*)nullptr);
             LAUNCHOK("cell_attend_bwd");
         }
-        if ((level == ksplit || level == ksplit2) && level >= 1) {
+        if (level == ksplit && level >= 1) {
             // cells per sentence at the levels from this one up to the part already on its way (a level's cells are contiguous)
             const int hi = tail_cells - g.off;
             HIPOK(hipEventRecord(plan->ev_fork[2], sa));
@@ -987,15 +931,13 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     // L 40 19.88 -> 19.36, L 12 unchanged; later steps or wider launches lose (the part must end before the chains do, and it takes
     // from them nearly what it removes from the tail: profiles/r03_ubench_priority.txt).  CLIORA_WGRAD_EARLY_STEP = -1 turns it off.
     static const int early_env = [] { const char* e = getenv("CLIORA_WGRAD_EARLY_STEP"); return e ? atoi(e) : -2; }();
-    static const int early_slices = [] { const char* e = getenv("CLIORA_WGRAD_EARLY_SLICES"); return e ? atoi(e) : 32; }();
+    constexpr int early_slices = 32;
     // round 4 (the two ends now run as ONE launch with one reduction, so a shorter tail pays more than it did): c2 J = 9 / 10 / 11 / 12:
     // 3.41 / 3.39 / 3.33 / 3.42 ms per step; L 40 J = 19 / 21 / 23: 19.25 / 19.22 / 19.60
     const int early_auto = L >= 16 && sw_beside ? L / 2 + 1 : -1;      // (not beside the chains: see ksplit above)
     const int early_pick = early_env == -2 ? early_auto : early_env;
     const int J_early = (p.share && ran_outside && !compress && !resident && early_pick >= 0 && early_pick <= L - 3) ? early_pick : -1;
-    static const int early2_env = [] { const char* e = getenv("CLIORA_WGRAD_EARLY_STEP2"); return e ? atoi(e) : -2; }();      // -1: off
-    const int early2_auto = L >= 28 ? (J_early + L) / 2 : -1;
-    const int early2_pick = early2_env == -2 ? early2_auto : early2_env;
+    const int early2_pick = L >= 28 ? (J_early + L) / 2 : -1;
     const int J_early2 = (J_early >= 0 && early2_pick > J_early && early2_pick <= L - 3) ? early2_pick : -1;
     long long early_r0 = 0, early_r1 = 0, early_t0 = 0, early_t1 = 0;       // ... as pair rows and as 16-row tiles
     if (resident) {
@@ -1019,9 +961,7 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     for (int j = 0; j <= L - 1 && !compress && !resident; ++j) {
         if (ran_outside) {
             // (the compress root step ends in a launch that takes no event; it never runs on two streams)
-            const bool by_kernel = two_streams && stop_events_on();
-            OKR(outside_bwd_step(j, by_kernel ? plan->ev_level[j] : nullptr));
-            if (two_streams && !by_kernel) HIPOK(hipEventRecord(plan->ev_level[j], sb));
+            OKR(outside_bwd_step(j, two_streams ? plan->ev_level[j] : nullptr));
         }
         // the gather of inside level L-1-j reads the outside pairs whose sibling it is: outside levels <= j-1
         if (two_streams && j >= 1) HIPOK(hipStreamWaitEvent(sa, plan->ev_level[j - 1], 0));
@@ -1070,13 +1010,13 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     // The pair rows' tail (the rows whose dW2 did not start early).  Two streams (round 4): on the OUTSIDE chain's stream -- that chain
     // ends a step before the inside chain, and the last pair rows are final after inside level 1 (ev_join[2]), so the tail runs beside the
     // inside chain's last gather, projection backward and leaf layer instead of after them.  One stream: on the caller's stream, last.
+    constexpr int tail_slices = 48, tail_slices2 = 72;      // row slices of the two ends: one launch each / both in one launch
     auto pair_rows_tail = [&](hipStream_t s_) -> int {
         ProfScope ps(CLIORA_KCLASS_WGRAD, s_);
         if (tiled) {
             if (ran_outside && !p.share)
                 OKR(launch_tn_tiles(s_, DZ, Xp, p.T_in, p.T_out, 0, 0, Dp, wb + bw.slab, bw.slab_floats, wb + bw.gw2o, wb + bw.gb2o, 0, 0));
             const long long ntl = (p.share && ran_outside) ? p.T_in + p.T_out : p.T_in;
-            static const int tail_slices2 = [] { const char* e = getenv("CLIORA_WGRAD_TAIL_SLICES2"); return e ? atoi(e) : 72; }();
             if (J_early >= 0)
                 OKR(launch_tn_tiles(s_, DZ, Xp, 0, early_t0, early_t1, ntl - early_t1, Dp, wb + bw.slab, bw.slab_floats, wb + bw.gw2i, wb + bw.gb2i, 0,
                                     tail_slices2));
@@ -1090,8 +1030,6 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
         // shared weights: inside and outside pair rows are one contiguous range -> one launch
         const long long nr = (p.share && ran_outside) ? p.R_in + p.R_out : p.R_in;
         if (J_early >= 0) {          // the middle of the range is on its way on the GEMM stream (into gw2o / gb2o): the two ends here
-            static const int tail_slices = [] { const char* e = getenv("CLIORA_WGRAD_TAIL_SLICES"); return e ? atoi(e) : 48; }();
-            static const int tail_slices2 = [] { const char* e = getenv("CLIORA_WGRAD_TAIL_SLICES2"); return e ? atoi(e) : 72; }();
             if (tn_pairs_two_ranges_ok(Dp))          // both ends in one launch (round 4): one slab, one reduction
                 OKR(launch_tn_pairs_two_ranges(s_, DZ, Xp, (int)early_r0, early_r1, (int)(nr - early_r1), Dp, wb + bw.slab, bw.slab_floats,
                                                wb + bw.gw2i, wb + bw.gb2i, tail_slices2));

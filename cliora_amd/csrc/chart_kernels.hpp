@@ -23,10 +23,9 @@ constexpr float UNIT_EPS = 1e-8f;   // cliora/net/utils.py:10
 // linear block id, and a cell's operand / partner rows all belong to its own sentence -- with t = block id, the cells of one sentence
 // spread over all eight L2s and each of them fetches the sentence's rows; here the blocks with id = x (mod 8) take the sentences
 // b = x (mod 8), so a sentence's chart rows are fetched by ONE L2.  A permutation of the blocks only: the results are the same bits.
-// CLIORA_XCD_AFFINE=0 (api_common.hpp: xcd_affine()) restores t = block id.
-__device__ __forceinline__ int cell_of_block(int bid, int B, int Lc, int affine) {
+__device__ __forceinline__ int cell_of_block(int bid, int B, int Lc) {
     const int n8 = (B >> 3) * 8 * Lc;                  // blocks of the sentences below the last multiple of 8
-    if (!affine || bid >= n8) return bid;
+    if (bid >= n8) return bid;
     const int x = bid & 7, q = bid >> 3;
     const int bb = q / Lc, p = q - bb * Lc;
     return (bb * 8 + x) * Lc + p;
@@ -35,7 +34,6 @@ __device__ __forceinline__ int cell_of_block(int bid, int B, int Lc, int affine)
 struct LevelArgs {
     int B, C, Dp, Lc, N, off;   // target cells of this level: chart row b*C + off + p, p < Lc; N splits each
     int rowbase;                // first global pair row of the level; row = rowbase + (b*Lc + p)*N + n
-    int affine;                 // one-workgroup-per-cell kernels: sentence-affine block order (cell_of_block)
 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -114,7 +112,7 @@ static __global__ __launch_bounds__(256) void pair_scores_fwd(LevelArgs g, const
     // in flight together for L <= 16, four at a time beyond), wave 0 then does the softmax
     __shared__ float sh_s[64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = cell_of_block(blockIdx.x, g.B, g.Lc, g.affine);
+    const int t = cell_of_block(blockIdx.x, g.B, g.Lc);
     const int b = t / g.Lc, p = t - b * g.Lc;
     const int row0 = g.rowbase + t * g.N;
     const int nv = g.Dp >> 2;
@@ -252,7 +250,7 @@ static __global__ __launch_bounds__(256) void cell_gather_bwd_in(LevelArgs g, in
     __shared__ float4 sh[2][GATHER_SLOTS][64];
     __shared__ float sh_s[4], sh_s2[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = cell_of_block(blockIdx.x, g.B, g.Lc, g.affine);
+    const int t = cell_of_block(blockIdx.x, g.B, g.Lc);
     const int b = t / g.Lc, p = t - b * g.Lc;
     const int c = g.off + p;
     const size_t crow = (size_t)b * g.C + c;
@@ -272,14 +270,9 @@ static __global__ __launch_bounds__(256) void cell_gather_bwd_in(LevelArgs g, in
     if (sib && act1) { sp1 = ld4(sib_pl + crow * Dp + col1); sq1 = ld4(sib_ql + crow * Dp + col1); }
     const float ss = (with_outside == 1 && wave == 0) ? sib_s[crow] : 0.f;
     // right-child uses: partner = left child; dH += ds * QL(left);  dPR += DA
-    // (CLIORA_DIAG_GATHER: wrong-result timing builds of tools/ab/anatomy.sh -- 1: no list, 2: the right-child list only, 3: no list, no dots)
-#if !defined(CLIORA_DIAG_GATHER) || CLIORA_DIAG_GATHER == 2
     gather_uses(inb, c, b, bC, wave, DA, DS, Dp, PI + 2 * Dp, ldpi, col0, col1, act0, act1, v[4], v[5], v[0], v[1], vS);
-#endif
     // left-child uses: partner = right child; dQL += ds * H(right);  dPL += DA
-#if !defined(CLIORA_DIAG_GATHER)
     gather_uses(ina, c, b, bC, wave, DA, DS, Dp, IH, Dp, col0, col1, act0, act1, v[2], v[3], v[6], v[7], vS);
-#endif
     wg_sum_pairs(sh, wave, lane, 8, v);
     if (with_outside == 2) {           // sibling uses in the outside pass, walked here: partner = parent (outside chart); own reduction round
         float4 w[4] = {f4zero(), f4zero(), f4zero(), f4zero()};
@@ -312,9 +305,6 @@ static __global__ __launch_bounds__(256) void cell_gather_bwd_in(LevelArgs g, in
         st4(VH + crow * Dp + col1, f4add(v[1], e));
     }
     if (lane == 0) dStot[crow] = vs;
-#if defined(CLIORA_DIAG_GATHER) && CLIORA_DIAG_GATHER == 3
-    dots = nullptr;
-#endif
     if (dots) {      // H . vH of the cell without the finished vH (NormBwdLevelE): H . vHg + dP . (P - bias) over the cell's projection blocks
         float d = 0.f;
         const float* hr = IH + crow * Dp;
@@ -350,7 +340,7 @@ static __global__ __launch_bounds__(256) void cell_gather_bwd_sib(LevelArgs g, U
     __shared__ float4 sh[2][GATHER_SLOTS][64];
     __shared__ float sh_s[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = cell_of_block(blockIdx.x, g.B, g.Lc, g.affine);
+    const int t = cell_of_block(blockIdx.x, g.B, g.Lc);
     const int b = t / g.Lc, p = t - b * g.Lc;
     const int c = g.off + p;
     const size_t crow = (size_t)b * g.C + c;
@@ -382,7 +372,7 @@ static __global__ __launch_bounds__(256) void cell_gather_bwd_out(LevelArgs g, i
     __shared__ float4 sh[2][GATHER_SLOTS][64];
     __shared__ float sh_s[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int t = cell_of_block(blockIdx.x, g.B, g.Lc, g.affine);
+    const int t = cell_of_block(blockIdx.x, g.B, g.Lc);
     const int b = t / g.Lc, p = t - b * g.Lc;
     const int c = g.off + p;
     const size_t crow = (size_t)b * g.C + c;

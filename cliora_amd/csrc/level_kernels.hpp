@@ -536,7 +536,8 @@ struct ComposeSeg {
     int TG, SP, ntask, gx;    // gx = 0: no such segment in this step
     float* HP;
 };
-// DUALPD > 0: compose_fwd_tasks_dual with that ring depth (two splits of a cell tile in flight per wave); 0: compose_fwd_tasks
+// DUALPD > 0: compose_fwd_tasks_dual with that ring depth (two splits of a cell tile in flight per wave; the d = 400 split-bf16 instance
+// runs depth 2); 0: compose_fwd_tasks
 template <int CT, int K16, bool F32, int DUALPD = 0>
 __global__ __launch_bounds__(512) void level_compose_fwd2(ComposeSeg s0, ComposeSeg s1, int S_, int K_, const float* __restrict__ Pp, size_t hp_stride,
                                                           int Dp, uint32_t* __restrict__ ymask, float* __restrict__ Y) {
@@ -607,10 +608,7 @@ struct ScoreArgs {
 // cells of ALL of the wave's splits (lane j: split w + 4 j), the "plain" splits (both operands final: rows of QA / HB) run SCORE_KF at a
 // time with all their rows and chart scores in flight together, and the (at most two per cell) splits with an operand on the newest
 // level follow.  Same formula per split, so the same bits.
-#ifndef CLIORA_SCORE_KF
-#define CLIORA_SCORE_KF 2
-#endif
-constexpr int SCORE_KF = CLIORA_SCORE_KF;
+constexpr int SCORE_KF = 2;
 __device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh_s) {
     const LevelArgs& g = sc.g;
     const int lane = threadIdx.x & 63;
@@ -723,7 +721,7 @@ __device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh
 // the scoring alone (first level of a pass: every operand is already final)
 static __global__ __launch_bounds__(256) void level_scores(ScoreArgs sc) {
     __shared__ float sh_s[64];
-    score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc, sc.g.affine), sh_s);
+    score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), sh_s);
 }
 
 // one projection block (16 rows x CT*16 columns) of level_project: block `bid` of nrgp * ncolblocks
@@ -842,7 +840,7 @@ __global__ __launch_bounds__(256) void level_project(const float* __restrict__ W
     __shared__ float sh_ss[4][16];
     (void)ncolblocks;
     if ((int)blockIdx.x < sc.nscore) {               // the next level's scores: first in the grid, so they start at once
-        score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc, sc.g.affine), &sh_ss[0][0]);
+        score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), &sh_ss[0][0]);
         return;
     }
     project_block<CT, SP>(part, sh_ss, (int)blockIdx.x - sc.nscore, Wfrag, K, nrg, nrgp, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm);
@@ -898,11 +896,7 @@ __device__ __forceinline__ void project_tile(float4 (*part)[RT * CT][64], float 
     const int nchunks = K >> 4;
     const int cbase = nchunks / 4, crem = nchunks % 4;
     const int ch0 = wave * cbase + min(wave, crem);
-#ifdef CLIORA_DIAG_GEMMK                               // wrong-result timing diagnostic (tools/ab/anatomy.sh): 1/N of each wave's chunks
-    const int nch = max(1, (cbase + (wave < crem ? 1 : 0)) / CLIORA_DIAG_GEMMK);
-#else
     const int nch = cbase + (wave < crem ? 1 : 0);
-#endif
     auto crow_of = [&](int r) { const int rc = min(r, ncell - 1); const int b = rc / Lc; return (size_t)b * C + off + (rc - b * Lc); };
     const float* hp[RT];
 #pragma unroll
@@ -1019,10 +1013,10 @@ __device__ __forceinline__ void project_tile(float4 (*part)[RT * CT][64], float 
 // ---------------------------------------------------------------------------------
 // level_project2 (round 5): the second launch of a wavefront step for BOTH passes -- norm + projection of inside level k and of outside
 // level L-k, the chart rows of a level that needs no projection (level_finish: inside root, outside leaves), and the split scores +
-// softmax of the next level of either pass -- as ONE grid on one queue.  Block order: the scores first (they are the latency chains of
-// the launch), then segment 0's projection blocks, segment 1's, then the finish blocks.  16 x 16 tiles (CT = 1: the variant every
-// sweep of the block size preferred, profiles/r04_notes.md); SP0 / SP1 = parts of the two levels' partial aggregates.  Every block runs
-// the code of level_project / level_finish on its own segment: the same bits as the per-pass launches.
+// softmax of the next level of either pass -- as ONE grid on one queue.  Block order: segment 0's projection blocks, segment 1's, then
+// the scores, then the finish blocks (projections first: 24.05 -> 22.97 us per launch at c2 against the scores first).  16 x 16 tiles
+// (CT = 1: the variant every sweep of the block size preferred, profiles/r04_notes.md); SP0 / SP1 = parts of the two levels' partial
+// aggregates.  Every block runs the code of level_project / level_finish on its own segment: the same bits as the per-pass launches.
 // ---------------------------------------------------------------------------------
 struct ProjSeg {
     const float* Wfrag; int K, nrg, nrgp, ntc, ncell, Lc, C, off;      // nrg row groups of P2_RT row tiles (nrgp: padded to 8), ntc column tiles
@@ -1031,45 +1025,31 @@ struct ProjSeg {
     int nfin, SPfin;      // level_finish blocks (cells_grid(ncell)) and the level's parts; 0: none
     ScoreArgs sc;         // sc.nscore = 0: no scoring
 };
-// tile shape of level_project2's projection blocks: RT row tiles x CTA (segment 0: inside, 75 column tiles at d 400) / CTB (segment 1:
-// outside, 25) column tiles, PD chunks of the reduction in flight per wave.  Build-time (tools/ab: -DCLIORA_P2_RT=.. etc.)
-#ifndef CLIORA_P2_RT
-#define CLIORA_P2_RT 1
-#endif
-#ifndef CLIORA_P2_CTA
-#define CLIORA_P2_CTA 1
-#endif
-#ifndef CLIORA_P2_CTB
-#define CLIORA_P2_CTB 1
-#endif
-#ifndef CLIORA_P2_PD
-#define CLIORA_P2_PD 4
-#endif
-constexpr int P2_RT = CLIORA_P2_RT, P2_CTA = CLIORA_P2_CTA, P2_CTB = CLIORA_P2_CTB, P2_PD = CLIORA_P2_PD;
-constexpr int P2_CTM = P2_CTA > P2_CTB ? P2_CTA : P2_CTB;
+// tile shape of level_project2's projection blocks (both segments): P2_RT row tiles x P2_CT column tiles, P2_PD chunks of the
+// reduction in flight per wave
+constexpr int P2_RT = 1, P2_CT = 1, P2_PD = 4;
 template <int SP0, int SP1>
-__global__ __launch_bounds__(256) void level_project2(ProjSeg a, ProjSeg b, int order) {
-    __shared__ float4 part[4][P2_RT * P2_CTM][64];
+__global__ __launch_bounds__(256) void level_project2(ProjSeg a, ProjSeg b) {
+    __shared__ float4 part[4][P2_RT * P2_CT][64];
     __shared__ float sh_ss[4][P2_RT * 16];
     int bid = blockIdx.x;
-    {   // order 1: the projection blocks first, the score blocks behind them (order 0: scores first); 2: scores in the middle
+    {   // dispatch order -> the logical order below (scores, projections, finish blocks)
         const int ns = a.sc.nscore + b.sc.nscore, np = a.nproj + b.nproj;
-        if (order == 1 && bid < ns + np) bid = bid < np ? bid + ns : bid - np;
-        else if (order == 2 && bid < ns + np) { const int h = np / 2; bid = bid < h ? bid + ns : (bid < h + ns ? bid - h : bid); }
+        if (bid < ns + np) bid = bid < np ? bid + ns : bid - np;
     }
-    if (bid < a.sc.nscore) { score_cell(a.sc, cell_of_block(bid, a.sc.g.B, a.sc.g.Lc, a.sc.g.affine), &sh_ss[0][0]); return; }
+    if (bid < a.sc.nscore) { score_cell(a.sc, cell_of_block(bid, a.sc.g.B, a.sc.g.Lc), &sh_ss[0][0]); return; }
     bid -= a.sc.nscore;
-    if (bid < b.sc.nscore) { score_cell(b.sc, cell_of_block(bid, b.sc.g.B, b.sc.g.Lc, b.sc.g.affine), &sh_ss[0][0]); return; }
+    if (bid < b.sc.nscore) { score_cell(b.sc, cell_of_block(bid, b.sc.g.B, b.sc.g.Lc), &sh_ss[0][0]); return; }
     bid -= b.sc.nscore;
     if (bid < a.nproj) {
-        project_tile<P2_RT, P2_CTA, SP0, P2_PD>(reinterpret_cast<float4 (*)[P2_RT * P2_CTA][64]>(&part[0][0][0]), sh_ss, bid, a.Wfrag, a.K, a.nrg, a.nrgp, a.ntc,
-                                                a.ncell, a.Lc, a.C, a.off, a.HP, a.hp_stride, a.normalize, a.bias, a.P, a.ldp, a.H, a.nrm);
+        project_tile<P2_RT, P2_CT, SP0, P2_PD>(part, sh_ss, bid, a.Wfrag, a.K, a.nrg, a.nrgp, a.ntc,
+                                               a.ncell, a.Lc, a.C, a.off, a.HP, a.hp_stride, a.normalize, a.bias, a.P, a.ldp, a.H, a.nrm);
         return;
     }
     bid -= a.nproj;
     if (bid < b.nproj) {
-        project_tile<P2_RT, P2_CTB, SP1, P2_PD>(reinterpret_cast<float4 (*)[P2_RT * P2_CTB][64]>(&part[0][0][0]), sh_ss, bid, b.Wfrag, b.K, b.nrg, b.nrgp, b.ntc,
-                                                b.ncell, b.Lc, b.C, b.off, b.HP, b.hp_stride, b.normalize, b.bias, b.P, b.ldp, b.H, b.nrm);
+        project_tile<P2_RT, P2_CT, SP1, P2_PD>(part, sh_ss, bid, b.Wfrag, b.K, b.nrg, b.nrgp, b.ntc,
+                                               b.ncell, b.Lc, b.C, b.off, b.HP, b.hp_stride, b.normalize, b.bias, b.P, b.ldp, b.H, b.nrm);
         return;
     }
     bid -= b.nproj;
@@ -1100,10 +1080,7 @@ __global__ __launch_bounds__(512) void level_compose_bwd(const uint32_t* __restr
                                                          float* __restrict__ DA, float* __restrict__ DZ, float* __restrict__ X,
                                                          float* __restrict__ DPP, float* __restrict__ DPB) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_img[];
-#ifndef CLIORA_CB_PD
-#define CLIORA_CB_PD 4
-#endif
-    constexpr int WAVES = 8, T = WAVES * 64, PD = CLIORA_CB_PD;       // k-steps of operand rows in flight per wave
+    constexpr int WAVES = 8, T = WAVES * 64, PD = 4;       // k-steps of operand rows in flight per wave
     constexpr bool KS = K16 > 0;
     constexpr int UNROLL_STEPS = KS ? 64 : 1;
     const int K = KS ? K16 * 16 : K_;
@@ -1171,7 +1148,7 @@ __global__ __launch_bounds__(512) void level_compose_bwd(const uint32_t* __restr
         // The epilogue runs in the FETCH-lane view (lane = 4 li + lg: row li = target cell ti, columns 4 lg .. of each column tile), like
         // the operand ring: its re-gather of xs = PL(a) + PR(b), the DA row stores and the X tile stores are then 64 contiguous bytes per
         // four lanes (the X tile: lane-linear) where the MFMA-lane view (row = lane & 15) made every one of them 64 separate requests per
-        // instruction -- the re-gather alone was 4.7 us of the c2 launch's 31 (tools/ab/anatomy.sh).  The accumulators come over with
+        // instruction -- the re-gather alone was 4.7 us of the c2 launch's 31 (a round-5 timing build).  The accumulators come over with
         // five ds_bpermute quadruples per tile (the k-loop has 26).
         const int gt = tile / lv.N, n = tile - gt * lv.N;
         const int ti = gt * 16 + li;
@@ -1198,11 +1175,7 @@ __global__ __launch_bounds__(512) void level_compose_bwd(const uint32_t* __restr
             const float4 f0 = masked(q.g0, q.m0 >> (4 * ((2 * st) % CT)));
             const float4 f1 = masked(q.g1, q.m1 >> (4 * ((2 * st + (second ? 1 : 0)) % CT)));
             const int k = 32 * st + 4 * lg;
-#ifdef CLIORA_DIAG_NOXZ      // timing proxy (WRONG weight gradients): no X / DZ tile stores (profiles/r06_notes.md section 4)
-            if (false) {
-#else
             if (st % gy == by) {
-#endif
                 if (TILED) {
                     uint32_t* zt = reinterpret_cast<uint32_t*>(ctx.zo) + (2 * st) * 256;
                     store_split_tile(zt, make_float4(ctx.pn * f0.x, ctx.pn * f0.y, ctx.pn * f0.z, ctx.pn * f0.w));
@@ -1258,11 +1231,7 @@ __global__ __launch_bounds__(512) void level_compose_bwd(const uint32_t* __restr
                                         x.z > 0.f ? pn * u.z : 0.f, x.w > 0.f ? pn * u.w : 0.f));
                 if (!TILED) st4(X + o, x);
             }
-#ifndef CLIORA_DIAG_NOXZ
             if (TILED)          // the tile's lane slot 8 (row) + 2 (piece) = 2 lane: lane-linear
-#else
-            if (false)
-#endif
                 store_split_tile(reinterpret_cast<uint32_t*>(X) + ((size_t)(lv.tilebase + tile) * NT + by * CT + c) * 256 + 2 * lane,
                                  ok ? x : f4zero());
         }

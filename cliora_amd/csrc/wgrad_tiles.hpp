@@ -72,7 +72,7 @@ template <int NT, int NIT, int NJT, int NJW, bool COLSUM>
 static __global__ __launch_bounds__(512) void tn_gemm_tiles(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B, long long tile0,
                                                             int ntiles, int tiles_per_slice, int nslices, int nkb,
                                                             float* __restrict__ slab, float* __restrict__ colsum,
-                                                            int slice2, long long tile0b, int ntilesb, int issue_mode) {
+                                                            int slice2, long long tile0b, int ntilesb) {
     // slices >= slice2 walk a SECOND tile range (ntilesb tiles from tile0b): the two ends of the pair rows around the part whose
     // weight gradient started early -- one launch, one slab, one reduction for both
     static_assert(2 * NJW > NJT, "the second half of the j-tiles needs a spare slot for the ones-tile");
@@ -150,14 +150,15 @@ static __global__ __launch_bounds__(512) void tn_gemm_tiles(const uint32_t* __re
     const uint32_t b_addr0 = lds0 + lane_b + (uint32_t)(xpart * 4) + (uint32_t)ju0 * 1024u;
 
     if (nstages > 0) issue(0, 0, NPW);
-    constexpr int PPT = (NPW + NIT - 1) / NIT;           // pieces of the NEXT stage issued beside each row tile's MFMAs (issue_mode 0)
+    // pieces of the NEXT stage issued beside each row tile's MFMAs (against all of them right behind the barrier: the kernel alone at
+    // L 40 2.30 / 2.48 ms, c2 step 3.21 / 3.24 ms)
+    constexpr int PPT = (NPW + NIT - 1) / NIT;
     for (int st = 0; st < nstages; ++st) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                 // stage st has landed for every wave; buffer (st+1)&1 is free again
         const bool more = st + 1 < nstages;
         const bool h1 = tbeg + 2 * st + 1 < tend;
         const uint32_t a_addr = a_addr0 + (uint32_t)((st & 1) * bufdw * 4), b_addr = b_addr0 + (uint32_t)((st & 1) * bufdw * 4);
-        if (more && issue_mode == 1) issue(st + 1, 0, NPW);
         TrOperand rb[NJW], ra[2];
 #pragma unroll
         for (int u = 0; u < NJW; ++u) rb[u] = lds_tr_operand(b_addr + (uint32_t)u * 1024u, NJT * 1024u);
@@ -175,7 +176,7 @@ static __global__ __launch_bounds__(512) void tn_gemm_tiles(const uint32_t* __re
             lgkm_wait(ra[t & 1]);
             tr_finish(ra[t & 1], h1, ah, al);
             if (t + 1 < NIT) ra[(t + 1) & 1] = lds_tr_operand(a_addr + (uint32_t)(t + 1) * 1024u, NT * 1024u);
-            if (more && issue_mode == 0) issue(st + 1, PPT * t, PPT * t + PPT);
+            if (more) issue(st + 1, PPT * t, PPT * t + PPT);
 #pragma unroll
             for (int u = 0; u < NJW; ++u) acc[t][u] = mfma32bf(al, bh[u], acc[t][u]);
 #pragma unroll
