@@ -122,6 +122,16 @@ def lib():
         i64 = C.c_int64
         L.cliora_ground_eval.argtypes = [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cliora_ground_eval.restype = i32
+    if hasattr(L, 'cliora_knn_ip'):                             # (absent from older builds loaded through CLIORA_CHART_LIB)
+        i64 = C.c_int64
+        L.cliora_phrase_gather.argtypes = [i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp, i64, i64, vp, vp]
+        L.cliora_phrase_gather.restype = i32
+        L.cliora_knn_ip_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        L.cliora_knn_ip_workspace_bytes.restype = sz
+        L.cliora_knn_ip.argtypes = [i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, sz, vp]
+        L.cliora_knn_ip.restype = i32
+        L.cliora_knn_filter.argtypes = [i32, i32, vp, i64, vp, i64, vp, vp, i32, i32, vp, vp, vp, vp]
+        L.cliora_knn_filter.restype = i32
     L.cliora_prof_enable.argtypes = [i32, i32]
     L.cliora_prof_enable.restype = i32
     L.cliora_prof_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]

@@ -311,6 +311,43 @@ int cliora_ground_eval(int B, int L, int R, const float* atten, int64_t atten_sb
                        const int32_t* spans, int G, const int32_t* gold_off, const int32_t* gold_span, int32_t* phr_out,
                        int32_t* span_box, float* span_xyxy, int32_t* sent_out, int32_t* status, void* stream);
 
+/* Phrase vectors (cliora/scripts/phrase_embed.py:79-92, 223-224; phrase_embed_simple.py:262-287): ONE launch for a batch's
+ * phrases, one wavefront per phrase.  All pointers are device memory.
+ *   inside_h / outside_h (B, C, D) fp32, C = L(L+1)/2, at element strides (sb, sc) for the sentence and the cell (unit stride along D).
+ *   table (N, 3) int32: (sentence, pos, size); the cell is C - (L-size+1)(L-size+2)/2 + pos (offset(L)[size-1] + pos).
+ *   out: row row_offset + r (leading dimension ldo >= 2D) = [inside_h[b, cell] | outside_h[b, cell]]; a caller-owned buffer, so a
+ *     whole corpus is appended on the device batch by batch.  normalize != 0: the row scaled to unit L2 norm as faiss.normalize_L2
+ *     does (a zero row stays zero); the norm is summed in fp64, so a row is within an ulp of an fp64 normalisation.
+ *   A row with size < 1, pos < 0, pos + size > L, or a sentence outside [0, B) is not read: it is written as zeros and counted in
+ *   *status (an int32 the call zeroes first), which the caller must check. */
+int cliora_phrase_gather(int B, int L, int D, const float* inside_h, int64_t in_sb, int64_t in_sc, const float* outside_h,
+                         int64_t out_sb, int64_t out_sc, int N, const int32_t* table, int normalize, float* out, int64_t ldo,
+                         int64_t row_offset, int32_t* status, void* stream);
+
+/* Exact inner-product top-k, the semantics of faiss.IndexFlatIP(D).add(keys); .search(q, k) (phrase_embed.py:136-146).
+ *   q (nq, D) and keys (nk, D) fp32 at leading dimensions ldq, ldk >= D, any D >= 1 (padded to 32 internally); 1 <= k <= 128
+ *   (anything else: CLIORA_EINVAL with a message).  D_out (nq, k) fp32 at ldd, I_out (nq, k) int64 at ldi: the k best keys per
+ *   query by descending score; slots past nk hold I = -1 and D = -inf.
+ *   Scores on the MFMA of cliora_set_mfma_mode: split-bf16 (three v_mfma_f32_16x16x32_bf16 per product) or fp32-input
+ *   (v_mfma_f32_16x16x4f32); fp32 accumulation.  The N x N score matrix is never written: each workgroup scores a 64-query tile
+ *   against a range of keys 256 at a time, the scores pass through LDS into a running top-k per query, the per-range lists go to the
+ *   workspace and a merge kernel reduces them.  The number of ranges grows as nq shrinks, so a few queries still fill the device.
+ *   Determinism: a score is a fixed-order sum over the columns that does not depend on where its rows sit in a tile; equal scores
+ *   are ordered by ascending key index; a NaN score ranks below every number.  So a query's result is bitwise the same whatever
+ *   other queries share the launch and however the keys were split, and two runs are bitwise equal.
+ *   ws: device workspace of cliora_knn_ip_workspace_bytes(nq, nk, D, k) bytes (0 for invalid arguments). */
+size_t cliora_knn_ip_workspace_bytes(int nq, int nk, int D, int k);
+int cliora_knn_ip(int nq, int nk, int D, int k, const float* q, int64_t ldq, const float* keys, int64_t ldk, float* D_out, int64_t ldd,
+                  int64_t* I_out, int64_t ldi, void* ws, size_t ws_bytes, void* stream);
+
+/* The post-search filter of phrase_embed.py:250-263 for a self-search (query i is phrase i): per query walk its k_candidates
+ * (I, D at leading dimensions ldi, ldd), skip I == -1 (past the keys: the reference would index example_ids[-1] there, the last
+ * phrase), skip a candidate with the query's example id, skip one with the query's phrase id (an integer per distinct token tuple),
+ * keep the first k_top.  I_out (nq, k_top) int64 / D_out (nq, k_top) fp32, -1 / -inf past what was found; count (nq) int32 the
+ * number found, which the caller compares with k_top.  example_ids / phrase_ids: n_ids >= nq int32 each. */
+int cliora_knn_filter(int nq, int k_candidates, const int64_t* I, int64_t ldi, const float* D, int64_t ldd, const int32_t* example_ids,
+                      const int32_t* phrase_ids, int n_ids, int k_top, int64_t* I_out, float* D_out, int32_t* count, void* stream);
+
 /* Optional HIP-event timing of one kernel class (used by bench.py for the roofline
  * line): enable, run steps, then read the accumulated device time and launch count. */
 int cliora_prof_enable(int kernel_class, int on);
