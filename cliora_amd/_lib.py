@@ -132,6 +132,14 @@ def lib():
         L.cliora_knn_ip.restype = i32
         L.cliora_knn_filter.argtypes = [i32, i32, vp, i64, vp, i64, vp, vp, i32, i32, vp, vp, vp, vp]
         L.cliora_knn_filter.restype = i32
+    if hasattr(L, 'cliora_neg_sample'):                         # (absent from older builds loaded through CLIORA_CHART_LIB)
+        i64, u64 = C.c_int64, C.c_uint64
+        L.cliora_token_counts.argtypes = [i64, vp, i32, vp, vp, vp]
+        L.cliora_token_counts.restype = i32
+        L.cliora_neg_sample_workspace_bytes.argtypes = [i32, i32, i32]
+        L.cliora_neg_sample_workspace_bytes.restype = sz
+        L.cliora_neg_sample.argtypes = [i32, vp, i32, i32, i32, u64, u64, C.c_uint32, vp, vp, vp, sz, vp]
+        L.cliora_neg_sample.restype = i32
     L.cliora_prof_enable.argtypes = [i32, i32]
     L.cliora_prof_enable.restype = i32
     L.cliora_prof_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]

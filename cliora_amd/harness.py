@@ -326,8 +326,10 @@ def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=
 
 
 class Trainer(object):
-    def __init__(self, net, lr=2e-3, reducer=None):
+    def __init__(self, net, lr=2e-3, reducer=None, negative_sampler=None, k_neg=100):
         self.net = net
+        self.negative_sampler = negative_sampler             # cliora_amd.sampling.NegativeSampler or None (batch_iterator.py:158-160)
+        self.k_neg = k_neg
         self.params = [p for p in net.parameters() if p.requires_grad]
         self.reducer = reducer                               # cliora_amd.parallel.FlatGradAllReduce or None
         self.defer_table_grads = True
@@ -343,8 +345,11 @@ class Trainer(object):
         `.item()` (trainer.py:463) -- a device synchronisation per step; sync=False returns the 0-d tensor and lets the host run
         ahead of the device (read it when logging)."""
         self.net.train(train)
+        neg_samples = batch_map.get('neg_samples')
+        if neg_samples is None and self.negative_sampler is not None:       # drawn on the current stream, ahead of the forward
+            neg_samples = self.negative_sampler.sample(self.k_neg)
         with torch.set_grad_enabled(train):
-            out = self.net(batch_map['sentences'], batch_map.get('obj_feats'), batch_map.get('neg_samples'), compute_loss)
+            out = self.net(batch_map['sentences'], batch_map.get('obj_feats'), neg_samples, compute_loss)
         total = out.total() if isinstance(out, LossDict) else out['total_loss'].mean(dim=0).sum()
         # sync=True returns the loss as a Python float like the reference's `.item()` (trainer.py:463).  Its value is final once the FORWARD is:
         # it is copied to pinned host memory here, behind the forward, and read at the end of the step by waiting for THAT copy only -- the

@@ -348,6 +348,30 @@ int cliora_knn_ip(int nq, int nk, int D, int k, const float* q, int64_t ldq, con
 int cliora_knn_filter(int nq, int k_candidates, const int64_t* I, int64_t ldi, const float* D, int64_t ldd, const int32_t* example_ids,
                       const int32_t* phrase_ids, int n_ids, int k_top, int64_t* I_out, float* D_out, int32_t* count, void* stream);
 
+/* Corpus token counts, the frequency vector of the reference's negative sampler (cliora/blocks/negative_sampler.py:15-24): ids (n)
+ * int64 on the device -> counts (V) fp32, counts[v] = the number of ids equal to v, converted from an exact integer count (so the
+ * reference's np.asarray(counts, float32) bit for bit).  Counted with integer atomics in LDS for V <= 16384, in HBM above.  Ids
+ * outside [0, V) are not counted there: their number goes to *n_out_of_range (one int64 on the device, zeroed by the call), which
+ * the caller must check.  n < 2^32.  Asynchronous on `stream`. */
+int cliora_token_counts(int64_t n, const int64_t* ids, int V, float* counts, int64_t* n_out_of_range, void* stream);
+
+/* S independent draws of k distinct ids from [0, V) without replacement, each new id drawn in proportion to its weight among those
+ * not yet drawn -- numpy's legacy RandomState.choice(V, k, replace=False, p=w / sum(w)) (negative_sampler.py:36-37), in law.
+ *   w (V) fp32 on the device, >= 0 and finite, any scale (the reference's freq**power + eps / V unnormalised); n_positive: the number
+ *   of w > 0, which the caller knows; 1 <= k <= min(1024, n_positive), else CLIORA_EINVAL ("Fewer non-zero entries in p than size"
+ *   as numpy words it), checked before any device call.  Zero weights are never drawn.
+ *   Draw s is the exponential race E_i = -log(u_i) / w_i (double), its ids the k smallest (E, id) in ascending order (the draw order
+ *   of the successive sampling).  u_i = (m + 0.5) 2^-53, m = (x0 >> 5) 2^26 + (x1 >> 6), x = Philox4x32-10 of counter
+ *   (i, d_lo, d_hi, stream_id), key (seed_lo, seed_hi), d = offset + s.  So a draw depends on (seed, stream_id, d) alone: not on S,
+ *   on the launch geometry or on the other draws of the call.
+ *   ids_out (S, k) int64; keys_out (S, k) fp64 or NULL: the selected E.  No V-long key vector is written: blocks of 1024 ids
+ *   (up to 4096 for k > 256) keep their k smallest (bitonic sort in LDS), and merge launches reduce the per-block lists (4 launches
+ *   at V = 400k, k = 100).
+ *   ws: cliora_neg_sample_workspace_bytes(V, S, k) bytes of device workspace (0 when V <= 4096, and for invalid arguments). */
+size_t cliora_neg_sample_workspace_bytes(int V, int S, int k);
+int cliora_neg_sample(int V, const float* w, int n_positive, int S, int k, uint64_t seed, uint64_t offset, uint32_t stream_id,
+                      int64_t* ids_out, double* keys_out, void* ws, size_t ws_bytes, void* stream);
+
 /* Optional HIP-event timing of one kernel class (used by bench.py for the roofline
  * line): enable, run steps, then read the accumulated device time and launch count. */
 int cliora_prof_enable(int kernel_class, int on);
