@@ -140,6 +140,9 @@ def lib():
         L.cliora_neg_sample_workspace_bytes.restype = sz
         L.cliora_neg_sample.argtypes = [i32, vp, i32, i32, i32, u64, u64, C.c_uint32, vp, vp, vp, sz, vp]
         L.cliora_neg_sample.restype = i32
+    if hasattr(L, 'cliora_cky_spans_ragged'):                   # (absent from older builds loaded through CLIORA_CHART_LIB)
+        L.cliora_cky_spans_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.cliora_cky_spans_ragged.restype = i32
     L.cliora_prof_enable.argtypes = [i32, i32]
     L.cliora_prof_enable.restype = i32
     L.cliora_prof_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]

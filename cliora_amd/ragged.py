@@ -1,0 +1,237 @@
+"""Sentences of different lengths parsed in one padded chart, decoded per sentence.
+
+Every other entry point of the library takes a batch whose sentences have one length, the reference's own rule (it buckets by exact
+length and never pads).  A caller who holds "these 40 captions" then pays one chain of dependent level launches and one CKY launch
+per distinct length.  The inside pass is prefix-closed: cell (level, pos) with pos + level < n reads only cells of words [0, n).  So a
+sentence of length n padded on the right to Lmax has, in its own triangle of the padded chart, the inside vectors, inside scores and
+per-split scores a chart of length n would hold, and the CKY tree needs only those.  ``cliora_cky_spans_ragged`` (include/
+cliora_chart.h) decodes each sentence from its own triangle; ``cliora_phrase_gather`` reads the inside vector of its own root cell.
+
+The OUTSIDE pass is not prefix-closed (in a padded chart every cell has parents that reach beyond the sentence), so this module is
+inference of trees and inside vectors only: it runs the chart with the outside pass off and nothing here may be trained through.
+
+    from cliora_amd.ragged import parse_ragged, encode_ragged
+    trees = parse_ragged(net, sentences)        # net: harness.Net (text-only); sentences: lists of token ids, any lengths 1..64
+    vecs = encode_ragged(net, sentences)        # (N, D) inside vectors of the sentences' roots, on the device
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L
+# Padded work a pack may carry beyond its sentences' own work, as a fraction of the latter.  Measured choice (tools/ragged_bench.py,
+# profiles/ragged_bench.json): the best of the sweep on 64 mixed sentences (5.3x the bucketed path), within
+# 2 % of the best on 1 000.
+DEFAULT_MAX_WASTE = 2.0
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _native():
+    lib = _lib.lib()
+    if not hasattr(lib, 'cliora_cky_spans_ragged'):
+        raise _lib.ChartLibError('%s has no cliora_cky_spans_ragged: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
+    return lib
+
+
+def work(length):
+    """Span pairs of one sentence's inside pass: sum over levels of (L - level) * level = (L^3 - L) / 6 compose rows."""
+    length = int(length)
+    return (length ** 3 - length) // 6
+
+
+def pad_batch(sentences, pad_id=0):
+    """-> (tokens (B, Lmax) int64, lengths (B,) int32), each sentence padded on the right with `pad_id`."""
+    lengths = [len(s) for s in sentences]
+    if not lengths:
+        return torch.zeros((0, 0), dtype=torch.int64), torch.zeros((0,), dtype=torch.int32)
+    if min(lengths) < 1:
+        raise ValueError('an empty sentence has no chart')
+    tokens = np.full((len(lengths), max(lengths)), pad_id, dtype=np.int64)
+    for i, s in enumerate(sentences):
+        tokens[i, :lengths[i]] = np.asarray(s, dtype=np.int64)
+    return torch.from_numpy(tokens), torch.tensor(lengths, dtype=torch.int32)
+
+
+def pack(lengths, max_batch=64, max_waste=DEFAULT_MAX_WASTE):
+    """Cut the sentences into batches that each share one padded chart: -> list of index lists.
+
+    The indices are sorted by length (longest first, ties by index) and cut greedily: a batch takes the next sentence while it holds
+    fewer than `max_batch` and its padded work, len(batch) * work(longest), stays within (1 + max_waste) times the sum of its
+    sentences' own work().  max_waste = 0 buckets by exact work (sentences of length 1 cost nothing and ride along with each other
+    only), float('inf') fills every batch.  Pure and deterministic."""
+    if max_batch < 1:
+        raise ValueError('max_batch must be at least 1')
+    if not max_waste >= 0:
+        raise ValueError('max_waste must be >= 0')
+    order = sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i))
+    packs, cur, exact, top = [], [], 0, 0
+    for i in order:
+        w = work(lengths[i])
+        if cur and (len(cur) >= max_batch or (len(cur) + 1) * top > (1.0 + max_waste) * (exact + w)):
+            packs.append(cur)
+            cur, exact = [], 0
+        if not cur:
+            top = w
+        cur.append(i)
+        exact += w
+    if cur:
+        packs.append(cur)
+    return packs
+
+
+def decode_ragged_numpy(pair_s, lengths):
+    """The decode of cliora_cky_spans_ragged restated in numpy, for tests: `pair_s[level]` (B, Lmax - level, level) are the per-split
+    inside scores of the PADDED chart; sentence b is decoded from levels 1 .. n-1 at positions pos < n - level, candidate
+    (val_l + val_r) + (s - max s) in fp32, first maximum wins.  -> per sentence the list of (start, end), children before parents."""
+    out = []
+    for b, n in enumerate(int(x) for x in lengths):
+        val = {(0, p): np.float32(1.0) for p in range(n)}
+        bp = {}
+        for level in range(1, n):
+            s = np.asarray(pair_s[level][b], dtype=np.float32)
+            for pos in range(n - level):
+                row = s[pos, :level]
+                rel = row - row.max()
+                cand = np.array([(val[(k, pos)] + val[(level - k - 1, pos + k + 1)]) + rel[k] for k in range(level)], dtype=np.float32)
+                k = int(np.argmax(cand))
+                val[(level, pos)], bp[(level, pos)] = cand[k], k
+        spans = []
+
+        def walk(level, pos):
+            if level == 0:
+                return
+            k = bp[(level, pos)]
+            walk(k, pos)
+            walk(level - k - 1, pos + k + 1)
+            spans.append((pos, pos + level))
+        walk(n - 1, 0)
+        out.append(spans)
+    return out
+
+
+def cky_spans_ragged(diora, lengths, split_out=False):
+    """cliora_cky_spans_ragged on a chart module after its forward over a right-padded batch.
+
+    lengths: int32 tensor (B,), one per sentence of the chart.  -> (spans, status) or (spans, status, split): spans (B, L-1, 2) int32
+    with (-1, -1) beyond each sentence's n - 1 rows; status (number of workspaces,) int32 counting the lengths outside [1, L], which
+    the caller must check; split (B, C) int32, -1 at the leaves and outside each triangle.  Device tensors; nothing is synchronised."""
+    lib = _native()
+    plan, wss = diora._plan, diora._wss
+    B, L = plan.B, plan.L
+    nws = len(wss)
+    if lengths.dtype != torch.int32 or lengths.numel() != B * nws:
+        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
+    dev = wss[0].device
+    with torch.cuda.device(dev):
+        lengths = lengths.to(dev).contiguous()
+        spans = torch.empty((B * nws, L - 1, 2), dtype=torch.int32, device=dev)
+        status = torch.empty(nws, dtype=torch.int32, device=dev)
+        split = torch.empty((B * nws, plan.C), dtype=torch.int32, device=dev) if split_out else None
+        for i, ws in enumerate(wss):
+            _lib.check(lib.cliora_cky_spans_ragged(plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[i * B:(i + 1) * B]),
+                                                   _p(split[i * B:(i + 1) * B]) if split_out else C.c_void_p(0),
+                                                   _p(spans[i * B:(i + 1) * B]), C.c_void_p(status[i:i + 1].data_ptr()), _stream()),
+                       'cliora_cky_spans_ragged')
+    return (spans, status, split) if split_out else (spans, status)
+
+
+def root_rows(diora, lengths):
+    """(B, D) inside vectors of the sentences' own root cells (n - 1, 0) of a padded chart: one cliora_phrase_gather launch over the
+    device table (b, 0, lengths[b]), whose outside half is pointed at the inside chart and dropped (the outside pass is off)."""
+    lib = _native()
+    ih = diora.chart.inside_h
+    B, Cc, D = ih.shape
+    L = diora._plan.L
+    dev = ih.device
+    with torch.cuda.device(dev):
+        n = lengths.to(dev).to(torch.int32)
+        tab = torch.stack([torch.arange(B, dtype=torch.int32, device=dev), torch.zeros_like(n), n], 1).contiguous()
+        out = torch.empty((B, 2 * D), dtype=torch.float32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.cliora_phrase_gather(B, L, D, _p(ih), ih.stride(0), ih.stride(1), _p(ih), ih.stride(0), ih.stride(1), B, _p(tab),
+                                            0, _p(out), out.stride(0), 0, _p(status), _stream()), 'cliora_phrase_gather')
+        bad = int(status.item())
+    if bad:
+        raise _lib.ChartLibError('%d sentence length(s) outside 1..%d' % (bad, L))
+    return out[:, :D]
+
+
+def _check_module(diora):
+    from .diora import DioraMLP as TextDiora
+    if not isinstance(diora, TextDiora):
+        raise NotImplementedError(
+            'ragged batches need the text-only cliora_amd.diora.DioraMLP, got %s: the vision-language module goes on to score regions '
+            'against inside_h + outside_h, and the outside pass of a padded chart is not that of the sentence' % type(diora).__name__)
+
+
+def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack):
+    """pack -> per pack: pad, embed, inside pass without the outside pass, `per_pack(indices, lengths_on_device)`."""
+    diora = net.diora
+    _check_module(diora)
+    lengths = [len(s) for s in sentences]
+    if not lengths:
+        return
+    if min(lengths) < 1:
+        raise ValueError('an empty sentence has no chart')
+    dev = next(net.parameters()).device
+    if max(lengths) > MAX_L:         # the plan's own refusal, before any pack has run
+        _lib.get_plan(1, max(lengths), diora.size, diora.share, diora.normalize, 0, dev.index if dev.type == 'cuda' else -1)
+    was_training, had_outside = net.training, diora.outside
+    net.eval()
+    diora.outside = False
+    try:
+        with torch.no_grad():
+            for idx in pack(lengths, max_batch, max_waste):
+                tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
+                x_span, x_word = net.embed(tokens.to(dev))
+                diora(x_span, x_word)
+                per_pack(idx, lens.to(dev))
+    finally:
+        diora.outside = had_outside
+        net.train(was_training)
+
+
+def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
+    """Best binary tree of every sentence (nested tuples of word positions as ``DioraBase.cky()``; 0 for a single word), in the
+    caller's order.  net: a text-only harness.Net; sentences: sequences of token ids of any lengths in 1..64.  Runs in eval mode under
+    no_grad with the outside pass off (both restored afterwards; the module's chart is left as the last pack's, outside_h unwritten).
+    One device-to-host copy per pack."""
+    diora = net.diora
+    trees = [None] * len(sentences)
+
+    def decode(idx, lens):
+        spans, status = cky_spans_ragged(diora, lens)
+        nsp = spans.numel()
+        host = torch.cat([spans.reshape(-1), status]).cpu().numpy()         # the pack's one device-to-host copy
+        if host[nsp:].any():
+            raise _lib.ChartLibError('cliora_cky_spans_ragged rejected %d sentence length(s)' % int(host[nsp:].sum()))
+        rows = host[:nsp].reshape(spans.shape)
+        for b, i in enumerate(idx):
+            trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode)
+    return trees
+
+
+def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
+    """(N, D) fp32 on the device: row i = inside_h of sentence i's root cell (its own length's root, not the padded chart's), the
+    vector DIORA users read off the root.  Same plumbing as parse_ragged."""
+    diora = net.diora
+    dev = next(net.parameters()).device
+    out = torch.empty((len(sentences), diora.size), dtype=torch.float32, device=dev)
+
+    def gather(idx, lens):
+        out[torch.tensor(idx, dtype=torch.int64, device=dev)] = root_rows(diora, lens)
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, gather)
+    return out

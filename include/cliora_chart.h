@@ -287,6 +287,17 @@ int cliora_cky_decode(cliora_plan* plan, void* fwd_workspace, int32_t* split_out
  * get_spans(get_actions(tree)) (cliora/analysis/utils.py:3-49; what scripts/train.py:184-204 scores F1 on): evaluation needs ONE
  * device-to-host copy of B*(L-1)*2 ints and no recursion over a split table.  split_out: as cliora_cky_decode, or NULL. */
 int cliora_cky_spans(cliora_plan* plan, void* fwd_workspace, int32_t* split_out, int32_t* spans_out, void* stream);
+/* The decode for sentences of DIFFERENT lengths that were run as one batch, each padded on the right to the plan's L.  The inside
+ * pass is prefix-closed -- cell (level, pos) with pos + level < n reads only cells of words [0, n) -- so sentence b's own triangle of
+ * the padded chart holds what a chart of length n = lengths[b] would ("Mixed-length batches"); the outside pass is not, and
+ * nothing here reads it.  One workgroup per sentence evaluates levels 1 .. n-1 at positions pos < n - level only (the same candidate
+ * in the same order as cliora_cky_spans, first maximum wins) and walks from cell (n-1, 0).
+ *   lengths (B) int32 device.  spans_out (B, L-1, 2): the first n-1 rows are the sentence's spans in cliora_cky_spans' order, the
+ *   root (0, n-1) last; the remaining rows are (-1, -1).  split_out (B, C) or NULL: -1 at the leaves and outside the triangle.
+ *   A length outside [1, L] is not decoded: every row of that sentence is -1 and it is counted in *status (an int32 on the device the
+ *   call zeroes first), which the caller must check.  With lengths[b] == L for every b the outputs are those of cliora_cky_spans. */
+int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, int32_t* split_out, int32_t* spans_out,
+                            int32_t* status, void* stream);
 
 /* Grounding evaluation (cliora/scripts/parse.py:176-264, the host loop over every phrase and predicted span): ONE launch for a batch,
  * one workgroup per sentence.  All pointers are device memory.
