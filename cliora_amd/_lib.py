@@ -143,6 +143,13 @@ def lib():
     if hasattr(L, 'cliora_cky_spans_ragged'):                   # (absent from older builds loaded through CLIORA_CHART_LIB)
         L.cliora_cky_spans_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.cliora_cky_spans_ragged.restype = i32
+    if hasattr(L, 'cliora_chart_forward_ragged'):               # (absent from older builds loaded through CLIORA_CHART_LIB)
+        i64 = C.c_int64
+        L.cliora_chart_forward_ragged.argtypes = [vp, C.POINTER(Params)] + [vp] * 8 + [vp, sz, i32, vp, C.c_uint64, vp, vp]
+        L.cliora_chart_forward_ragged.restype = i32
+        L.cliora_ground_eval_ragged.argtypes = [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                vp]
+        L.cliora_ground_eval_ragged.restype = i32
     L.cliora_prof_enable.argtypes = [i32, i32]
     L.cliora_prof_enable.restype = i32
     L.cliora_prof_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]

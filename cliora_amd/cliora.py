@@ -15,7 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .diora import DioraBase, ComposeMLP, Bilinear, Chart, _ptr, _stream, _param_struct, _grad_out
+from .diora import DioraBase, ComposeMLP, Bilinear, Chart, _ptr, _stream, _param_struct, _grad_out, ragged_chart
 from .index import Index
 
 DROPOUT_P = 0.1   # AttentionHead: nn.Dropout(0.1), cliora.py:32
@@ -387,7 +387,13 @@ class DioraMLP(DioraBase):
         needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [x_span, obj_embed_span] + list(params))
         hooks = self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook')
         flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
-        ih, is_, oh, os_, ic = VLChartFunction.apply(plan, holder, flags, x_span, obj_embed_span, mask, *params)
+        ragged = self.__dict__.get('_ragged')
+        if ragged is not None:      # cliora_amd.ragged: a right-padded batch of mixed lengths, eval only (rows of words >= n are unspecified)
+            self._check_ragged(needs_grad, hooks)
+            ih, is_, oh, os_, ic, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, obj_embed_span, params,
+                                                                                 *ragged)
+        else:
+            ih, is_, oh, os_, ic = VLChartFunction.apply(plan, holder, flags, x_span, obj_embed_span, mask, *params)
         ch = Chart()
         ch.inside_h, ch.inside_s, ch.outside_h, ch.outside_s, ch.inside_c = ih, is_, oh, os_, ic
         ch.outside_c = torch.zeros_like(oh)

@@ -85,6 +85,12 @@ int cliora_ensure_max_lds(const void* fn);
 // uploads the plan's index tables on first use (current device) and checks that later calls run on that device
 int cliora_plan_ready(cliora_plan* plan, hipStream_t st);
 
+// cliora_chart_forward_ragged's extra arguments (api_ragged.hip), handed to the forward's body (api_mlp.hip)
+struct RaggedFwd { const int32_t* lengths; uint64_t root_levels; int32_t* status; };
+int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span, const float* drop_mask,
+                             float* inside_h, float* inside_s, float* outside_h, float* outside_s, float* inside_c, void* fwd_ws,
+                             size_t fwd_ws_bytes, int run_outside, void* stream, const RaggedFwd* rg);
+
 constexpr size_t TRACE_BYTES = (size_t)256 * 4 * (CLIORA_MAX_L + 1) * 10 * 8;   // diagnostic stamp words per device
 
 // ------------------------------------------------------------------ profiling (HIP events)

@@ -3,6 +3,7 @@
 #include "api_common.hpp"
 #include <hip/hip_ext.h>
 #include "level_kernels.hpp"
+#include "ragged_kernels.hpp"
 #include "resident_kernels.hpp"
 #include "vl_kernels.hpp"
 
@@ -296,10 +297,13 @@ static int build_chart_images(const cliora_plan* plan, float* ws, bool compress,
 }
 
 // ------------------------------------------------------------------ forward
-extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
-                                    const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
-                                    float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
-                                    void* stream) {
+// The body of cliora_chart_forward.  rg == nullptr: that entry, launch for launch.  rg != nullptr: cliora_chart_forward_ragged
+// (api_ragged.hip, which has checked its own refusals) -- the sequential schedule of the compress path on the caller's stream, with
+// the mask between the passes and the root fix-up behind every outside level that is some sentence's root level (ragged_kernels.hpp).
+int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                             const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
+                             float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
+                             void* stream, const RaggedFwd* rg) {
     if (!plan || !P || !x_span || !inside_h || !inside_s || !outside_h || !outside_s || !fwd_ws)
         return fail(CLIORA_EINVAL, "NULL argument");
     const Plan& p = plan->p;
@@ -331,7 +335,7 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
     const float* OBJ = vl ? (padded ? ws + f.objp : obj_span) : nullptr;
     const float* w1o = p.share ? P->in_w1 : P->out_w1;
 
-    const bool resident = !(run_outside & CLIORA_FWD_PAIR_STATES) && resident_pays(plan, vl, compress, false);     // its workgroups do the leaves too
+    const bool resident = !rg && !(run_outside & CLIORA_FWD_PAIR_STATES) && resident_pays(plan, vl, compress, false);     // its workgroups do the leaves too
 
     // ---- pack parameters into padded / concatenated / transposed layouts ----
     {
@@ -461,8 +465,8 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
     // two streams run such kernels side by side at the cost of one; an event dependency per step adds 3 us).
     // round 5: the same wavefront on ONE queue -- the two passes' launches of a step as one grid each (level_compose_fwd2 /
     // level_project2): no side stream, no event per step (merged_pays)
-    const bool merged = run_outside && !compress && !resident && merged_pays(p, vl);
-    const bool two_streams = wavefront_pays(p, g_cliora_wavefront) && run_outside && !compress && !resident && !merged;
+    const bool merged = run_outside && !compress && !resident && !rg && merged_pays(p, vl);
+    const bool two_streams = wavefront_pays(p, g_cliora_wavefront) && run_outside && !compress && !resident && !merged && !rg;
     hipStream_t sa = st, sb = two_streams ? plan->side : st;
 
     auto inside_step = [&](int level, hipEvent_t project_stop) -> int {          // diora.py:295-331 for one level
@@ -550,7 +554,7 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
         }
         return CLIORA_OK;
     };
-    if (!compress) OKR(init_root());
+    if (!compress && !rg) OKR(init_root());
     if (resident) {
         // ---- one workgroup per sentence, every level of both passes (resident_kernels.hpp) ----
         ResArgs a = resident_args(plan, ws, IH, OH, IS, OS, run_outside);
@@ -630,7 +634,7 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
             OKR(inside_step(k, by_kernel ? plan->ev_level[k] : nullptr));
             if (two_streams && !by_kernel) HIPOK(hipEventRecord(plan->ev_level[k], sa));
         }
-        if (run_outside && k >= 2 && !compress) {
+        if (run_outside && k >= 2 && !compress && !rg) {
             const int level = L - k;
             // compose reads the siblings' projections of inside levels <= k-2, the riding scores (level >= 1) those of level k-1
             const int need = level >= 1 ? k - 1 : k - 2;
@@ -641,6 +645,23 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
     if (compress) {           // the outside pass after the inside pass, on the caller's stream
         OKR(init_root());
         for (int level = L - 2; level >= 0 && run_outside; --level) OKR(outside_step(level));
+    }
+    if (rg) {
+        // Mixed lengths in one padded chart (ragged_kernels.hpp).  The mask comes before init_root, whose level_scores launch for
+        // level L-2 already reads inside_s.  outside_step(t) scores level t-1 inside its projection launch, i.e. from the root cell
+        // as it was BEFORE the fix-up: after a fix-up the whole level t-1 is scored again with every operand final.
+        hipLaunchKernelGGL(ragged_mask_inside_s, dim3((unsigned)(((size_t)B * C + 255) / 256)), dim3(256), 0, st, B, L, C,
+                           rg->lengths, IS, rg->status);
+        LAUNCHOK("ragged_mask_inside_s");
+        OKR(init_root());
+        for (int level = L - 2; level >= 0 && run_outside; --level) {
+            OKR(outside_step(level));
+            if (!((rg->root_levels >> level) & 1)) continue;
+            hipLaunchKernelGGL(ragged_root_seed, dim3(B), dim3(4 * 64), 0, st, level, p.level_offset[level], C, Dp, rg->lengths, OH, OS,
+                               ws + f.nrmo, ws + f.po);
+            LAUNCHOK("ragged_root_seed");
+            if (level >= 1) OKR(launch_scores(st, score_args(level - 1, true, -1, 0)));
+        }
     }
     if (two_streams) {
         HIPOK(hipEventRecord(plan->ev_join[0], sb));
@@ -654,6 +675,14 @@ extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, c
         OKR(run_copies(st, t));
     }
     return CLIORA_OK;
+}
+
+extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                                    const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
+                                    float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
+                                    void* stream) {
+    return cliora_chart_forward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws,
+                                    fwd_ws_bytes, run_outside, stream, nullptr);
 }
 
 // ------------------------------------------------------------------ backward

@@ -44,22 +44,32 @@ __device__ __forceinline__ int ground_pick_word(const float* rowmax, int s, int 
 // phr_out (P, 4): selected word, selected box, hit, ccr; a phrase outside 0 <= start < end <= L gets (-1, -1, 0, 0) and is counted
 // in *status.  span_box (B, L-1) / span_xyxy (B, L-1, 4): the box of every predicted span (the root's too).  sent_out (B, 3):
 // |pred & gold|, |pred|, |gold| over the span SETS, pred without its root (the last span).  atten == nullptr: counts only.
+// lengths == nullptr: every sentence has L words (cliora_ground_eval).  Else (cliora_ground_eval_ragged) sentence b has n = lengths[b]
+// words of a batch padded to L: its spans are rows 0 .. n-2 (the root row n-2), its words the first n rows of atten, a phrase must end
+// at or before n, and the rows n-1 .. L-2 of span_box / span_xyxy are written as -1 / 0.  n outside [1, L]: one count in *status, no
+// word, span or phrase of the sentence is read.
 __global__ __launch_bounds__(GROUND_THREADS) void ground_eval_kernel(
         int L, int R, const float* __restrict__ atten, int64_t sb, int64_t sl, int64_t sr, const float* __restrict__ boxes,
         int P, const int32_t* __restrict__ phr_off, const int32_t* __restrict__ phr_span, const float* __restrict__ phr_box,
         const int32_t* __restrict__ spans, int G, const int32_t* __restrict__ gold_off, const int32_t* __restrict__ gold_span,
         int32_t* __restrict__ phr_out, int32_t* __restrict__ span_box, float* __restrict__ span_xyxy, int32_t* __restrict__ sent_out,
-        int32_t* __restrict__ status) {
+        int32_t* __restrict__ status, const int32_t* __restrict__ lengths) {
     extern __shared__ float rowmax[];             // L row maxima, then L first-argmax region ids
     int32_t* rowarg = reinterpret_cast<int32_t*>(rowmax + L);
     __shared__ int32_t cnt[3];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int NS = L - 1;                         // predicted spans per sentence, the root last
-    const int32_t* sp = spans + (size_t)b * NS * 2;
+    const int NSL = L - 1;                        // span rows per sentence in the tables
+    int nw = L;                                   // the sentence's words
+    if (lengths) {
+        nw = lengths[b];
+        if (nw < 1 || nw > L) { nw = 0; if (tid == 0) atomicAdd(status, 1); }
+    }
+    const int NS = nw > 0 ? nw - 1 : 0;           // predicted spans of the sentence, the root last
+    const int32_t* sp = spans + (size_t)b * NSL * 2;
     if (tid < 3) cnt[tid] = 0;
     // 1. per word: max over the regions and the first region attaining it (one wavefront per row)
     if (atten) {
-        for (int l = wave; l < L; l += GROUND_THREADS / 64) {
+        for (int l = wave; l < nw; l += GROUND_THREADS / 64) {
             const float* row = atten + (int64_t)b * sb + (int64_t)l * sl;
             float best = -INFINITY; int bi = 0x7fffffff;
             for (int r = lane; r < R; r += 64) {          // increasing r: a later equal value never replaces the lane's first
@@ -81,7 +91,7 @@ __global__ __launch_bounds__(GROUND_THREADS) void ground_eval_kernel(
     for (int p = p0 + tid; p < p1; p += GROUND_THREADS) {
         const int s = phr_span[2 * p], e = phr_span[2 * p + 1];
         int32_t* o = phr_out + (size_t)4 * p;
-        if (!atten || s < 0 || s >= e || e > L) {
+        if (!atten || s < 0 || s >= e || e > nw) {
             o[0] = -1; o[1] = -1; o[2] = 0; o[3] = 0;
             atomicAdd(status, 1);
             continue;
@@ -100,13 +110,13 @@ __global__ __launch_bounds__(GROUND_THREADS) void ground_eval_kernel(
     // 3. predicted spans: box of each; distinct non-root spans
     for (int k = tid; k < NS; k += GROUND_THREADS) {
         const int s = sp[2 * k], e = sp[2 * k + 1];
-        const bool ok = s >= 0 && s <= e && e < L;
+        const bool ok = s >= 0 && s <= e && e < nw;
         if (!ok) atomicAdd(status, 1);
         if (atten) {
             const int box = ok ? rowarg[ground_pick_word(rowmax, s, e + 1)] : -1;
-            if (span_box) span_box[(size_t)b * NS + k] = box;
+            if (span_box) span_box[(size_t)b * NSL + k] = box;
             if (span_xyxy)
-                for (int c = 0; c < 4; ++c) span_xyxy[((size_t)b * NS + k) * 4 + c] = ok ? boxes[((size_t)b * R + box) * 4 + c] : 0.f;
+                for (int c = 0; c < 4; ++c) span_xyxy[((size_t)b * NSL + k) * 4 + c] = ok ? boxes[((size_t)b * R + box) * 4 + c] : 0.f;
         }
         if (ok && k < NS - 1) {
             bool first = true;
@@ -114,6 +124,12 @@ __global__ __launch_bounds__(GROUND_THREADS) void ground_eval_kernel(
             if (first) atomicAdd(&cnt[1], 1);
         }
     }
+    if (atten)                                    // rows beyond the sentence's own spans (ragged batches only: NS == NSL otherwise)
+        for (int k = NS + tid; k < NSL; k += GROUND_THREADS) {
+            if (span_box) span_box[(size_t)b * NSL + k] = -1;
+            if (span_xyxy)
+                for (int c = 0; c < 4; ++c) span_xyxy[((size_t)b * NSL + k) * 4 + c] = 0.f;
+        }
     // 4. distinct gold spans, and those among the predicted non-root spans
     int g0 = gold_off[b], g1 = gold_off[b + 1];
     g0 = min(max(g0, 0), G); g1 = min(max(g1, g0), G);

@@ -119,6 +119,42 @@ class ChartFunction(torch.autograd.Function):
         return (None, None, None, d_x) + tuple(g[n] for n in _lib.PARAM_FIELDS)
 
 
+def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_levels):
+    """cliora_chart_forward_ragged (include/cliora_chart.h): both passes of a right-padded batch of mixed lengths, inference only, so no
+    autograd node.  lengths: int32 device tensor (B,); root_levels: the bit mask of {n - 1}.  -> inside_h, inside_s, outside_h,
+    outside_s, inside_c (None for a text-only plan), status (1,) int32 on the device, which the caller must read."""
+    lib = _lib.lib()
+    if not hasattr(lib, 'cliora_chart_forward_ragged'):
+        raise _lib.ChartLibError('%s has no cliora_chart_forward_ragged: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
+    if not x_span.is_cuda:
+        raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
+    B, Cc, D = plan.B, plan.C, plan.D
+    dev = x_span.device
+    if lengths.dtype != torch.int32 or lengths.numel() != B or lengths.device != dev:
+        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (B, dev))
+    x_span = x_span.detach().contiguous().float()
+    obj_span = obj_span.detach().contiguous().float() if obj_span is not None else None
+    lengths = lengths.contiguous()
+    ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
+    with _OnDevice(dev):
+        inside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
+        inside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
+        outside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
+        outside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
+        inside_c = torch.zeros((B, Cc, D), device=dev, dtype=torch.float32) if obj_span is not None else None
+        status = torch.empty(1, device=dev, dtype=torch.int32)
+        ws = torch.empty(plan.fwd_bytes, device=dev, dtype=torch.uint8)
+        pst = _param_struct(ptens)
+        rc = lib.cliora_chart_forward_ragged(
+            plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), None, _ptr(inside_h), _ptr(inside_s), _ptr(outside_h),
+            _ptr(outside_s), _ptr(inside_c), _ptr(ws), plan.fwd_bytes, int(bool(outside)) | _lib.FWD_NO_BACKWARD, _ptr(lengths),
+            int(root_levels), _ptr(status), _stream())
+        _lib.check(rc, 'cliora_chart_forward_ragged')
+    holder.clear()
+    holder.append(ws)
+    return inside_h, inside_s, outside_h, outside_s, inside_c, status
+
+
 # --------------------------------------------------------------------------------------
 # Parameter containers with the reference's module tree, so state_dict keys match
 # (diora.py:26-97, 453-471).  Their forward() is never used on the product path.
@@ -183,6 +219,9 @@ class DioraBase(nn.Module):
         self.ninput = 2
         self.index = None
         self.charts = None
+        # cliora_amd.ragged sets (lengths on the device, root-level mask) around an eval forward over a right-padded batch of mixed
+        # lengths: the chart then runs through cliora_chart_forward_ragged and leaves its status word in _ragged_status
+        self.__dict__['_ragged'] = None
         self.init_parameters()
         self.reset_parameters()
         self.reset()
@@ -240,7 +279,15 @@ class DioraBase(nn.Module):
         # plain attributes, written straight into the instance dict: nn.Module.__setattr__ walks its parameter / buffer / module
         # registries for every assignment (~3.5 us each; a configs[0]-sized step is bound by the host)
         self.__dict__.update(batch_size=None, length=None, chart=None, atten_score=None, all_atten_score=None, vg_atten_score=None,
-                             _wss=None, _plan=None)
+                             _wss=None, _plan=None, _ragged_status=None)
+
+    def _check_ragged(self, needs_grad, hooks):
+        if needs_grad or self.training:
+            raise _lib.ChartLibError('a padded chart of mixed lengths is inference only: call it in eval mode under torch.no_grad()')
+        if hooks:
+            raise NotImplementedError('inside_hook / outside_hook overrides get no per-pair states from a padded chart of mixed lengths')
+        if self.compress:
+            raise NotImplementedError('compress = True is not supported on a padded chart of mixed lengths')
 
     def _hook_overridden(self, name):
         return name in self.__dict__ or getattr(type(self), name) is not getattr(DioraBase, name)
@@ -281,7 +328,12 @@ class DioraBase(nn.Module):
         needs_grad = torch.is_grad_enabled() and (x_span.requires_grad or any(t is not None and t.requires_grad for t in params))
         hooks = self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook')
         flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
-        ih, is_, oh, os_ = ChartFunction.apply(plan, holder, flags, x_span, *params)
+        ragged = self.__dict__.get('_ragged')
+        if ragged is not None:
+            self._check_ragged(needs_grad, hooks)
+            ih, is_, oh, os_, _, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, None, params, *ragged)
+        else:
+            ih, is_, oh, os_ = ChartFunction.apply(plan, holder, flags, x_span, *params)
         ch = Chart()
         ch.inside_h, ch.inside_s, ch.outside_h, ch.outside_s = ih, is_, oh, os_       # the zero cell states: on first read (Chart)
         d = self.__dict__

@@ -31,7 +31,8 @@ class Targets(object):
     phrases: (sentence, start, end) per phrase, ``end`` exclusive, in the reference's order (the items of each sentence's dict);
     phr_off (B+1), phr_span (P, 2), phr_box (P, 4) float32; gold_off (B+1), gold_span (G, 2); gold: the Python list per sentence."""
 
-    def __init__(self, vg_gt, gt, B, L):
+    def __init__(self, vg_gt, gt, B, L, lengths=None):
+        """lengths: per sentence, for a batch of mixed lengths padded to L (a phrase must then lie inside its own sentence)."""
         self.B, self.L = B, L
         self.phrases, spans, boxes = [], [], []
         phr_off = [0]
@@ -41,8 +42,9 @@ class Targets(object):
                 for _, anno in target.items():
                     start, end, box = anno
                     start, end = int(start), int(end)
-                    if not (0 <= start < end <= L):
-                        raise ValueError('sentence %d: phrase [%d, %d) is empty or outside the sentence of length %d' % (b, start, end, L))
+                    n = L if lengths is None else int(lengths[b])
+                    if not (0 <= start < end <= n):
+                        raise ValueError('sentence %d: phrase [%d, %d) is empty or outside the sentence of length %d' % (b, start, end, n))
                     if len(box) != 4:
                         raise ValueError('sentence %d: gold box %r is not (x1, y1, x2, y2)' % (b, box))
                     self.phrases.append((b, start, end))
@@ -100,9 +102,13 @@ def ground_batch(diora, batch_map, spans=None):
     return ground(atten, boxes, tg, spans if spans is not None else diora.cky_spans_device, device=diora._wss[0].device)
 
 
-def ground(atten, boxes, targets, spans, device=None):
+def ground(atten, boxes, targets, spans, device=None, lengths=None, extra_status=()):
     """One cliora_ground_eval launch.  atten: (B, L, R) fp32 CUDA tensor, any strides (None: counts only); boxes (B, R, 4); targets:
-    a Targets; spans: (B, L-1, 2) int32 device tensor, or a callable that writes them into the tensor it is given (the decode)."""
+    a Targets; spans: (B, L-1, 2) int32 device tensor, or a callable that writes them into the tensor it is given (the decode).
+    lengths: int32 device tensor (B,) of a batch of mixed lengths padded to L -- cliora_ground_eval_ragged; the rows of `spans` beyond
+    a sentence's n - 1 come back as (-1, -1).  extra_status: names and one-element int32 device tensors, or callables returning one
+    once the decode has run (the status words of the forward and the decode): they ride in the same device-to-host copy and must
+    be 0."""
     B, L = targets.B, targets.L
     P, G, NS = targets.P, targets.G, L - 1
     R = atten.shape[2] if atten is not None else 0
@@ -111,7 +117,8 @@ def ground(atten, boxes, targets, spans, device=None):
     if not hasattr(lib, 'cliora_ground_eval'):
         raise _lib.ChartLibError('%s has no cliora_ground_eval: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
     # output buffer: [status | sent B*3 | phrases P*4 | spans B*NS*2 | span boxes B*NS*4 (fp32 bits)]
-    sizes = [1, B * 3, P * 4, B * NS * 2, B * NS * 4 if atten is not None else 0]
+    extra_status = list(extra_status)
+    sizes = [1, B * 3, P * 4, B * NS * 2, B * NS * 4 if atten is not None else 0, len(extra_status)]
     offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
     with torch.cuda.device(dev):
         out = torch.empty(offs[-1], device=dev, dtype=torch.int32)
@@ -132,13 +139,32 @@ def ground(atten, boxes, targets, spans, device=None):
         else:
             boxes, sb, sl, sr = None, 0, 0, 0
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-        _lib.check(lib.cliora_ground_eval(B, L, R, p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span), p(phr_box), p(d_spans), G,
-                                          p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]), p(sec[1]), p(sec[0]),
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cliora_ground_eval')
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if lengths is None:
+            _lib.check(lib.cliora_ground_eval(B, L, R, p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span), p(phr_box), p(d_spans), G,
+                                              p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]), p(sec[1]), p(sec[0]), st),
+                       'cliora_ground_eval')
+        else:
+            if not hasattr(lib, 'cliora_ground_eval_ragged'):
+                raise _lib.ChartLibError('%s has no cliora_ground_eval_ragged: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
+            lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+            if lengths.numel() != B:
+                raise ValueError('lengths holds %d sentences, not %d' % (lengths.numel(), B))
+            _lib.check(lib.cliora_ground_eval_ragged(B, L, R, p(lengths), p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span),
+                                                     p(phr_box), p(d_spans), G, p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]),
+                                                     p(sec[1]), p(sec[0]), st), 'cliora_ground_eval_ragged')
+        for k, (_, t) in enumerate(extra_status):
+            sec[5][k:k + 1].copy_((t() if callable(t) else t).reshape(1))
         host = out.cpu().numpy()
     h = [host[offs[i]:offs[i + 1]] for i in range(len(sizes))]
-    if h[0][0]:
+    if h[0][0] and lengths is None:
         raise _lib.ChartLibError('cliora_ground_eval rejected %d phrase(s) / span(s) outside their sentence' % int(h[0][0]))
+    if h[0][0]:
+        raise _lib.ChartLibError('cliora_ground_eval_ragged rejected %d sentence length(s) outside 1..%d, or phrase(s) / span(s) outside '
+                                 'their sentence' % (int(h[0][0]), L))
+    for k, (name, _) in enumerate(extra_status):
+        if h[5][k]:
+            raise _lib.ChartLibError('%s rejected %d sentence length(s)' % (name, int(h[5][k])))
     xyxy = h[4].view(np.float32).reshape(B, NS, 4) if atten is not None else None
     return GroundResult(targets, h[3].reshape(B, NS, 2), h[2], h[1].reshape(B, 3), xyxy)
 
@@ -240,3 +266,68 @@ def evaluate(net, batches, idx2word, out_path=None, postprocess=False):
         if f is not None:
             f.close()
     return ev.result()
+
+
+def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, max_batch=64, max_waste=None, pad_id=0,
+                    return_details=False):
+    """``evaluate`` for examples of any lengths, given in any order: the sentences are packed into right-padded charts
+    (cliora_amd.ragged), each pack costs one forward with the outside pass (cliora_chart_forward_ragged), one cliora_cky_spans_ragged,
+    one cliora_ground_eval_ragged and one device-to-host copy, and the results come back in the caller's order.
+
+    examples: dicts with 'sentence' (token ids), 'example_id', 'GT' (gold constituents, the root last, as batch_map['GT'][b]) and,
+    for a CLIORA net, 'VG_GT' ((phrase dict, noun mask) as batch_map['VG_GT'][b]), 'boxes' (R, 4) and 'obj_feats' (R, img_dim).
+    Examples of length <= 2 are skipped, as ``evaluate`` skips such batches.  Returns the first four METRICS (corpus_f1, sent_f1,
+    ground_acc, ccra); parse.jsonl goes to `out_path` in the caller's order.  The four loss fields are left out: the reference defines
+    the eval losses per uniform-length batch (the reconstruction loss reads every leaf of the batch and shares its negatives, the
+    contrastive and VG losses compare the sentences of a batch with each other), and their ops take no per-sentence lengths.  return_details: also a list with, per
+    example, None (skipped) or a dict of spans (n-1, 2), sent (3,), hit / ccr / word / box per phrase and span_xyxy (n-1, 4)."""
+    from . import ragged
+    diora = net.diora
+    keep = [i for i, ex in enumerate(examples) if len(ex['sentence']) > 2]
+    sents = [list(examples[i]['sentence']) for i in keep]
+    vl = bool(net.obj_feats)
+    feats = torch.stack([torch.as_tensor(examples[i]['obj_feats']) for i in keep]) if vl and keep else None
+    details = [None] * len(examples)
+    lines = [None] * len(examples)
+
+    def per_pack(idx, lens, d):
+        ex = [examples[keep[j]] for j in idx]
+        B, L = len(idx), d._plan.L
+        ns = [len(e['sentence']) for e in ex]
+        atten = d.atten_score if vl else None
+        tg = Targets([e['VG_GT'] for e in ex] if vl else None, [e['GT'] for e in ex], B, L, lengths=ns)
+        boxes = torch.stack([torch.as_tensor(e['boxes'], dtype=torch.float32) for e in ex]) if vl else None
+        cky_status = []
+
+        def decode(out):
+            cky_status.append(ragged.cky_spans_ragged(d, lens, out=out)[1])
+
+        res = ground(atten, boxes, tg, decode, device=d._wss[0].device, lengths=lens,
+                     extra_status=[('cliora_chart_forward_ragged', d._ragged_status), ('cliora_cky_spans_ragged', lambda: cky_status[0])])
+        off = tg.phr_off
+        for b, j in enumerate(idx):
+            n = ns[b]
+            sl = slice(int(off[b]), int(off[b + 1]))
+            det = dict(spans=res.spans[b, :n - 1].copy(), sent=res.sent[b].copy(), hit=res.hit[sl].copy(), ccr=res.ccr[sl].copy(),
+                       word=res.word[sl].copy(), box=res.box[sl].copy(),
+                       span_xyxy=res.span_xyxy[b, :n - 1].copy() if res.span_xyxy is not None else None)
+            details[keep[j]] = det
+            if out_path:
+                one = GroundResult(Targets(None, [ex[b]['GT']], 1, n), det['spans'][None], np.zeros((0, 4), np.int32), det['sent'][None],
+                                   det['span_xyxy'][None] if det['span_xyxy'] is not None else None)
+                tree = diora.trees_from_spans(det['spans'][None])
+                lines[keep[j]] = batch_records(one, tree, [list(ex[b]['sentence'])], [ex[b]['example_id']], idx2word, vl, postprocess)[0]
+
+    ragged.forward_ragged(net, sents, obj_feats=feats, per_pack=per_pack, max_batch=max_batch,
+                          max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste, pad_id=pad_id)
+    ev = Evaluator()
+    for det in details:                 # in the caller's order: the sentence F1s are averaged in it
+        if det is not None:
+            ev.add_counts(det['sent'], det['hit'], det['ccr'])
+    if out_path:
+        with open(out_path, 'w') as f:
+            for line in lines:
+                if line is not None:
+                    f.write(line + '\n')
+    m = {k: v for k, v in ev.result().items() if k in METRICS[:4]}
+    return (m, details) if return_details else m

@@ -225,6 +225,86 @@ def embed_phrases(net, batches, mode, normalize=False, min_size=2, postprocess=F
     return pset
 
 
+def embed_phrases_ragged(net, sentences, mode, example_ids=None, entity_labels=None, trees=None, obj_feats=None, normalize=False,
+                         min_size=2, postprocess=False, idx2word=None, max_batch=64, max_waste=None, pad_id=0):
+    """``embed_phrases`` for sentences of any lengths, given in any order: packed into right-padded charts and run with the outside
+    pass made each sentence's own (cliora_amd.ragged.forward_ragged); cliora_phrase_gather addresses a cell by (sentence, pos, size)
+    within the padded chart's L, so it reads the padded charts as they are.  -> PhraseSet whose rows follow the caller's order of
+    sentences (within a sentence the order of `embed_phrases`), as one batch.
+
+    sentences: lists of token ids; example_ids: one per sentence (default: its index); entity_labels (mode 'entities') / trees
+    (mode 'given'): one entry per sentence, as batch_map['entity_labels'][b] / batch_map['trees'][b]; obj_feats: (N, R, img_dim) for a
+    CLIORA net.  'all-spans' means the cells of each sentence's own triangle.  Sentences of length <= 2 are skipped, as both scripts
+    skip such batches.  Every row must lie inside its sentence (checked on the host)."""
+    from . import ragged
+    if mode not in MODES:
+        raise ValueError('mode %r: one of %s' % (mode, ', '.join(MODES)))
+    if mode == 'entities' and entity_labels is None:
+        raise ValueError("mode 'entities' needs entity_labels")
+    if mode == 'given' and trees is None:
+        raise ValueError("mode 'given' needs the sentences' trees")
+    lib = _native()
+    diora = net.diora
+    dev = next(net.parameters()).device
+    keep = [i for i, s_ in enumerate(sentences) if len(s_) > 2]
+    sents = [list(sentences[i]) for i in keep]
+    feats = obj_feats[torch.as_tensor(keep, dtype=torch.int64)] if obj_feats is not None else None
+    ids = list(example_ids) if example_ids is not None else list(range(len(sentences)))
+    parts = {}                          # position in `sentences` -> (its rows with the sentence renumbered, its vectors on the device)
+
+    def per_pack(idx, lens, d):
+        local = [sents[j] for j in idx]
+        if mode == 'entities':
+            rows = entity_rows([entity_labels[keep[j]] for j in idx], min_size)
+        elif mode == 'given':
+            rows = tree_rows([trees[keep[j]] for j in idx], local, idx2word, postprocess)
+        elif mode == 'latent':
+            spans, status = ragged.cky_spans_ragged(d, lens)
+            host = torch.cat([spans.reshape(-1), status, d._ragged_status]).cpu().numpy()
+            if host[-2:].any():
+                raise _lib.ChartLibError('the padded chart rejected %d sentence length(s)' % int(host[-2:].max()))
+            sp = host[:-2].reshape(spans.shape)
+            cky = [d.trees_from_spans(sp[b:b + 1, :len(local[b]) - 1])[0] for b in range(len(idx))]
+            rows = tree_rows(cky, local, idx2word, postprocess)
+        else:
+            rows = [(b, pos, level + 1, None) for b in range(len(idx)) for level in range(len(local[b]))
+                    for pos in range(len(local[b]) - level)]
+        for b, pos, size, _ in rows:
+            if pos < 0 or size < 1 or pos + size > len(local[b]):
+                raise ValueError('phrase (pos %d, size %d) lies outside its sentence of length %d' % (pos, size, len(local[b])))
+        ih, oh = d.inside_h, d.outside_h
+        B, _, D = ih.shape
+        N = len(rows)
+        with torch.cuda.device(dev):
+            out = torch.empty((N, 2 * D), dtype=torch.float32, device=dev)
+            tab = torch.from_numpy(np.array([r[:3] for r in rows], dtype=np.int32).reshape(-1, 3)).to(dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            _lib.check(lib.cliora_phrase_gather(B, d._plan.L, D, _p(ih), ih.stride(0), ih.stride(1), _p(oh), oh.stride(0), oh.stride(1), N,
+                                                _p(tab), int(bool(normalize)), _p(out), out.stride(0), 0, _p(status), _stream()),
+                       'cliora_phrase_gather')
+            bad = torch.stack([status[0], d._ragged_status[0]]).cpu().tolist() if N else [0, int(d._ragged_status.item())]
+        if any(bad):
+            raise _lib.ChartLibError('the padded chart rejected %d phrase(s) / %d sentence length(s)' % tuple(bad))
+        by_sent = {}
+        for r, row in enumerate(rows):
+            by_sent.setdefault(row[0], []).append(r)
+        for b, rr in by_sent.items():
+            i = keep[idx[b]]
+            parts[i] = ([(i,) + rows[r][1:] for r in rr], out[torch.as_tensor(rr, dtype=torch.int64, device=dev)])
+
+    ragged.forward_ragged(net, sents, obj_feats=feats, per_pack=per_pack, max_batch=max_batch,
+                          max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste, pad_id=pad_id)
+    pset = PhraseSet(dim=diora.size, device=dev)
+    order = sorted(parts)
+    if order:
+        all_rows = [r for i in order for r in parts[i][0]]
+        with torch.cuda.device(dev):
+            pset._reserve(len(all_rows), dev)
+            pset._buf[:len(all_rows)].copy_(torch.cat([parts[i][1] for i in order], 0))
+        pset._record(all_rows, [list(s_) for s_ in sentences], ids)
+    return pset
+
+
 # ---- search --------------------------------------------------------------------------------------------------------------
 def knn_ip(q, keys, k):
     """cliora_knn_ip: (D, I) = faiss.IndexFlatIP search of the rows of q among the rows of keys (fp32 CUDA, unit column stride, any

@@ -7,12 +7,19 @@ sentence of length n padded on the right to Lmax has, in its own triangle of the
 per-split scores a chart of length n would hold, and the CKY tree needs only those.  ``cliora_cky_spans_ragged`` (include/
 cliora_chart.h) decodes each sentence from its own triangle; ``cliora_phrase_gather`` reads the inside vector of its own root cell.
 
-The OUTSIDE pass is not prefix-closed (in a padded chart every cell has parents that reach beyond the sentence), so this module is
-inference of trees and inside vectors only: it runs the chart with the outside pass off and nothing here may be trained through.
+The OUTSIDE pass is not prefix-closed (in a padded chart every cell has parents that reach beyond the sentence), but masking makes
+it the sentence's own without touching a level kernel (``cliora_chart_forward_ragged``): a pair (parent,
+sibling) of a cell of the triangle leaves the triangle iff its sibling does and its score adds inside_s[sibling], so -1e30 written
+into inside_s beyond each triangle after the inside pass zeroes those pairs' softmax weights, and each sentence's root cell
+(n - 1, 0) receives the seed rows after its level.  ``forward_ragged`` runs both passes that way, for text-only and CLIORA nets;
+``evaluate.evaluate_ragged`` and ``phrases.embed_phrases_ragged`` are built on it.  Inference only: nothing here may be trained
+through.
 
-    from cliora_amd.ragged import parse_ragged, encode_ragged
-    trees = parse_ragged(net, sentences)        # net: harness.Net (text-only); sentences: lists of token ids, any lengths 1..64
+    from cliora_amd.ragged import parse_ragged, encode_ragged, forward_ragged
+    trees = parse_ragged(net, sentences)        # net: harness.Net; sentences: lists of token ids, any lengths 1..64
     vecs = encode_ragged(net, sentences)        # (N, D) inside vectors of the sentences' roots, on the device
+    trees = parse_ragged(vl_net, sentences, obj_feats=feats)     # a CLIORA net: region features (N, R, img_dim), one row per sentence
+    forward_ragged(net, sentences, per_pack=lambda idx, lens, diora: ...)    # both passes; diora holds the pack's padded charts
 """
 import ctypes as C
 
@@ -119,12 +126,13 @@ def decode_ragged_numpy(pair_s, lengths):
     return out
 
 
-def cky_spans_ragged(diora, lengths, split_out=False):
+def cky_spans_ragged(diora, lengths, split_out=False, out=None):
     """cliora_cky_spans_ragged on a chart module after its forward over a right-padded batch.
 
     lengths: int32 tensor (B,), one per sentence of the chart.  -> (spans, status) or (spans, status, split): spans (B, L-1, 2) int32
     with (-1, -1) beyond each sentence's n - 1 rows; status (number of workspaces,) int32 counting the lengths outside [1, L], which
-    the caller must check; split (B, C) int32, -1 at the leaves and outside each triangle.  Device tensors; nothing is synchronised."""
+    the caller must check; split (B, C) int32, -1 at the leaves and outside each triangle.  Device tensors; nothing is synchronised.
+    out: a contiguous int32 tensor (B, L-1, 2) on the chart's device to decode into (cliora_amd.evaluate: its output buffer)."""
     lib = _native()
     plan, wss = diora._plan, diora._wss
     B, L = plan.B, plan.L
@@ -134,7 +142,12 @@ def cky_spans_ragged(diora, lengths, split_out=False):
     dev = wss[0].device
     with torch.cuda.device(dev):
         lengths = lengths.to(dev).contiguous()
-        spans = torch.empty((B * nws, L - 1, 2), dtype=torch.int32, device=dev)
+        if out is not None:
+            if out.shape != (B * nws, L - 1, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+                raise ValueError('out must be a contiguous int32 tensor (%d, %d, 2) on %s' % (B * nws, L - 1, dev))
+            spans = out
+        else:
+            spans = torch.empty((B * nws, L - 1, 2), dtype=torch.int32, device=dev)
         status = torch.empty(nws, dtype=torch.int32, device=dev)
         split = torch.empty((B * nws, plan.C), dtype=torch.int32, device=dev) if split_out else None
         for i, ws in enumerate(wss):
@@ -166,46 +179,96 @@ def root_rows(diora, lengths):
     return out[:, :D]
 
 
-def _check_module(diora):
+def root_level_mask(lengths):
+    """Bit t set iff some sentence has n - 1 == t: the outside levels after which cliora_chart_forward_ragged seeds a root."""
+    m = 0
+    for n in lengths:
+        if 1 <= int(n) <= MAX_L:
+            m |= 1 << (int(n) - 1)
+    return m
+
+
+def _check_module(net, obj_feats):
+    from .cliora import DioraMLP as VLDiora
     from .diora import DioraMLP as TextDiora
-    if not isinstance(diora, TextDiora):
-        raise NotImplementedError(
-            'ragged batches need the text-only cliora_amd.diora.DioraMLP, got %s: the vision-language module goes on to score regions '
-            'against inside_h + outside_h, and the outside pass of a padded chart is not that of the sentence' % type(diora).__name__)
-
-
-def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack):
-    """pack -> per pack: pad, embed, inside pass without the outside pass, `per_pack(indices, lengths_on_device)`."""
     diora = net.diora
-    _check_module(diora)
+    if isinstance(diora, VLDiora):
+        if obj_feats is None:
+            raise NotImplementedError(
+                'the vision-language module scores regions against inside_h + outside_h of every cell: pass the region features of '
+                'every sentence (obj_feats=) to run it on a padded chart')
+        return True
+    if not isinstance(diora, TextDiora):
+        raise NotImplementedError('ragged batches need cliora_amd.diora.DioraMLP or cliora_amd.cliora.DioraMLP, got %s'
+                                  % type(diora).__name__)
+    if obj_feats is not None:
+        raise ValueError('obj_feats given to a text-only net')
+    return False
+
+
+def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats=None, outside=False):
+    """pack -> per pack: pad, embed (and encode the regions), chart forward, `per_pack(indices, lengths_on_device)`.  outside False:
+    the inside pass alone through the module's ordinary forward; True: both passes through cliora_chart_forward_ragged."""
+    diora = net.diora
+    vl = _check_module(net, obj_feats)
     lengths = [len(s) for s in sentences]
     if not lengths:
         return
     if min(lengths) < 1:
         raise ValueError('an empty sentence has no chart')
+    if vl and len(obj_feats) != len(sentences):
+        raise ValueError('obj_feats holds %d sentences, not %d' % (len(obj_feats), len(sentences)))
     dev = next(net.parameters()).device
     if max(lengths) > MAX_L:         # the plan's own refusal, before any pack has run
         _lib.get_plan(1, max(lengths), diora.size, diora.share, diora.normalize, 0, dev.index if dev.type == 'cuda' else -1)
     was_training, had_outside = net.training, diora.outside
     net.eval()
-    diora.outside = False
+    diora.outside = bool(outside)
     try:
         with torch.no_grad():
             for idx in pack(lengths, max_batch, max_waste):
                 tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
                 x_span, x_word = net.embed(tokens.to(dev))
-                diora(x_span, x_word)
-                per_pack(idx, lens.to(dev))
+                o_span = o_word = None
+                if vl:
+                    o_span, o_word = net.img_encoder(obj_feats[torch.as_tensor(idx, dtype=torch.int64)].to(dev))
+                lens = lens.to(dev)
+                if outside:
+                    diora.__dict__['_ragged'] = (lens, root_level_mask(lengths[i] for i in idx))
+                try:
+                    diora(x_span, x_word, o_span, o_word)
+                finally:
+                    diora.__dict__['_ragged'] = None
+                per_pack(idx, lens)
     finally:
         diora.outside = had_outside
         net.train(was_training)
 
 
-def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
+def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
+    """Both passes over sentences of any lengths in 1..64: packs them (``pack``), runs each pack as one right-padded chart through
+    cliora_chart_forward_ragged in eval mode under no_grad, and calls ``per_pack(indices, lengths, diora)`` after each -- `indices`
+    the pack's positions in `sentences`, `lengths` their int32 lengths on the device, `diora` the chart module holding the pack's
+    state: the four charts, valid on each sentence's own triangle (cells beyond it are unspecified), and for a CLIORA net
+    atten_score[b, :n_b] / vg_atten_score.  `diora._ragged_status` is the call's status word, still on the device: the callback (or
+    whoever reads the pack's results) must find it 0.  obj_feats: (N, R, img_dim) region features, one row per sentence, for a
+    CLIORA net.  Returns the packs.  Training mode and the module's `outside` are restored afterwards."""
+    packs = []
+
+    def each(idx, lens):
+        packs.append(idx)
+        if per_pack is not None:
+            per_pack(idx, lens, net.diora)
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, each, obj_feats=obj_feats, outside=True)
+    return packs
+
+
+def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None):
     """Best binary tree of every sentence (nested tuples of word positions as ``DioraBase.cky()``; 0 for a single word), in the
-    caller's order.  net: a text-only harness.Net; sentences: sequences of token ids of any lengths in 1..64.  Runs in eval mode under
-    no_grad with the outside pass off (both restored afterwards; the module's chart is left as the last pack's, outside_h unwritten).
-    One device-to-host copy per pack."""
+    caller's order.  net: a harness.Net; sentences: sequences of token ids of any lengths in 1..64; obj_feats: the region features
+    (N, R, img_dim) of a CLIORA net, one row per sentence.  Runs in eval mode under no_grad with the outside pass off (both restored
+    afterwards; the module's chart is left as the last pack's, outside_h unwritten).  One device-to-host copy per pack."""
     diora = net.diora
     trees = [None] * len(sentences)
 
@@ -219,11 +282,11 @@ def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_
         for b, i in enumerate(idx):
             trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode, obj_feats=obj_feats)
     return trees
 
 
-def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
+def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None):
     """(N, D) fp32 on the device: row i = inside_h of sentence i's root cell (its own length's root, not the padded chart's), the
     vector DIORA users read off the root.  Same plumbing as parse_ragged."""
     diora = net.diora
@@ -233,5 +296,5 @@ def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad
     def gather(idx, lens):
         out[torch.tensor(idx, dtype=torch.int64, device=dev)] = root_rows(diora, lens)
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, gather)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, gather, obj_feats=obj_feats)
     return out

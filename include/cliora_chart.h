@@ -289,15 +289,44 @@ int cliora_cky_decode(cliora_plan* plan, void* fwd_workspace, int32_t* split_out
 int cliora_cky_spans(cliora_plan* plan, void* fwd_workspace, int32_t* split_out, int32_t* spans_out, void* stream);
 /* The decode for sentences of DIFFERENT lengths that were run as one batch, each padded on the right to the plan's L.  The inside
  * pass is prefix-closed -- cell (level, pos) with pos + level < n reads only cells of words [0, n) -- so sentence b's own triangle of
- * the padded chart holds what a chart of length n = lengths[b] would ("Mixed-length batches"); the outside pass is not, and
- * nothing here reads it.  One workgroup per sentence evaluates levels 1 .. n-1 at positions pos < n - level only (the same candidate
- * in the same order as cliora_cky_spans, first maximum wins) and walks from cell (n-1, 0).
+ * the padded chart holds what a chart of length n = lengths[b] would ("Mixed-length batches"); nothing here reads the
+ * outside pass (cliora_chart_forward_ragged makes that one the sentence's own too).  One workgroup per sentence evaluates levels
+ * 1 .. n-1 at positions pos < n - level only (the same candidate in the same order as cliora_cky_spans, first maximum wins) and
+ * walks from cell (n-1, 0).
  *   lengths (B) int32 device.  spans_out (B, L-1, 2): the first n-1 rows are the sentence's spans in cliora_cky_spans' order, the
  *   root (0, n-1) last; the remaining rows are (-1, -1).  split_out (B, C) or NULL: -1 at the leaves and outside the triangle.
  *   A length outside [1, L] is not decoded: every row of that sentence is -1 and it is counted in *status (an int32 on the device the
  *   call zeroes first), which the caller must check.  With lengths[b] == L for every b the outputs are those of cliora_cky_spans. */
 int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, int32_t* split_out, int32_t* spans_out,
                             int32_t* status, void* stream);
+/* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
+ * arguments of cliora_chart_forward, plus
+ *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
+ *   host, so the call makes no device-to-host copy; a sentence whose bit is missing gets an unspecified outside chart);
+ *   status: an int32 on the device the call zeroes first, then counts the lengths outside [1, L] in -- the caller must check it; the
+ *   cells of such a sentence are unspecified (nothing is read or written out of bounds).
+ * For every cell of sentence b's own triangle (pos + level < lengths[b]) the four charts hold what cliora_chart_forward computes for
+ * that sentence alone at its exact length, to rounding (the level kernels tile a level by its row count).  Cells OUTSIDE a
+ * sentence's triangle are unspecified in all four charts -- inside_s holds -1e30 there, written whether or not bit 0 of run_outside
+ * asks for the outside pass.  normalize = none: nothing bounds the vectors of the padded cells, so padded input whose unnormalised
+ * charts leave fp32's range (as they do at any length beyond a few words with N(0, 1) weights) can bring a non-finite value into a
+ * sentence's own cells through a 0-weight pair; the same holds for the padded inside pass.  With normalize = unit every value is
+ * finite.  How: the inside pass is prefix-closed; an
+ * outside pair (parent, sibling) of a cell of the triangle leaves the triangle iff its sibling does, and its score adds
+ * inside_s[sibling], so the -1e30 written after the inside pass gives those pairs a softmax weight of exactly 0 in the unchanged
+ * level kernels; the sentence's root cell (lengths[b] - 1, 0) then receives the rows of the padded chart's root cell after its level
+ * has run, and the level below is scored again.  Schedule: inside levels, mask, root, outside levels one
+ * after the other on the caller's stream -- no wavefront, no side stream, no resident kernels.  The per-split scores in the
+ * workspace are untouched by the outside pass: cliora_cky_spans_ragged after this call decodes what it decodes after the
+ * inside-only forward.  With every length equal to L the charts are bitwise those of cliora_chart_forward on the sequential
+ * schedule (cliora_set_wavefront(0), launch path).
+ * Refused with CLIORA_EINVAL and a message: run_outside without CLIORA_FWD_NO_BACKWARD (a padded chart has no backward), with
+ * CLIORA_FWD_PAIR_STATES, a drop_mask, params->root_mat (compress), TreeLSTM plans.  Text-only and CLIORA plans, share 0 / 1,
+ * normalize unit / none. */
+int cliora_chart_forward_ragged(cliora_plan* plan, const cliora_params* params, const float* x_span, const float* obj_span,
+                                const float* drop_mask, float* inside_h, float* inside_s, float* outside_h, float* outside_s,
+                                float* inside_c, void* fwd_workspace, size_t fwd_workspace_bytes, int run_outside,
+                                const int32_t* lengths, uint64_t root_levels, int32_t* status, void* stream);
 
 /* Grounding evaluation (cliora/scripts/parse.py:176-264, the host loop over every phrase and predicted span): ONE launch for a batch,
  * one workgroup per sentence.  All pointers are device memory.
@@ -321,6 +350,15 @@ int cliora_ground_eval(int B, int L, int R, const float* atten, int64_t atten_sb
                        const float* boxes, int P, const int32_t* phr_off, const int32_t* phr_span, const float* phr_box,
                        const int32_t* spans, int G, const int32_t* gold_off, const int32_t* gold_span, int32_t* phr_out,
                        int32_t* span_box, float* span_xyxy, int32_t* sent_out, int32_t* status, void* stream);
+/* The same for a batch of sentences of different lengths padded to L: lengths (B) int32 device.  Sentence b is its first
+ * n = lengths[b] words: rows 0 .. n-2 of `spans` are read (cliora_cky_spans_ragged's layout, the root = row n-2), phrases must satisfy
+ * 0 <= start < end <= n, rows of atten beyond word n-1 are not read, and rows n-1 .. L-2 of span_box / span_xyxy are written as -1 / 0.
+ * A length outside [1, L] is counted in *status and the sentence is not read (its phrases get (-1, -1, 0, 0) and count too).  The same
+ * kernel with the same rules; with every length equal to L the outputs are bitwise those of cliora_ground_eval. */
+int cliora_ground_eval_ragged(int B, int L, int R, const int32_t* lengths, const float* atten, int64_t atten_sb, int64_t atten_sl,
+                              int64_t atten_sr, const float* boxes, int P, const int32_t* phr_off, const int32_t* phr_span,
+                              const float* phr_box, const int32_t* spans, int G, const int32_t* gold_off, const int32_t* gold_span,
+                              int32_t* phr_out, int32_t* span_box, float* span_xyxy, int32_t* sent_out, int32_t* status, void* stream);
 
 /* Phrase vectors (cliora/scripts/phrase_embed.py:79-92, 223-224; phrase_embed_simple.py:262-287): ONE launch for a batch's
  * phrases, one wavefront per phrase.  All pointers are device memory.
