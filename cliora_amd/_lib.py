@@ -13,6 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CLIORA_CHART_LIB') or os.path.join(HERE, 'libcliora_chart.so')   # override: kernel experiments only
 
 NORM = {'none': 0, 'unit': 1}
+MAX_L = 64               # csrc/plan.hpp CLIORA_MAX_L: the longest sentence of anything with a backward, of TreeLSTM / compress plans, of the ragged both-pass entries
+MAX_L_FWD = 128          # csrc/plan.hpp CLIORA_MAX_L_FWD: the longest sentence of a forward-only ("long") DioraMLP / CLIORA plan
 FWD_NO_BACKWARD = 2      # include/cliora_chart.h: flag bits of cliora_chart_forward's run_outside word
 FWD_PAIR_STATES = 4
 KCLASS = {'compose_fwd': 0, 'compose_bwd': 1, 'wgrad': 2}
@@ -198,7 +200,12 @@ def check(rc, what):
 class Plan:
     """Owns one cliora_plan (chart shape + device index tables)."""
 
-    def __init__(self, B, L, D, share=True, normalize='unit', R=0, arch=0):
+    def __init__(self, B, L, D, share=True, normalize='unit', R=0, arch=0, forward_only=False):
+        # A plan of 64 < L <= 128 words is forward only (no backward workspace, no use lists: include/cliora_chart.h), so it has to be
+        # asked for as such: whoever holds a Plan may otherwise count on bwd_bytes and cliora_chart_backward.  get_plan() asks.
+        if L > MAX_L and not forward_only:
+            raise ChartLibError('L > %d is not supported by a plan with a backward (one split per lane in its softmax kernels): '
+                                'Plan(..., forward_only=True) covers L <= %d for inference' % (MAX_L, MAX_L_FWD))
         self.key = (B, L, D, bool(share), normalize, R, arch)
         self.arch = arch
         self.B, self.L, self.D, self.share, self.normalize, self.R = B, L, D, bool(share), normalize, R
@@ -233,7 +240,8 @@ class Plan:
 # Plan cache: least-recently-used, bounded by the bytes of index tables the cached plans hold on the device AND by their number
 # (the host-side use lists of a plan are several times its device tables).  Length-bucketed batches give one (B, L) key per bucket:
 # a DioraMLP plan holds 0.1 MB (L 20) to 1 MB (L 40) of device tables, a TreeLSTM plan at B 64 / L 40 about 25 MB (its
-# batch-expanded row maps).
+# batch-expanded row maps).  A long plan (64 < L <= 128, forward only) uploads its pair tables alone, no use lists: 1.1 MB at L 65,
+# 8.4 MB at L 128 -- table_bytes is what cliora_plan_device_bytes reports for it, so the budget below counts it as it is.
 PLAN_CACHE_BYTES = int(os.environ.get('CLIORA_PLAN_CACHE_MB', '512')) << 20
 PLAN_CACHE_MAX = int(os.environ.get('CLIORA_PLAN_CACHE_MAX', '128'))
 _plans = collections.OrderedDict()
@@ -245,7 +253,7 @@ def get_plan(B, L, D, share, normalize, R, device_index, arch=0):
     if pl is not None:
         _plans.move_to_end(key)
         return pl
-    pl = _plans[key] = Plan(B, L, D, share, normalize, R, arch)
+    pl = _plans[key] = Plan(B, L, D, share, normalize, R, arch, forward_only=L > MAX_L)    # long plans: the modules refuse training on them
     total = sum(q.table_bytes for q in _plans.values())
     while (total > PLAN_CACHE_BYTES or len(_plans) > PLAN_CACHE_MAX) and len(_plans) > 1:
         _, old = _plans.popitem(last=False)          # evicted plans free their device tables when the last user drops them

@@ -376,6 +376,10 @@ class DioraMLP(DioraBase):
         R = obj_embed_span.shape[1]
         assert D == self.size
         dev_index = x_span.device.index if x_span.is_cuda else -1
+        if L > _lib.MAX_L:       # a forward-only plan (include/cliora_chart.h): refusals before the plan and any launch
+            self._check_long(L, self.training or (torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad for t in [x_span, obj_embed_span] + list(self._param_tensors()))),
+                self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook'))
         plan = _lib.get_plan(B, L, D, self.share, self.normalize, R, dev_index)
         mask = None
         if self.training:

@@ -52,7 +52,7 @@ extern "C" int cliora_plan_create(int B, int L, int D, int share, int normalize,
     if (!out) return fail(CLIORA_EINVAL, "out is NULL");
     cliora_plan* pl = new (std::nothrow) cliora_plan();
     if (!pl) return fail(CLIORA_ENOMEM, "host allocation failed");
-    const std::string e = build_plan(pl->p, B, L, D, share, normalize, R);
+    const std::string e = build_plan(pl->p, B, L, D, share, normalize, R, 0, CLIORA_MAX_L_FWD);
     if (!e.empty()) { delete pl; return fail(CLIORA_EINVAL, e); }
     *out = pl;
     return CLIORA_OK;
@@ -62,7 +62,7 @@ extern "C" int cliora_plan_create_ex(int B, int L, int D, int share, int normali
     if (!out) return fail(CLIORA_EINVAL, "out is NULL");
     cliora_plan* pl = new (std::nothrow) cliora_plan();
     if (!pl) return fail(CLIORA_ENOMEM, "host allocation failed");
-    const std::string e = build_plan(pl->p, B, L, D, share, normalize, R, arch);
+    const std::string e = build_plan(pl->p, B, L, D, share, normalize, R, arch, CLIORA_MAX_L_FWD);
     if (!e.empty()) { delete pl; return fail(CLIORA_EINVAL, e); }
     *out = pl;
     return CLIORA_OK;
@@ -123,7 +123,7 @@ struct DeviceLanes {
     hipStream_t side = nullptr, side2 = nullptr;
     bool side2_beside = false;              // the probe found side2 concurrent with the caller's stream and side (not queued behind either)
     hipStream_t side3 = nullptr;            // the callers' lane (cliora_device_side_stream), created at its first request
-    hipEvent_t fork[3], join[3], level[CLIORA_MAX_L + 1];
+    hipEvent_t fork[3], join[3], level[CLIORA_MAX_L_FWD + 1];
     unsigned long long* trace = nullptr;    // TRACE_BYTES of device words for the diagnostic stamps of the resident kernels (CLIORA_RES_TRACE)
     int ncu = 0;
     std::mutex mu;
@@ -206,7 +206,7 @@ static int device_lanes(int dev, hipStream_t st, DeviceLanes** out) {
             HIPOK(hipEventCreateWithFlags(&ln->fork[k], ev_flags));
             HIPOK(hipEventCreateWithFlags(&ln->join[k], ev_flags));
         }
-        for (int k = 0; k <= CLIORA_MAX_L; ++k) HIPOK(hipEventCreateWithFlags(&ln->level[k], ev_flags));
+        for (int k = 0; k <= CLIORA_MAX_L_FWD; ++k) HIPOK(hipEventCreateWithFlags(&ln->level[k], ev_flags));
         HIPOK(hipMalloc((void**)&ln->trace, TRACE_BYTES));
         HIPOK(hipMemsetAsync(ln->trace, 0, TRACE_BYTES, st));
         HIPOK(hipDeviceGetAttribute(&ln->ncu, hipDeviceAttributeMultiprocessorCount, dev));
@@ -300,7 +300,11 @@ extern "C" int cliora_outside_pair_states(const cliora_plan* plan, void* fwd_ws,
 // order (cky.py:83, utils.py:89-90); argmax keeps the first maximum (cky.py:86).
 // One workgroup of CKY_WAVES wavefronts per sentence (round 5: was one wavefront walking every cell in turn -- 190 dependent steps at
 // L 20; the cells of a level are independent, so wave w takes the positions w, w + CKY_WAVES, ... and the level ends with one barrier).
+// LONG: a long plan (plan.hpp: L <= 128, up to 127 splits per cell) -- a lane takes the splits `lane` and `lane + 64`, the earlier one on
+// a tie, then the same butterfly.  LDS: 8 C + 12 (L + 1) bytes = 67.6 KB at L 128 (C = 8 256), inside the CU's 160 KB, so the value
+// table stays in LDS; above 64 KB the launch raises the kernel's dynamic-LDS limit (cliora_ensure_max_lds).
 constexpr int CKY_WAVES = 4;
+template <bool LONG = false>
 __global__ __launch_bounds__(CKY_WAVES * 64) void cky_kernel(int L, int C, const int32_t* __restrict__ level_off_tab_a, const int32_t* __restrict__ pair_a,
                                                  const int32_t* __restrict__ pair_b, const int32_t* __restrict__ lvl_base, int B,
                                                  const float* __restrict__ Sp, int32_t* __restrict__ split, int32_t* __restrict__ spans) {
@@ -323,6 +327,17 @@ __global__ __launch_bounds__(CKY_WAVES * 64) void cky_kernel(int L, int C, const
             float cand = -INFINITY;
             if (an) cand = (val[pair_a[loc + lane]] + val[pair_b[loc + lane]]) + (s - smax);
             float best = cand; int bi = an ? lane : 0x7fffffff;
+            if constexpr (LONG) {
+                const bool an1 = lane + 64 < N;
+                const float s1 = an1 ? Sp[row0 + lane + 64] : -INFINITY;
+                const float smax2 = wave_max(fmaxf(s, s1));
+                best = -INFINITY;
+                if (an) best = (val[pair_a[loc + lane]] + val[pair_b[loc + lane]]) + (s - smax2);
+                if (an1) {
+                    const float c1 = (val[pair_a[loc + lane + 64]] + val[pair_b[loc + lane + 64]]) + (s1 - smax2);
+                    if (c1 > best) { best = c1; bi = lane + 64; }
+                }
+            }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
                 const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
@@ -360,7 +375,13 @@ static int launch_cky(cliora_plan* plan, void* fwd_ws, int32_t* split_out, int32
     Plan& p = plan->p;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)p.C * (sizeof(float) + sizeof(int32_t)) + (size_t)3 * (p.L + 1) * sizeof(int32_t);
-    hipLaunchKernelGGL(cky_kernel, dim3(p.B), dim3(CKY_WAVES * 64), lds, st, p.L, p.C, (const int32_t*)nullptr,
+    if (p.is_long()) {
+        if (lds > 64 * 1024) OKR(cliora_ensure_max_lds((const void*)cky_kernel<true>));
+        hipLaunchKernelGGL(cky_kernel<true>, dim3(p.B), dim3(CKY_WAVES * 64), lds, st, p.L, p.C, (const int32_t*)nullptr,
+                           p.d_tables + p.dev.pair_a_in, p.d_tables + p.dev.pair_b_in, p.d_tables + p.dev.lvl_base_in, p.B,
+                           (const float*)fwd_ws + p.fwd.sp, split_out, spans_out);
+    } else
+    hipLaunchKernelGGL(cky_kernel<false>, dim3(p.B), dim3(CKY_WAVES * 64), lds, st, p.L, p.C, (const int32_t*)nullptr,
                        p.d_tables + p.dev.pair_a_in, p.d_tables + p.dev.pair_b_in, p.d_tables + p.dev.lvl_base_in, p.B,
                        (const float*)fwd_ws + p.fwd.sp, split_out, spans_out);
     LAUNCHOK("cky_kernel");

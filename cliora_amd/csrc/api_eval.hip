@@ -9,7 +9,7 @@ static int ground_eval_run(const char* what, int B, int L, int R, const float* a
                            const int32_t* spans, int G, const int32_t* gold_off, const int32_t* gold_span, int32_t* phr_out,
                            int32_t* span_box, float* span_xyxy, int32_t* sent_out, int32_t* status, const int32_t* lengths, void* stream) {
     const std::string w(what);
-    if (B < 0 || L < 1 || L > CLIORA_MAX_L || P < 0 || G < 0) return fail(CLIORA_EINVAL, w + ": bad B / L / P / G");
+    if (B < 0 || L < 1 || L > CLIORA_MAX_L_FWD || P < 0 || G < 0) return fail(CLIORA_EINVAL, w + ": bad B / L / P / G");
     if (B == 0) return CLIORA_OK;
     if (!phr_off || !gold_off || !sent_out || !status || (L > 1 && !spans) || (G > 0 && !gold_span))
         return fail(CLIORA_EINVAL, w + ": NULL argument");

@@ -109,35 +109,40 @@ static int launch_level_compose_bwd(hipStream_t st, const float* WT, const float
 // `stop`: an event to be signalled by the level_project launch itself (hipExtLaunchKernelGGL's stop event: the dispatch packet's own
 // completion signal) instead of by a hipEventRecord behind it -- the record is a barrier packet of its own on the chain's queue, and the
 // kernel behind it started 6-7 us late at every level of the forward's inside chain (profiles/r04_notes.md).  nullptr: none.
-template <int CT, int SP>
+template <int CT, int SP, bool LONG = false>
 static int launch_level_project_inst(hipStream_t st, const float* Wfrag, int K, int ncols, int ncell, int Lc, int C, int off, const float* HP,
                                      size_t hp_stride, int normalize, const float* bias, float* P, int ldp, float* H, float* nrm,
                                      const ScoreArgs& sc, hipEvent_t stop) {
     const int nrg = (ncell + 15) / 16;
     const int nrgp = nrg >= 8 ? (nrg + 7) / 8 * 8 : nrg;          // column blocks of one row group share an XCD
     const int ncb = ncols / (16 * CT);
-    LAUNCH_SIGNALLING(stop, (level_project<CT, SP>), dim3(sc.nscore + nrgp * ncb), dim3(256), 0, st, Wfrag, K, nrg, nrgp, ncb, ncell, Lc,
+    LAUNCH_SIGNALLING(stop, (level_project<CT, SP, LONG>), dim3(sc.nscore + nrgp * ncb), dim3(256), 0, st, Wfrag, K, nrg, nrgp, ncb, ncell, Lc,
                       C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc);
     LAUNCHOK("level_project");
     return CLIORA_OK;
 }
-template <int CT>
+template <int CT, bool LONG = false>
 static int launch_level_project_sp(hipStream_t st, int SP, const float* Wfrag, int K, int ncols, int ncell, int Lc, int C, int off,
                                    const float* HP, size_t hp_stride, int normalize, const float* bias, float* P, int ldp, float* H, float* nrm,
                                    const ScoreArgs& sc, hipEvent_t stop) {
     switch (SP) {
-        case 1: return launch_level_project_inst<CT, 1>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
-        case 2: return launch_level_project_inst<CT, 2>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
-        case 3: return launch_level_project_inst<CT, 3>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
-        default: return launch_level_project_inst<CT, 4>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
+        case 1: return launch_level_project_inst<CT, 1, LONG>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
+        case 2: return launch_level_project_inst<CT, 2, LONG>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
+        case 3: return launch_level_project_inst<CT, 3, LONG>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
+        default: return launch_level_project_inst<CT, 4, LONG>(st, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
     }
 }
 // h = unit(sum of the SP parts) for the level's cells (chart rows of H, raw norms) and P = h W^T + bias; sc: the next level's
 // scoring, in the same launch
 static int launch_level_project(hipStream_t st, int SP, const float* Wfrag, int K, int ncols, int ncell, int Lc, int C, int off, const float* HP,
                                 size_t hp_stride, int normalize, const float* bias, float* P, int ldp, float* H, float* nrm, const ScoreArgs& sc,
-                                hipEvent_t stop = nullptr) {
+                                hipEvent_t stop = nullptr, bool lng = false) {
     const int nt = ncols / 16, nrt = (ncell + 15) / 16;
+    if (lng) {        // a long plan (plan.hpp): the riding scores take two splits per lane (score_cell<true>); same tile rule
+        if (nt % 5 == 0 && nrt * (nt / 5) >= KSPLIT_MIN_BLOCKS)
+            return launch_level_project_sp<5, true>(st, SP, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
+        return launch_level_project_sp<1, true>(st, SP, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
+    }
     // a block's MFMA work and operand bytes are fixed by its tile: wide tiles only when the launch still covers the chip
     if (nt % 5 == 0 && nrt * (nt / 5) >= KSPLIT_MIN_BLOCKS)
         return launch_level_project_sp<5>(st, SP, Wfrag, K, ncols, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm, sc, stop);
@@ -180,19 +185,20 @@ static int launch_level_compose2(hipStream_t st, const ComposeSeg& a, const Comp
 #undef LC2_CASE
 #undef LC2_ARGS
 }
-template <int SP0, int SP1>
+template <int SP0, int SP1, bool LONG = false>
 static int launch_level_project2_inst(hipStream_t st, const ProjSeg& a, const ProjSeg& b) {
     const int n = a.sc.nscore + b.sc.nscore + a.nproj + b.nproj + a.nfin + b.nfin;
     if (n <= 0) return CLIORA_OK;
-    hipLaunchKernelGGL((level_project2<SP0, SP1>), dim3(n), dim3(256), 0, st, a, b);
+    hipLaunchKernelGGL((level_project2<SP0, SP1, LONG>), dim3(n), dim3(256), 0, st, a, b);
     LAUNCHOK("level_project2");
     return CLIORA_OK;
 }
 static bool project2_parts_ok(int SP) { return SP == 1 || SP == 2 || SP == 4; }      // what plan.cpp compose_geom deals (powers of two <= HP_PARTS)
-static int launch_level_project2(hipStream_t st, int SP0, int SP1, const ProjSeg& a, const ProjSeg& b) {
+template <bool LONG>
+static int launch_level_project2_sel(hipStream_t st, int SP0, int SP1, const ProjSeg& a, const ProjSeg& b) {
 #define P2_ROW(s0) \
-    switch (SP1) { case 1: return launch_level_project2_inst<s0, 1>(st, a, b); case 2: return launch_level_project2_inst<s0, 2>(st, a, b); \
-                   default: return launch_level_project2_inst<s0, 4>(st, a, b); }
+    switch (SP1) { case 1: return launch_level_project2_inst<s0, 1, LONG>(st, a, b); case 2: return launch_level_project2_inst<s0, 2, LONG>(st, a, b); \
+                   default: return launch_level_project2_inst<s0, 4, LONG>(st, a, b); }
     if (!project2_parts_ok(SP0) || !project2_parts_ok(SP1)) return fail(CLIORA_EINVAL, "level_project2: parts per level must be 1, 2 or 4");
     switch (SP0) {
         case 1: P2_ROW(1)
@@ -200,6 +206,10 @@ static int launch_level_project2(hipStream_t st, int SP0, int SP1, const ProjSeg
         default: P2_ROW(4)
     }
 #undef P2_ROW
+}
+// lng: a long plan (plan.hpp), whose riding scores take two splits per lane
+static int launch_level_project2(hipStream_t st, int SP0, int SP1, const ProjSeg& a, const ProjSeg& b, bool lng = false) {
+    return lng ? launch_level_project2_sel<true>(st, SP0, SP1, a, b) : launch_level_project2_sel<false>(st, SP0, SP1, a, b);
 }
 
 // Two streams pay when a level's launches carry enough work to outweigh the event per step (3 us): measured on MI355X from
@@ -246,7 +256,7 @@ static size_t resident_lds_bytes(const Plan& p) {
 }
 static bool resident_pays(const cliora_plan* plan, bool vl, bool compress, bool /*backward*/) {
     const Plan& p = plan->p;
-    if (g_cliora_resident == 0 || vl || compress || p.arch != 0 || p.L < 2 || p.Dp > 64) return false;
+    if (g_cliora_resident == 0 || vl || compress || p.arch != 0 || p.L < 2 || p.L > CLIORA_MAX_L || p.Dp > 64) return false;
     if (resident_lds_bytes(p) > 160 * 1024) return false;
     if (g_cliora_resident < 0) {
         // short sentences (the chain of L steps beats the launch boundaries), or enough sentences to give every other CU its own
@@ -319,6 +329,17 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
     // compress = True (diora.py:342-343): the outside root is a projection of the inside root, so the passes run one after the other
     const bool compress = P->root_mat != nullptr;
     if (!compress && !P->root_h) return fail(CLIORA_EINVAL, "root_h (or root_mat with compress = True) is NULL");
+    const bool lng = p.is_long();
+    if (lng) {      // 64 < L <= 128: forward only (plan.hpp); every refusal before the first launch
+        if (!(run_outside & CLIORA_FWD_NO_BACKWARD))
+            return fail(CLIORA_EINVAL, "L > 64 is forward only: pass CLIORA_FWD_NO_BACKWARD (the backward's kernels and workspace stop at 64 words)");
+        if (run_outside & CLIORA_FWD_PAIR_STATES)
+            return fail(CLIORA_EINVAL, "L > 64: CLIORA_FWD_PAIR_STATES is not supported (a long plan sizes no per-pair rows)");
+        if (compress) return fail(CLIORA_EINVAL, "L > 64: compress (root_mat) is not supported");
+        if (rg) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: L > 64 is not supported (the root-level mask holds 64 levels)");
+        if (g_cliora_resident == 1 && !vl && p.Dp <= 64)
+            return fail(CLIORA_EINVAL, "L > 64: the sentence-resident kernels are not supported (cliora_set_resident / CLIORA_RESIDENT forces them on)");
+    }
     hipStream_t st = (hipStream_t)stream;
     OKR(cliora_plan_ready(plan, st));
     std::lock_guard<std::mutex> lanes_lock(*plan->lanes_mu);
@@ -451,7 +472,8 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
         return sc;
     };
     auto launch_scores = [&](hipStream_t s, const ScoreArgs& sc) {
-        hipLaunchKernelGGL(level_scores, dim3(sc.nscore), dim3(256), 0, s, sc);
+        if (lng) hipLaunchKernelGGL(level_scores<true>, dim3(sc.nscore), dim3(256), 0, s, sc);
+        else hipLaunchKernelGGL(level_scores<false>, dim3(sc.nscore), dim3(256), 0, s, sc);
         LAUNCHOK("level_scores");
         return CLIORA_OK;
     };
@@ -489,11 +511,11 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
                 ScoreArgs sc = score_args(level + 1, false, level, 1);
                 sc.HPn = nullptr;                  // the newest cells are final rows of H already
                 OKR(launch_level_project(sa, 1, ws + f.wcat3, Dp, ldpi, ncell, g.Lc, C, g.off, IH, 0, 0, ws + f.bcat, ws + f.pi, ldpi,
-                                         (float*)nullptr, (float*)nullptr, sc));
+                                         (float*)nullptr, (float*)nullptr, sc, nullptr, lng));
             }
         } else if (level < L - 1) {      // norm + projection of this level, and the next level's scores in the same launch
             OKR(launch_level_project(sa, SP, ws + f.wcat3, Dp, ldpi, ncell, g.Lc, C, g.off, HPi, hp_stride, p.normalize, ws + f.bcat,
-                                     ws + f.pi, ldpi, IH, ws + f.nrmi, score_args(level + 1, false, level, SP), project_stop));
+                                     ws + f.pi, ldpi, IH, ws + f.nrmi, score_args(level + 1, false, level, SP), project_stop, lng));
         } else {
             hipLaunchKernelGGL(level_finish, dim3(cells_grid(ncell)), dim3(256), 0, sa, ncell, g.Lc, C, g.off, Dp, HPi, hp_stride, SP,
                                p.normalize, IH, ws + f.nrmi);
@@ -513,7 +535,7 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
         }
         if (level >= 1)      // the level below is scored in the same launch: its newest parents are this level's cells
             OKR(launch_level_project(sb, SP, ws + f.w1ro3, Dp, Dp, ncell, g.Lc, C, g.off, HPo, hp_stride, p.normalize, nullptr,
-                                     ws + f.po, Dp, OH, ws + f.nrmo, score_args(level - 1, true, level, SP)));
+                                     ws + f.po, Dp, OH, ws + f.nrmo, score_args(level - 1, true, level, SP), nullptr, lng));
         else {
             hipLaunchKernelGGL(level_finish, dim3(cells_grid(ncell)), dim3(256), 0, sb, ncell, g.Lc, C, g.off, Dp, HPo, hp_stride, SP,
                                p.normalize, OH, ws + f.nrmo);
@@ -625,7 +647,7 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
                                    ws + f.nrmi, ws + f.att_u, ws + f.att_nrmu, ws + f.att_pk, (float*)nullptr, D, IS);
                 LAUNCHOK("cell_attend_fwd");
             }
-            OKR(launch_level_project2(st, (ca.gx && !vl) ? ca.SP : 1, cb.gx ? cb.SP : 1, qa, qb));
+            OKR(launch_level_project2(st, (ca.gx && !vl) ? ca.SP : 1, cb.gx ? cb.SP : 1, qa, qb, lng));
         }
     }
     for (int k = 1; k <= L && !resident && !merged; ++k) {
@@ -697,6 +719,7 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     const Plan& p = plan->p;
     const bool vl = p.R > 0;
     if (p.arch != 0) return fail(CLIORA_EINVAL, "TreeLSTM plan: use cliora_lstm_backward");
+    if (p.is_long()) return fail(CLIORA_EINVAL, "cliora_chart_backward: L > 64 is forward only (cell_dsoftmax, the weight-gradient schedule and the workspace stop at 64 words)");
     if (vl && !obj_span) return fail(CLIORA_EINVAL, "a CLIORA plan (R > 0) needs obj_span");
     if (fwd_ws_bytes < p.fwd.total * sizeof(float)) return fail(CLIORA_ENOMEM, "forward workspace too small");
     if (bwd_ws_bytes < p.bwd.total * sizeof(float)) return fail(CLIORA_ENOMEM, "backward workspace too small");

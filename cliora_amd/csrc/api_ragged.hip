@@ -13,7 +13,13 @@ extern "C" int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_ws, const in
     HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
     Plan& p = plan->p;
     const size_t lds = (size_t)p.C * (sizeof(float) + sizeof(int32_t)) + (size_t)3 * (p.L + 1) * sizeof(int32_t);
-    hipLaunchKernelGGL(cky_ragged_kernel, dim3(p.B), dim3(RAGGED_CKY_WAVES * 64), lds, st, p.L, p.C, p.d_tables + p.dev.pair_a_in,
+    if (p.is_long()) {
+        if (lds > 64 * 1024) OKR(cliora_ensure_max_lds((const void*)cky_ragged_kernel<true>));
+        hipLaunchKernelGGL(cky_ragged_kernel<true>, dim3(p.B), dim3(RAGGED_CKY_WAVES * 64), lds, st, p.L, p.C, p.d_tables + p.dev.pair_a_in,
+                           p.d_tables + p.dev.pair_b_in, p.d_tables + p.dev.lvl_base_in, p.B, (const float*)fwd_ws + p.fwd.sp, lengths,
+                           split_out, spans_out, status);
+    } else
+    hipLaunchKernelGGL(cky_ragged_kernel<false>, dim3(p.B), dim3(RAGGED_CKY_WAVES * 64), lds, st, p.L, p.C, p.d_tables + p.dev.pair_a_in,
                        p.d_tables + p.dev.pair_b_in, p.d_tables + p.dev.lvl_base_in, p.B, (const float*)fwd_ws + p.fwd.sp, lengths,
                        split_out, p.L > 1 ? spans_out : (int32_t*)nullptr, status);
     LAUNCHOK("cky_ragged_kernel");
@@ -26,6 +32,7 @@ extern "C" int cliora_chart_forward_ragged(cliora_plan* plan, const cliora_param
                                            uint64_t root_levels, int32_t* status, void* stream) {
     if (!plan || !P || !lengths || !status) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: NULL argument");
     if (plan->p.arch != 0) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: TreeLSTM plans are not supported");
+    if (plan->p.is_long()) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: L > 64 is not supported (the root-level mask holds 64 levels)");
     if (!(run_outside & CLIORA_FWD_NO_BACKWARD))
         return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: inference only, pass CLIORA_FWD_NO_BACKWARD (a padded chart has no backward)");
     if (run_outside & CLIORA_FWD_PAIR_STATES) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: CLIORA_FWD_PAIR_STATES is not supported");

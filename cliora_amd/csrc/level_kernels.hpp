@@ -608,7 +608,12 @@ struct ScoreArgs {
 // cells of ALL of the wave's splits (lane j: split w + 4 j), the "plain" splits (both operands final: rows of QA / HB) run SCORE_KF at a
 // time with all their rows and chart scores in flight together, and the (at most two per cell) splits with an operand on the newest
 // level follow.  Same formula per split, so the same bits.
+//
+// LONG: a level of a long plan (plan.hpp: 64 < L <= 128), up to 127 splits.  The walk above already covers them (lane j of a wave holds
+// split w + 4 j); sh_s then holds 128 scores and the softmax tail takes two splits per lane (n = lane and lane + 64), max and sums over
+// both.  A cell with N <= 64 gets the bits of the short tail (the second split adds an exact 0).
 constexpr int SCORE_KF = 2;
+template <bool LONG = false>
 __device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh_s) {
     const LevelArgs& g = sc.g;
     const int lane = threadIdx.x & 63;
@@ -709,6 +714,19 @@ __device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh
     }
     __syncthreads();
     if (wave != 0) return;
+    if constexpr (LONG) {
+        const bool h0 = lane < g.N, h1 = lane + 64 < g.N;
+        const float s0 = h0 ? sh_s[lane] : -INFINITY, s1 = h1 ? sh_s[lane + 64] : -INFINITY;
+        const float m = wave_max(fmaxf(s0, s1));
+        const float e0 = h0 ? expf(s0 - m) : 0.f, e1 = h1 ? expf(s1 - m) : 0.f;
+        const float den = wave_sum(e0 + e1);
+        const float p0 = e0 / den, p1 = e1 / den;
+        if (h0) { sc.Sp[row0 + lane] = s0; sc.Pp[row0 + lane] = p0; }
+        if (h1) { sc.Sp[row0 + lane + 64] = s1; sc.Pp[row0 + lane + 64] = p1; }
+        const float st = wave_sum((h0 ? p0 * s0 : 0.f) + (h1 ? p1 * s1 : 0.f));
+        if (lane == 0) sc.Sout[(size_t)bC + g.off + p] = st;
+        return;
+    }
     const float my_s = lane < g.N ? sh_s[lane] : -INFINITY;
     const float m = wave_max(my_s);
     const float e = lane < g.N ? expf(my_s - m) : 0.f;
@@ -719,9 +737,10 @@ __device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh
 }
 
 // the scoring alone (first level of a pass: every operand is already final)
+template <bool LONG = false>
 static __global__ __launch_bounds__(256) void level_scores(ScoreArgs sc) {
-    __shared__ float sh_s[64];
-    score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), sh_s);
+    __shared__ float sh_s[LONG ? 128 : 64];
+    score_cell<LONG>(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), sh_s);
 }
 
 // one projection block (16 rows x CT*16 columns) of level_project: block `bid` of nrgp * ncolblocks
@@ -831,7 +850,7 @@ __device__ __forceinline__ void project_block(float4 (*part)[CT][64], float (*sh
     }
 }
 
-template <int CT, int SP>
+template <int CT, int SP, bool LONG = false>
 __global__ __launch_bounds__(256) void level_project(const float* __restrict__ Wfrag, int K, int nrg, int nrgp, int ncolblocks,
                                                      int ncell, int Lc, int C, int off, const float* __restrict__ HP, size_t hp_stride,
                                                      int normalize, const float* __restrict__ bias, float* __restrict__ P, int ldp,
@@ -840,7 +859,11 @@ __global__ __launch_bounds__(256) void level_project(const float* __restrict__ W
     __shared__ float sh_ss[4][16];
     (void)ncolblocks;
     if ((int)blockIdx.x < sc.nscore) {               // the next level's scores: first in the grid, so they start at once
-        score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), &sh_ss[0][0]);
+        if constexpr (LONG) {                        // 128 scores: `part` is idle in a score block
+            score_cell<true>(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), reinterpret_cast<float*>(&part[0][0][0]));
+        } else {
+            score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), &sh_ss[0][0]);
+        }
         return;
     }
     project_block<CT, SP>(part, sh_ss, (int)blockIdx.x - sc.nscore, Wfrag, K, nrg, nrgp, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm);
@@ -1028,7 +1051,7 @@ struct ProjSeg {
 // tile shape of level_project2's projection blocks (both segments): P2_RT row tiles x P2_CT column tiles, P2_PD chunks of the
 // reduction in flight per wave
 constexpr int P2_RT = 1, P2_CT = 1, P2_PD = 4;
-template <int SP0, int SP1>
+template <int SP0, int SP1, bool LONG = false>
 __global__ __launch_bounds__(256) void level_project2(ProjSeg a, ProjSeg b) {
     __shared__ float4 part[4][P2_RT * P2_CT][64];
     __shared__ float sh_ss[4][P2_RT * 16];
@@ -1037,9 +1060,11 @@ __global__ __launch_bounds__(256) void level_project2(ProjSeg a, ProjSeg b) {
         const int ns = a.sc.nscore + b.sc.nscore, np = a.nproj + b.nproj;
         if (bid < ns + np) bid = bid < np ? bid + ns : bid - np;
     }
-    if (bid < a.sc.nscore) { score_cell(a.sc, cell_of_block(bid, a.sc.g.B, a.sc.g.Lc), &sh_ss[0][0]); return; }
+    // (a long plan's 128 scores go into `part`, idle in a score block: no LDS beyond the short instance's)
+    float* sh_sc = LONG ? reinterpret_cast<float*>(&part[0][0][0]) : &sh_ss[0][0];
+    if (bid < a.sc.nscore) { score_cell<LONG>(a.sc, cell_of_block(bid, a.sc.g.B, a.sc.g.Lc), sh_sc); return; }
     bid -= a.sc.nscore;
-    if (bid < b.sc.nscore) { score_cell(b.sc, cell_of_block(bid, b.sc.g.B, b.sc.g.Lc), &sh_ss[0][0]); return; }
+    if (bid < b.sc.nscore) { score_cell<LONG>(b.sc, cell_of_block(bid, b.sc.g.B, b.sc.g.Lc), sh_sc); return; }
     bid -= b.sc.nscore;
     if (bid < a.nproj) {
         project_tile<P2_RT, P2_CT, SP0, P2_PD>(part, sh_ss, bid, a.Wfrag, a.K, a.nrg, a.nrgp, a.ntc,

@@ -52,10 +52,13 @@ int compose_cap_share(const Plan& p, int pass, int lv) {
     return cap;
 }
 
-std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, int R, int arch) {
+std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, int R, int arch, int max_L) {
     if (B < 1 || L < 1 || D < 1) return "B, L, D must be positive";
     if (D > 512) return "D > 512 is not supported by the weight-stationary kernels";
-    if (L > CLIORA_MAX_L) return "L > 64 is not supported (one split per lane in the score kernels)";
+    if (L > CLIORA_MAX_L_FWD) return "L > 128 is not supported (two splits per lane in the score kernels)";
+    if (L > max_L) return "L > 64 is not supported (one split per lane in the score kernels)";      // the caller takes no forward-only plan
+    const bool lng = L > CLIORA_MAX_L;       // a long plan: forward only (plan.hpp)
+    if (lng && arch != 0) return "L > 64 is not supported by TreeLSTM plans (one split per lane in their score kernel)";
     if (R < 0 || R > 64) return "R (image regions) must be in [0, 64]";
     if (normalize != 0 && normalize != 1) return "normalize must be 0 (none) or 1 (unit)";
     p.B = B; p.L = L; p.D = D; p.Dp = (D + 15) / 16 * 16; p.C = ncells(L);
@@ -76,6 +79,7 @@ std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, i
     p.R_in = (long long)B * p.P_in;
     p.R_out = (long long)B * p.P_out;
     if (p.R_in + p.R_out > 0x7fffffffLL / 2) return "batch too large for 32-bit pair rows";
+    if (lng && (long long)B * p.C * std::max(HP_PARTS, share ? 3 : 5) * p.Dp > 0x7fffffffLL) return "batch too large for 32-bit projection rows at L > 64";
     p.tile_base_in_.assign(L + 1, 0); p.tile_base_out_.assign(L + 1, 0);
     for (int lv = 0; lv < L; ++lv) {
         const long long g16 = ((long long)B * (L - lv) + 15) / 16;
@@ -96,6 +100,7 @@ std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, i
     std::vector<std::vector<std::vector<int32_t>>> tmp(N_ROLES, std::vector<std::vector<int32_t>>(C));
     // each use is pushed as three ints: row, stride, partner
     auto push_use = [&](int role, int c, long long row, int stride, int partner) {
+        if (lng) return;                       // the use lists serve the backward and the resident kernels only
         tmp[role][c].push_back((int32_t)row);
         tmp[role][c].push_back(stride);
         tmp[role][c].push_back(partner);
@@ -202,7 +207,7 @@ std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, i
         }
         f.hp = take(arch == 0 ? (size_t)HP_PARTS * BC * Dp : 0);
         f.hp_o = take(arch == 0 ? (size_t)HP_PARTS * BC * Dp : 0);
-        f.ymask = take(arch == 0 ? Rt * f.ncb3 * 4 : 0);
+        f.ymask = take(arch == 0 && !lng ? Rt * f.ncb3 * 4 : 0);       // (a long plan keeps no ReLU bits: nothing differentiates it)
         f.nrmi = take(BC);
         f.nrmo = take(BC);
         f.icp = take(lstm * BC * Dp); f.ocp = take(lstm * BC * Dp);
@@ -217,9 +222,10 @@ std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, i
         // per-pair compose outputs for the hooks: the TreeLSTM keeps them anyway (y rows), DioraMLP writes them into an
         // optional tail of the workspace only when a hook is overridden
         f.pair_h = arch == 0 ? o : f.y;
-        f.pair_h_floats = arch == 0 ? align64(Rt * Dp) : 0;
+        f.pair_h_floats = arch == 0 && !lng ? align64(Rt * Dp) : 0;    // (long plans serve no hooks: 13 GB of pair rows at B 8 / L 128 / D 400)
     }
-    {
+    p.bwd = BwdLayout{};
+    if (!lng) {
         BwdLayout& b = p.bwd;
         size_t o = 0;
         auto take = [&](size_t n) { size_t at = o; o = align64(o + n); return at; };

@@ -20,7 +20,9 @@ constexpr int ROLE_OUTA = 2;  // inside cell used as SIBLING in the outside pass
 constexpr int ROLE_OUTB = 3;  // outside cell used as PARENT in the outside pass
 constexpr int N_ROLES = 4;
 constexpr int HP_PARTS = 4;        // a cell's split range is cut into at most this many parts (level_compose_fwd tasks)
-constexpr int CLIORA_MAX_L = 64;   // sentence length bound: one split per lane in the score kernels
+constexpr int CLIORA_MAX_L = 64;   // sentence length bound of everything with a backward, TreeLSTM, compress and the resident kernels:
+                                   // one split per lane in the score / softmax-backward kernels
+constexpr int CLIORA_MAX_L_FWD = 128;   // forward-only DioraMLP / CLIORA plans ("long" plans): two splits per lane (score_cell<true>, the CKY kernels)
 constexpr int PLEVEL_INTS = 8;     // ints per entry of Plan::level_geom {Lc, N, level offset, pair-row base, pair-table base, TG, SP, ntask}
 
 struct UseList {
@@ -113,6 +115,7 @@ struct Plan {
     size_t d_tables_count = 0;
     struct DevOff { size_t pair_a_in, pair_b_in, pair_a_out, pair_b_out; size_t use_off[N_ROLES], use_row[N_ROLES], use_stride[N_ROLES], use_partner[N_ROLES]; size_t arow, brow, trow, lvl_base_in, lvl_base_out, level_geom; } dev;
 
+    bool is_long() const { return L > CLIORA_MAX_L; }      // forward only: no use lists, no backward layout, no ReLU bits
     int Lc(int level) const { return L - level; }
     int Nin(int level) const { return level; }
     int Nout(int level) const { return L - level - 1; }
@@ -133,8 +136,10 @@ struct ComposeGeom { int TG, SP, ntask; };
 ComposeGeom compose_geom(int ncell, int N, int cap);
 int compose_cap_share(const Plan& p, int pass, int lv);   // the cap a level's geometry is sized for: its share of Plan::compose_cap in its wavefront step
 
-// Builds every host table and the workspace layouts.  Returns "" or an error message.
-std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, int R, int arch = 0);
+// Builds every host table and the workspace layouts.  Returns "" or an error message.  max_L: the longest sentence the caller takes --
+// CLIORA_MAX_L (a plan with a backward), or CLIORA_MAX_L_FWD to accept a long, forward-only plan for 64 < L <= 128 as well
+// (cliora_plan_create does: its callers are told by cliora_plan_bwd_workspace_bytes = 0).
+std::string build_plan(Plan& p, int B, int L, int D, int share, int normalize, int R, int arch = 0, int max_L = CLIORA_MAX_L);
 
 // Flattens all int32 tables into one array (to upload once); fills p.dev offsets.
 std::vector<int32_t> flatten_tables(Plan& p);

@@ -20,6 +20,8 @@ constexpr int RAGGED_CKY_WAVES = 4;
 // by its cell ids; only the cells of the sentence's triangle are written and read.
 // split (B, C) or NULL: chosen split per cell, -1 at the leaves and outside the triangle.  spans (B, L-1, 2): the n - 1 constituents,
 // children before parents, the root last; (-1, -1) beyond.  A length outside [1, L]: every row -1, one count in *status, no chart read.
+// LONG: the padded chart of a long plan (64 < L <= 128): two splits per lane, as cky_kernel<true>.
+template <bool LONG = false>
 static __global__ __launch_bounds__(RAGGED_CKY_WAVES * 64) void cky_ragged_kernel(int L, int C, const int32_t* __restrict__ pair_a,
                                                                          const int32_t* __restrict__ pair_b,
                                                                          const int32_t* __restrict__ lvl_base, int B,
@@ -49,6 +51,17 @@ static __global__ __launch_bounds__(RAGGED_CKY_WAVES * 64) void cky_ragged_kerne
             float cand = -INFINITY;
             if (an) cand = (val[pair_a[loc + lane]] + val[pair_b[loc + lane]]) + (s - smax);
             float best = cand; int bi = an ? lane : 0x7fffffff;
+            if constexpr (LONG) {
+                const bool an1 = lane + 64 < N;
+                const float s1 = an1 ? Sp[row0 + lane + 64] : -INFINITY;
+                const float smax2 = wave_max(fmaxf(s, s1));
+                best = -INFINITY;
+                if (an) best = (val[pair_a[loc + lane]] + val[pair_b[loc + lane]]) + (s - smax2);
+                if (an1) {
+                    const float c1 = (val[pair_a[loc + lane + 64]] + val[pair_b[loc + lane + 64]]) + (s1 - smax2);
+                    if (c1 > best) { best = c1; bi = lane + 64; }
+                }
+            }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) {
                 const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);

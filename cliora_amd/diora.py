@@ -281,6 +281,22 @@ class DioraBase(nn.Module):
         self.__dict__.update(batch_size=None, length=None, chart=None, atten_score=None, all_atten_score=None, vg_atten_score=None,
                              _wss=None, _plan=None, _ragged_status=None)
 
+    def _check_long(self, L, needs_grad, hooks):
+        """64 < L <= 128 runs on a forward-only plan (include/cliora_chart.h): every refusal before any launch."""
+        if L <= _lib.MAX_L:
+            return
+        if needs_grad or self.training:
+            raise _lib.ChartLibError('L = %d > %d is inference only (the backward stops at %d words): call it in eval mode under '
+                                     'torch.no_grad()' % (L, _lib.MAX_L, _lib.MAX_L))
+        if hooks:
+            raise _lib.ChartLibError('L = %d > %d: inside_hook / outside_hook overrides get no per-pair states (a long plan sizes no '
+                                     'per-pair rows)' % (L, _lib.MAX_L))
+        if self.compress:
+            raise _lib.ChartLibError('L = %d > %d: compress = True is not supported' % (L, _lib.MAX_L))
+        if self.__dict__.get('_ragged') is not None:
+            raise _lib.ChartLibError('L > %d is not supported by the both-pass padded chart (its root-level mask holds %d levels): run '
+                                     'longer sentences through the uniform-length entry points' % (_lib.MAX_L, _lib.MAX_L))
+
     def _check_ragged(self, needs_grad, hooks):
         if needs_grad or self.training:
             raise _lib.ChartLibError('a padded chart of mixed lengths is inference only: call it in eval mode under torch.no_grad()')
@@ -320,13 +336,14 @@ class DioraBase(nn.Module):
         B, L, D = x_span.shape
         assert D == self.size
         dev_index = x_span.device.index if x_span.is_cuda else -1
-        plan = _lib.get_plan(B, L, D, self.share, self.normalize, 0, dev_index)
         holder = []
         # eval / torch.no_grad: nothing will ask for the backward, so the per-pair state is not written -- unless a hook
         # override wants the per-split tensors (analysis/utils.py:67-95)
         params = self._param_tensors()
         needs_grad = torch.is_grad_enabled() and (x_span.requires_grad or any(t is not None and t.requires_grad for t in params))
         hooks = self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook')
+        self._check_long(L, needs_grad, hooks)
+        plan = _lib.get_plan(B, L, D, self.share, self.normalize, 0, dev_index)
         flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
         ragged = self.__dict__.get('_ragged')
         if ragged is not None:

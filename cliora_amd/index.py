@@ -21,7 +21,7 @@ class Index(object):
 
     def _plan(self, length):
         if length not in self._plans:
-            self._plans[length] = _lib.Plan(1, length, 16)
+            self._plans[length] = _lib.Plan(1, length, 16, forward_only=length > _lib.MAX_L)   # tables only: a long plan has them all
         return self._plans[length]
 
     def _dev(self, a):

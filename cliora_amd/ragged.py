@@ -17,6 +17,7 @@ through.
 
     from cliora_amd.ragged import parse_ragged, encode_ragged, forward_ragged
     trees = parse_ragged(net, sentences)        # net: harness.Net; sentences: lists of token ids, any lengths 1..64
+    trees = parse_ragged(net, sentences, max_len=128)            # ... 1..128: the inside pass alone needs no root-level mask
     vecs = encode_ragged(net, sentences)        # (N, D) inside vectors of the sentences' roots, on the device
     trees = parse_ragged(vl_net, sentences, obj_feats=feats)     # a CLIORA net: region features (N, R, img_dim), one row per sentence
     forward_ragged(net, sentences, per_pack=lambda idx, lens, diora: ...)    # both passes; diora holds the pack's padded charts
@@ -28,7 +29,8 @@ import torch
 
 from . import _lib
 
-MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L
+MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L -- the both-pass padded chart (64 root levels in one mask word) and the default of max_len
+MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_len may be raised to for the inside-only entries (parse_ragged, encode_ragged)
 # Padded work a pack may carry beyond its sentences' own work, as a fraction of the latter.  Measured choice (tools/ragged_bench.py,
 # profiles/ragged_bench.json): the best of the sweep on 64 mixed sentences (5.3x the bucketed path), within
 # 2 % of the best on 1 000.
@@ -206,9 +208,10 @@ def _check_module(net, obj_feats):
     return False
 
 
-def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats=None, outside=False):
+def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats=None, outside=False, max_len=MAX_L):
     """pack -> per pack: pad, embed (and encode the regions), chart forward, `per_pack(indices, lengths_on_device)`.  outside False:
-    the inside pass alone through the module's ordinary forward; True: both passes through cliora_chart_forward_ragged."""
+    the inside pass alone through the module's ordinary forward; True: both passes through cliora_chart_forward_ragged.  max_len: the
+    longest sentence taken (64, or up to 128 for the inside pass alone); a longer one is refused before any pack has run."""
     diora = net.diora
     vl = _check_module(net, obj_feats)
     lengths = [len(s) for s in sentences]
@@ -219,8 +222,16 @@ def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats
     if vl and len(obj_feats) != len(sentences):
         raise ValueError('obj_feats holds %d sentences, not %d' % (len(obj_feats), len(sentences)))
     dev = next(net.parameters()).device
-    if max(lengths) > MAX_L:         # the plan's own refusal, before any pack has run
-        _lib.get_plan(1, max(lengths), diora.size, diora.share, diora.normalize, 0, dev.index if dev.type == 'cuda' else -1)
+    if not 1 <= int(max_len) <= (MAX_L if outside else MAX_L_INSIDE):
+        raise ValueError('max_len must be in 1..%d' % (MAX_L if outside else MAX_L_INSIDE))
+    if max(lengths) > max_len:       # before any pack has run
+        if outside:
+            raise _lib.ChartLibError('L > %d is not supported by the both-pass padded chart (its root-level mask holds %d levels; got a '
+                                     'sentence of %d words): run longer sentences through the uniform-length entry points'
+                                     % (MAX_L, MAX_L, max(lengths)))
+        raise _lib.ChartLibError('L > %d is not supported (got a sentence of %d words)%s' % (
+            max_len, max(lengths), ': pass max_len=%d for sentences of up to %d words' % (MAX_L_INSIDE, MAX_L_INSIDE)
+            if max_len < MAX_L_INSIDE and max(lengths) <= MAX_L_INSIDE else ''))
     was_training, had_outside = net.training, diora.outside
     net.eval()
     diora.outside = bool(outside)
@@ -264,9 +275,10 @@ def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, 
     return packs
 
 
-def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None):
+def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L):
     """Best binary tree of every sentence (nested tuples of word positions as ``DioraBase.cky()``; 0 for a single word), in the
-    caller's order.  net: a harness.Net; sentences: sequences of token ids of any lengths in 1..64; obj_feats: the region features
+    caller's order.  net: a harness.Net; sentences: sequences of token ids of any lengths in 1..max_len (64; up to 128 when asked for:
+    a pack whose longest sentence has more than 64 words runs on a forward-only plan); obj_feats: the region features
     (N, R, img_dim) of a CLIORA net, one row per sentence.  Runs in eval mode under no_grad with the outside pass off (both restored
     afterwards; the module's chart is left as the last pack's, outside_h unwritten).  One device-to-host copy per pack."""
     diora = net.diora
@@ -282,13 +294,13 @@ def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_
         for b, i in enumerate(idx):
             trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode, obj_feats=obj_feats)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode, obj_feats=obj_feats, max_len=max_len)
     return trees
 
 
-def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None):
+def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L):
     """(N, D) fp32 on the device: row i = inside_h of sentence i's root cell (its own length's root, not the padded chart's), the
-    vector DIORA users read off the root.  Same plumbing as parse_ragged."""
+    vector DIORA users read off the root.  Same plumbing as parse_ragged, max_len included."""
     diora = net.diora
     dev = next(net.parameters()).device
     out = torch.empty((len(sentences), diora.size), dtype=torch.float32, device=dev)
@@ -296,5 +308,5 @@ def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad
     def gather(idx, lens):
         out[torch.tensor(idx, dtype=torch.int64, device=dev)] = root_rows(diora, lens)
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, gather, obj_feats=obj_feats)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, gather, obj_feats=obj_feats, max_len=max_len)
     return out

@@ -79,7 +79,20 @@ typedef struct cliora_params {
  * every later call must run on that device.  Create and warm plans outside the
  * step loop, or cache them (the reference caches the same tables in Index,
  * cliora/net/utils.py:67-134; cliora_amd/_lib.py keeps an LRU of plans under
- * a byte budget). */
+ * a byte budget).
+ *
+ * Sentence length.  L <= 64 for everything that has a backward, for TreeLSTM plans, compress and the sentence-resident kernels (one
+ * split of a cell per lane in their score / softmax kernels).  A DioraMLP or CLIORA plan (arch 0; share 0 / 1, normalize unit / none)
+ * may also be created for 64 < L <= 128: a LONG plan, FORWARD ONLY.  It builds no use lists, sizes no backward workspace
+ * (cliora_plan_bwd_workspace_bytes = 0), no pair-state tail (cliora_plan_pair_states_bytes = 0) and no ReLU bits: 1 300.8 MiB of
+ * forward workspace at B 8 / L 128 / D 400 (text-only, shared weights), 8.1 MiB of device tables.  Its score + softmax and the CKY
+ * kernels take two splits per lane; the compose, projection and attention kernels are the ones every plan runs.  On a long plan,
+ * refused with CLIORA_EINVAL and a message that says why, before any launch:
+ *   cliora_chart_forward without CLIORA_FWD_NO_BACKWARD, with CLIORA_FWD_PAIR_STATES, or with params->root_mat (compress);
+ *   cliora_chart_forward while cliora_set_resident(1) / CLIORA_RESIDENT=1 forces the sentence-resident kernels on a plan they would
+ *   otherwise take (text-only, D <= 64); cliora_chart_backward; cliora_chart_forward_ragged (its root-level mask holds 64 levels);
+ *   cliora_plan_create_ex with arch = 1.  cliora_cky_decode, cliora_cky_spans, cliora_cky_spans_ragged, cliora_ground_eval(_ragged),
+ *   cliora_phrase_gather and the cliora_vl_scores_* forward entries take L <= 128.  L > 128 is refused at plan creation. */
 int cliora_plan_create(int B, int L, int D, int share, int normalize, int R, cliora_plan** out);
 /* arch: 0 = DioraMLP (as above), 1 = DioraTreeLSTM (text-only: R = 0) */
 int cliora_plan_create_ex(int B, int L, int D, int share, int normalize, int R, int arch, cliora_plan** out);
