@@ -1,4 +1,4 @@
-// Shared pieces of the C-ABI translation units (api_core / api_mlp / api_lstm / api_vl): the plan handle, error and
+// Shared pieces of the C-ABI translation units (api_core / api_mlp with api_mlp_launch.hpp / api_lstm / api_vl): the plan handle, error and
 // profiling plumbing, and the launch helpers of the MFMA kernels.  Header-only templates: each unit instantiates what it uses,
 // so the units compile in parallel.
 #pragma once
@@ -85,7 +85,7 @@ int cliora_ensure_max_lds(const void* fn);
 // uploads the plan's index tables on first use (current device) and checks that later calls run on that device
 int cliora_plan_ready(cliora_plan* plan, hipStream_t st);
 
-// cliora_chart_forward_ragged's extra arguments (api_ragged.hip), handed to the forward's body (api_mlp.hip)
+// cliora_chart_forward_ragged's extra arguments (api_ragged.hip), handed to the forward's body (api_mlp.hip: FwdSchedule::Ragged, forward_ragged)
 struct RaggedFwd { const int32_t* lengths; uint64_t root_levels; int32_t* status; };
 int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span, const float* drop_mask,
                              float* inside_h, float* inside_s, float* outside_h, float* outside_s, float* inside_c, void* fwd_ws,

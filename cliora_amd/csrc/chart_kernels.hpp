@@ -236,7 +236,7 @@ __device__ __forceinline__ void wg_sum_pairs(float4 (*sh)[GATHER_SLOTS][64], int
 // outside chain one step earlier (cell_gather_bwd_sib) -- half of an inside cell's uses leave the inside chain, the longer of the two.
 // Shared weights: rows of two scratch charts, added into the PL / QL blocks here; unshared: the kernel wrote blocks 3 / 4 of dPI itself.
 // with_outside: 0 no outside pass; 1 the sibling sums come from cell_gather_bwd_sib (sib_pl / sib_ql / sib_s); 2 this kernel walks the
-// sibling use list itself (the steps in which the OUTSIDE chain is the longer one: api_mlp.hip picks per step) and -- unshared weights --
+// sibling use list itself (the steps in which the OUTSIDE chain is the longer one: api_mlp.hip: BwdCall::sib_split picks per step) and -- unshared weights --
 // leaves its sums in sib_pl / sib_ql, which then are blocks 3 / 4 of dPI.
 static __global__ __launch_bounds__(256) void cell_gather_bwd_in(LevelArgs g, int D, const float* __restrict__ dH_ext, const float* __restrict__ dS_ext,
                                                           UseTab ina, UseTab inb, UseTab outa, int with_outside,

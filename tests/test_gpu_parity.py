@@ -529,7 +529,7 @@ def test_two_host_threads_make_their_first_call_on_one_cold_plan():
 @pytest.mark.parametrize('D,B,L', [(64, 3, 17), (96, 2, 20), (400, 1, 16), (33, 5, 18), (256, 2, 16), (400, 7, 23)])
 def test_early_weight_gradient_ranges(D, B, L, mfma_mode):
     """L >= 16 with shared weights: the pair rows' weight gradient is taken in three pieces -- the finished middle of the rows on the GEMM
-    stream after backward step (L-1)/2, the two end ranges in the tail (api_mlp.hip).  Every width class of the weight-gradient kernels,
+    stream after backward step (L-1)/2, the two end ranges in the tail (api_mlp.hip: pair_rows_early / pair_rows_tail).  Every width class of the weight-gradient kernels,
     odd batch sizes, and CLIORA_WGRAD_EARLY_STEP's default against the oracle; the pieces must add up to the reference's dW2 / db2."""
     from oracle import diora_ref as R
     from oracle import synth

@@ -1,5 +1,5 @@
 """The mid-chain weight-gradient pieces (the projections' part from level ksplit, the pair rows' early dW2 after step J) are taken only
-when the lane probe finds the weight-gradient stream concurrent with the chains (api_mlp.hip: sw_beside); with too few hardware queues
+when the lane probe finds the weight-gradient stream concurrent with the chains (api_mlp.hip: wgrad_placement, sw_beside); with too few hardware queues
 every weight gradient runs in the tail.  Whichever the default on this device, both placements must give the reference's gradients:
 the existing oracle checks run once more in a fresh process with the pieces forced on through their switches (read once per process)."""
 import os
