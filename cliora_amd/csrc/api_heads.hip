@@ -8,37 +8,18 @@ static inline size_t al64(size_t x) { return (x + 63) & ~size_t(63); }
 static inline int ceil16(int x) { return (x + 15) / 16 * 16; }
 
 // C[i][j] (+ colsum[i]) = sum_r A(r,i) B(r,j) for a rectangular C (Mi x Nj, both multiples of 16): tile counts per dimension
-template <int TI, int TJ, class AP, class BP>
-static int launch_tn_rect_t(hipStream_t st, int nrows, int Mi, int Nj, AP ap, BP bp, float* slab, size_t slab_floats, float* out, float* colsum_out) {
-    const int blocks = (Mi / (TI * 16)) * (Nj / (TJ * 16));
-    const size_t per_slice = (size_t)Mi * Nj + (colsum_out ? Mi : 0);
-    int nsl = (int)std::min<size_t>(slab_floats / per_slice, (size_t)std::max(4, 2048 / std::max(1, blocks)));
-    nsl = std::min(nsl, (nrows + 31) / 32);
-    nsl = std::max(4, nsl / 4 * 4);
-    if ((size_t)nsl * per_slice > slab_floats) return fail(CLIORA_ENOMEM, "workspace too small for the weight-gradient GEMM");
-    int rps = (nrows + nsl - 1) / nsl;
-    rps = (rps + 3) / 4 * 4;
-    float* csl = slab + (size_t)nsl * Mi * Nj;
-    if (colsum_out) hipLaunchKernelGGL((tn_gemm<TI, TJ, true, AP, BP>), dim3(blocks, nsl / 4), dim3(WS_THREADS), 0, st, nrows, rps, Mi, Nj, ap, bp, slab, csl);
-    else hipLaunchKernelGGL((tn_gemm<TI, TJ, false, AP, BP>), dim3(blocks, nsl / 4), dim3(WS_THREADS), 0, st, nrows, rps, Mi, Nj, ap, bp, slab, csl);
-    LAUNCHOK("tn_gemm(rect)");
-    const size_t n = (size_t)Mi * Nj;
-    launch_slab_reduce(st, slab, nsl, n, out, 0, csl, (size_t)Mi, colsum_out);
-    LAUNCHOK("slab_reduce");
-    return CLIORA_OK;
-}
 template <class AP, class BP>
 static int launch_tn_rect(hipStream_t st, int nrows, int Mi, int Nj, AP ap, BP bp, float* slab, size_t slab_floats, float* out, float* colsum_out) {
     const int ti = (Mi / 16) % 5 == 0 ? 5 : ((Mi / 16) % 4 == 0 ? 4 : 1);
     const int tj = (Nj / 16) % 4 == 0 ? 4 : 1;
-#define TNR(a, b) return launch_tn_rect_t<a, b>(st, nrows, Mi, Nj, ap, bp, slab, slab_floats, out, colsum_out)
-    if (ti == 5 && tj == 4) TNR(5, 4);
-    if (ti == 5) TNR(5, 1);
-    if (ti == 4 && tj == 4) TNR(4, 4);
-    if (ti == 4) TNR(4, 1);
-    if (tj == 4) TNR(1, 4);
-    TNR(1, 1);
-#undef TNR
+    return with_int<5, 4, 1>(ti, [&](auto TI) {
+        return with_int<4, 1>(tj, [&](auto TJ) {
+            return with_colsum(colsum_out != nullptr, [&](auto COLSUM) {
+                return launch_tn_slab<decltype(TI)::value, decltype(TJ)::value, decltype(COLSUM)::value>(
+                    st, nrows, Mi, Nj, ap, bp, slab, slab_floats, out, colsum_out, 0, TnSlabRule{32, 4, "workspace too small for the weight-gradient GEMM", "tn_gemm(rect)"});
+            });
+        });
+    });
 }
 // slab floats for a (Mi x Nj) product over nrows rows: at most 16 slices, at most 64 MB
 static size_t tn_rect_slab_floats(int nrows, int Mi, int Nj) {

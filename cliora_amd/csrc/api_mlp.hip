@@ -238,7 +238,7 @@ struct FwdCall {
             sg.gx = std::min(e[7], p.compose_cap);
             // workgroups are dealt round-robin over the 8 XCDs by linear id (x + y*gx): with gx a multiple of 8 the column blocks
             // that gather the same operand rows share one XCD's L2 (speed only, never correctness)
-            if (sg.gx >= 8 && (sg.gx + 7) / 8 * 8 <= p.compose_cap) sg.gx = (sg.gx + 7) / 8 * 8;
+            sg.gx = xcd_pad_within(sg.gx, p.compose_cap);
         }
         return sg;
     }
@@ -262,7 +262,7 @@ struct FwdCall {
             return q;
         }
         q.nrg = ((q.ncell + 15) / 16 + P2_RT - 1) / P2_RT;          // row groups of P2_RT sixteen-row tiles
-        q.nrgp = q.nrg >= 8 ? (q.nrg + 7) / 8 * 8 : q.nrg;
+        q.nrgp = xcd_pad(q.nrg);
         q.ntc = o.ncols / 16;
         q.nproj = q.nrgp * ((q.ntc + P2_CT - 1) / P2_CT);
         q.Wfrag = o.Wproj;
@@ -828,7 +828,7 @@ struct BwdCall {
         // shared weights: inside and outside pair rows are one contiguous range -> one launch
         const long long nr = (p.share && ran_outside) ? p.R_in + p.R_out : p.R_in;
         if (w.J_early >= 0) {          // the middle of the range is on its way on the GEMM stream (into gw2o / gb2o): the two ends here
-            if (tn_pairs_two_ranges_ok(Dp))          // both ends in one launch (round 4): one slab, one reduction
+            if (tn_pairs_strided_ok(Dp))         // both ends in one launch (round 4): one slab, one reduction
                 OKR(launch_tn_pairs_two_ranges(s_, DZ, Xp, (int)w.early_r0, w.early_r1, (int)(nr - w.early_r1), Dp, wb + bw.slab, bw.slab_floats,
                                                wb + bw.gw2i, wb + bw.gb2i, tail_slices2));
             else {

@@ -1,13 +1,8 @@
 // Launch helpers of the chart unit (api_mlp.hip, its only includer): the template dispatch of the fused level kernels
 // (level_kernels.hpp), each axis written once, and the geometry of their launches.
 #pragma once
-#include <type_traits>
-
 #include "api_common.hpp"
 #include "level_kernels.hpp"
-
-template <int V> using Int = std::integral_constant<int, V>;
-template <bool V> using Bool = std::integral_constant<bool, V>;
 
 // ------------------------------------------------------------------ one dispatcher per template axis
 // f(Int<NR>): the attention kernels keep a wave's regions in registers: 9 per wave cover R <= 36 (the reference's 36 boxes), 16 cover R <= 64
@@ -22,12 +17,7 @@ template <class F>
 static int with_compose_shape(int ct, int Dp, F&& f) {
     auto mode = [&](auto CT, auto K16) { return split_bf16() ? f(CT, K16, Bool<false>{}) : f(CT, K16, Bool<true>{}); };
     if (ct == 5 && Dp == 400) return mode(Int<5>{}, Int<25>{});
-    switch (ct) {
-        case 5: return mode(Int<5>{}, Int<0>{});
-        case 4: return mode(Int<4>{}, Int<0>{});
-        case 2: return mode(Int<2>{}, Int<0>{});
-        default: return mode(Int<1>{}, Int<0>{});
-    }
+    return with_int<5, 4, 2, 1>(ct, [&](auto CT) { return mode(CT, Int<0>{}); });
 }
 // the reduction's LDS row of the weight image: S3 dwords per column (split-bf16) or the K fp32 values (exact mode)
 static int compose_image_stride(int S3, int Dp) { return split_bf16() ? S3 : Dp; }
@@ -35,22 +25,13 @@ static int compose_image_stride(int S3, int Dp) { return split_bf16() ? S3 : Dp;
 // f(Int<SP>): the parts a level's aggregates come in (level_project sums 1 .. HP_PARTS of them)
 template <class F>
 static int with_parts(int SP, F&& f) {
-    switch (SP) {
-        case 1: return f(Int<1>{});
-        case 2: return f(Int<2>{});
-        case 3: return f(Int<3>{});
-        default: return f(Int<4>{});
-    }
+    return with_int<1, 2, 3, 4>(SP, f);
 }
 // ... and of the merged projection grid: what plan.cpp compose_geom deals (powers of two <= HP_PARTS)
 static bool project2_parts_ok(int SP) { return SP == 1 || SP == 2 || SP == 4; }
 template <class F>
 static int with_parts2(int SP, F&& f) {
-    switch (SP) {
-        case 1: return f(Int<1>{});
-        case 2: return f(Int<2>{});
-        default: return f(Int<4>{});
-    }
+    return with_int<1, 2, 4>(SP, f);
 }
 // f(Bool<LONG>): a long plan (plan.hpp), whose riding scores take two splits per lane (score_cell<true>)
 template <class F>
@@ -85,8 +66,7 @@ static int launch_level_compose2(hipStream_t st, const ComposeSeg& a, const Comp
                                  size_t hp_stride, uint32_t* ymask, float* Y) {
     if (a.gx + b.gx <= 0) return CLIORA_OK;
     const int S = compose_image_stride(S3, Dp);
-    int gx = a.gx + b.gx;
-    if (gx >= 8) gx = (gx + 7) / 8 * 8;            // padding blocks return at once; column blocks of one x share an XCD (linear id = x + y * gx)
+    const int gx = xcd_pad(a.gx + b.gx);           // padding blocks return at once; column blocks of one x share an XCD (linear id = x + y * gx)
     return with_compose_shape(ct, Dp, [&](auto CT, auto K16, auto F32) {
         constexpr int ct_ = decltype(CT)::value, k16 = decltype(K16)::value;
         constexpr bool f32 = decltype(F32)::value;
@@ -115,11 +95,7 @@ static int launch_level_compose_bwd(hipStream_t st, const float* WT, const float
         constexpr int ct_ = decltype(CT)::value, k16 = decltype(K16)::value;
         constexpr bool f32 = decltype(F32)::value, tiled_ = decltype(TILED)::value;
         OKR(cliora_ensure_max_lds((const void*)level_compose_bwd<ct_, k16, f32, tiled_>));
-        const int ntiles = (lv.ncell + 15) / 16 * lv.N;
-        const int cap = std::max(1, cus / ncb);
-        const int passes = (ntiles + 8 * cap - 1) / (8 * cap);
-        int gx = (ntiles + 8 * passes - 1) / (8 * passes);
-        if (gx >= 8 && (gx + 7) / 8 * 8 <= cap) gx = (gx + 7) / 8 * 8;      // column blocks of the same tiles on one XCD
+        const int gx = ws_grid((lv.ncell + 15) / 16 * lv.N, ncb, 8, cus);      // eight waves, a row tile each
         hipLaunchKernelGGL((level_compose_bwd<ct_, k16, f32, tiled_>), dim3(gx, ncb), dim3(512), compose_lds_bytes(ct_, S, false) + (size_t)((K + 31) / 32 * 32) * sizeof(float), st, I, S, K, lv, dG, ymask,
                            Pp, PA, lda, PB, ldb, b2, K, DA, DZ, X, DPP, DPB);
         LAUNCHOK("level_compose_bwd");
@@ -139,7 +115,7 @@ static int launch_level_compose_bwd(hipStream_t st, const float* WT, const float
 // kernel behind it started 6-7 us late at every level of the forward's inside chain (profiles/r04_notes.md).  nullptr: none.
 static int launch_level_project(hipStream_t st, int SP, const ProjSeg& q, hipEvent_t stop, bool lng) {
     const int nt = q.ntc, nrg = (q.ncell + 15) / 16;
-    const int nrgp = nrg >= 8 ? (nrg + 7) / 8 * 8 : nrg;          // column blocks of one row group share an XCD
+    const int nrgp = xcd_pad(nrg);          // column blocks of one row group share an XCD
     auto launch = [&](auto CT, auto SP_, auto LONG) {
         const int ncb = nt / decltype(CT)::value;
         LAUNCH_SIGNALLING(stop, (level_project<decltype(CT)::value, decltype(SP_)::value, decltype(LONG)::value>), dim3(q.sc.nscore + nrgp * ncb),

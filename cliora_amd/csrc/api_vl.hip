@@ -6,33 +6,15 @@
 extern "C" size_t cliora_plan_vl_workspace_bytes(const cliora_plan* plan) { return plan ? plan->p.vl.total * sizeof(float) : 0; }
 
 // C[i][j] = sum_r A(r,i) B(r,j) with different tile counts per side (register-only split-K kernel)
-template <int TI, int TJ, class AP, class BP>
-static int launch_tn_ij(hipStream_t st, int nrows, int Mi, int Nj, AP ap, BP bp, float* slab, size_t slab_floats, float* out) {
-    const int blocks = (Mi / (TI * 16)) * (Nj / (TJ * 16));
-    const size_t per_slice = (size_t)Mi * Nj;
-    int nsl = (int)std::min<size_t>(slab_floats / per_slice, (size_t)std::max(1, 2048 / blocks));
-    nsl = std::min(nsl, (nrows + 15) / 16);
-    nsl = std::max(4, nsl / 4 * 4);
-    if ((size_t)nsl * per_slice > slab_floats) return fail(CLIORA_ENOMEM, "slab too small for the region-gradient GEMM");
-    int rps = (nrows + nsl - 1) / nsl;
-    rps = (rps + 3) / 4 * 4;
-    hipLaunchKernelGGL((tn_gemm<TI, TJ, false, AP, BP>), dim3(blocks, nsl / 4), dim3(WS_THREADS), 0, st, nrows, rps, Mi, Nj, ap, bp, slab,
-                       (float*)nullptr);
-    LAUNCHOK("tn_gemm(ij)");
-    launch_slab_reduce(st, slab, nsl, per_slice, out, 0);
-    LAUNCHOK("slab_reduce");
-    return CLIORA_OK;
-}
 template <class AP, class BP>
 static int launch_tn_regions(hipStream_t st, int nrows, int Mi, int Nj, AP ap, BP bp, float* slab, size_t slab_floats, float* out) {
     const int ti = (Mi / 16) % 4 == 0 ? 4 : ((Mi / 16) % 2 == 0 ? 2 : 1);
-    const int tj = pick_tiles(Nj / 16);
-#define RG_CASE(a, b) if (ti == a && tj == b) return launch_tn_ij<a, b>(st, nrows, Mi, Nj, ap, bp, slab, slab_floats, out)
-    RG_CASE(4, 5); RG_CASE(4, 4); RG_CASE(4, 2); RG_CASE(4, 1);
-    RG_CASE(2, 5); RG_CASE(2, 4); RG_CASE(2, 2); RG_CASE(2, 1);
-    RG_CASE(1, 5); RG_CASE(1, 4); RG_CASE(1, 2); RG_CASE(1, 1);
-#undef RG_CASE
-    return fail(CLIORA_EINVAL, "unsupported region-gradient tile shape");
+    return with_int<4, 2, 1>(ti, [&](auto TI) {
+        return with_int<5, 4, 2, 1>(pick_tiles(Nj / 16), [&](auto TJ) {
+            return launch_tn_slab<decltype(TI)::value, decltype(TJ)::value, false>(st, nrows, Mi, Nj, ap, bp, slab, slab_floats, out, (float*)nullptr, 0,
+                                                                                 TnSlabRule{16, 1, "slab too small for the region-gradient GEMM", "tn_gemm(ij)"});
+        });
+    });
 }
 
 // reduction over the (padded) region axis: split it into LDS-sized segments
