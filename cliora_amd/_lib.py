@@ -152,6 +152,11 @@ def lib():
         L.cliora_ground_eval_ragged.argtypes = [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                                 vp]
         L.cliora_ground_eval_ragged.restype = i32
+    if hasattr(L, 'cliora_span_posteriors'):                    # (absent from older builds loaded through CLIORA_CHART_LIB)
+        L.cliora_span_posteriors_scratch_bytes.argtypes = [vp]
+        L.cliora_span_posteriors_scratch_bytes.restype = sz
+        L.cliora_span_posteriors.argtypes = [vp] * 10
+        L.cliora_span_posteriors.restype = i32
     L.cliora_prof_enable.argtypes = [i32, i32]
     L.cliora_prof_enable.restype = i32
     L.cliora_prof_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]

@@ -482,6 +482,24 @@ class DioraBase(nn.Module):
         Returns nested tuples of word positions, e.g. ``(0, ((1, 2), 3))`` -- a view of the device-built span lists (cky_spans)."""
         return self.trees_from_spans(self.cky_spans())
 
+    def span_posteriors(self, lengths=None, mbr=False):
+        """Span posteriors, log-partition and (mbr=True) the minimum-Bayes-risk tree of the last forward: the sum-product pass over
+        the potentials cky() maximises (cliora_amd.posterior.span_posteriors).  Device tensors."""
+        from . import posterior
+        return posterior.span_posteriors(self, lengths=lengths, mbr=mbr)
+
+    def mbr_spans_device(self, out=None):
+        """Spans of the MBR tree -- the tree with the most expected correct brackets under the span posteriors -- in the layout of
+        cky_spans_device: an int32 tensor (B, L-1, 2) on the chart's GPU, written into `out` when given."""
+        from . import posterior
+        return posterior.span_posteriors(self, mbr=True, out=out).spans
+
+    def mbr(self):
+        """MBR tree per sentence as nested tuples of word positions, as cky() returns the Viterbi tree."""
+        if self._plan.L < 2:
+            return [0] * (self._plan.B * len(self._wss))
+        return self.trees_from_spans(self.mbr_spans_device().cpu().numpy())
+
 
 class DioraMLP(DioraBase):
     def init_parameters(self):

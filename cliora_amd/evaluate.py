@@ -89,17 +89,22 @@ class GroundResult(object):
         self.word, self.box, self.hit, self.ccr = phr[:, 0], phr[:, 1], phr[:, 2], phr[:, 3]
 
 
-def ground_batch(diora, batch_map, spans=None):
+def ground_batch(diora, batch_map, spans=None, decode='viterbi'):
     """cliora_ground_eval for the batch the chart module last ran on: packs batch_map's VG_GT / GT into CSR tables, launches once
     on the current stream and copies every output back in one transfer.  `spans`: the (B, L-1, 2) int32 device spans of
     ``diora.cky_spans_device()``; None decodes them here, into the output buffer.  Text-only DIORA (``atten_score`` None): F1 counts
-    only, the phrases are not read (the reference skips them too)."""
+    only, the phrases are not read (the reference skips them too).  decode: which tree is decoded when `spans` is None -- 'viterbi'
+    (cky_spans_device) or 'mbr' (mbr_spans_device, cliora_amd.posterior)."""
+    if decode not in ('viterbi', 'mbr'):
+        raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
     plan = diora._plan
     B, L = plan.B * len(diora._wss), plan.L
     atten = getattr(diora, 'atten_score', None)
     tg = Targets(batch_map.get('VG_GT') if atten is not None else None, batch_map.get('GT'), B, L)
     boxes = batch_map['boxes'] if atten is not None else None
-    return ground(atten, boxes, tg, spans if spans is not None else diora.cky_spans_device, device=diora._wss[0].device)
+    if spans is None:
+        spans = diora.mbr_spans_device if decode == 'mbr' else diora.cky_spans_device
+    return ground(atten, boxes, tg, spans, device=diora._wss[0].device)
 
 
 def ground(atten, boxes, targets, spans, device=None, lengths=None, extra_status=()):
@@ -237,9 +242,10 @@ def batch_records(res, trees, sentences, example_ids, idx2word, with_boxes, post
     return lines
 
 
-def evaluate(net, batches, idx2word, out_path=None, postprocess=False):
+def evaluate(net, batches, idx2word, out_path=None, postprocess=False, decode='viterbi'):
     """parse.py:run (lines 101-291) on a harness.Net: eval mode, outside pass on, batches of length <= 2 skipped; returns the eight
-    numbers it prints (METRICS) and writes parse.jsonl to `out_path` when given."""
+    numbers it prints (METRICS) and writes parse.jsonl to `out_path` when given.  decode: 'viterbi' (the reference's tree) or 'mbr'
+    (the minimum-Bayes-risk tree of cliora_amd.posterior: F1, CCRA and the records are then those of that tree)."""
     diora = net.diora
     diora.outside = True
     net.eval()
@@ -255,7 +261,7 @@ def evaluate(net, batches, idx2word, out_path=None, postprocess=False):
                 obj = bm.get('obj_feats') if net.obj_feats else None
                 out = net(sentences.to(dev), obj.to(dev) if obj is not None else None, bm['neg_samples'].to(dev), compute_loss=True)
                 ev.add_losses(out)
-                res = ground_batch(diora, bm)
+                res = ground_batch(diora, bm, decode=decode)
                 ev.add(res)
                 if f is not None:
                     trees = diora.trees_from_spans(res.spans)
@@ -269,7 +275,7 @@ def evaluate(net, batches, idx2word, out_path=None, postprocess=False):
 
 
 def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, max_batch=64, max_waste=None, pad_id=0,
-                    return_details=False):
+                    return_details=False, decode='viterbi'):
     """``evaluate`` for examples of any lengths, given in any order: the sentences are packed into right-padded charts
     (cliora_amd.ragged), each pack costs one forward with the outside pass (cliora_chart_forward_ragged), one cliora_cky_spans_ragged,
     one cliora_ground_eval_ragged and one device-to-host copy, and the results come back in the caller's order.
@@ -280,8 +286,11 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
     ground_acc, ccra); parse.jsonl goes to `out_path` in the caller's order.  The four loss fields are left out: the reference defines
     the eval losses per uniform-length batch (the reconstruction loss reads every leaf of the batch and shares its negatives, the
     contrastive and VG losses compare the sentences of a batch with each other), and their ops take no per-sentence lengths.  return_details: also a list with, per
-    example, None (skipped) or a dict of spans (n-1, 2), sent (3,), hit / ccr / word / box per phrase and span_xyxy (n-1, 4)."""
+    example, None (skipped) or a dict of spans (n-1, 2), sent (3,), hit / ccr / word / box per phrase and span_xyxy (n-1, 4).
+    decode: 'viterbi' or 'mbr', as ``evaluate``."""
     from . import ragged
+    if decode not in ('viterbi', 'mbr'):
+        raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
     diora = net.diora
     keep = [i for i, ex in enumerate(examples) if len(ex['sentence']) > 2]
     sents = [list(examples[i]['sentence']) for i in keep]
@@ -299,11 +308,12 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
         boxes = torch.stack([torch.as_tensor(e['boxes'], dtype=torch.float32) for e in ex]) if vl else None
         cky_status = []
 
-        def decode(out):
-            cky_status.append(ragged.cky_spans_ragged(d, lens, out=out)[1])
+        def decode_into(out):
+            cky_status.append(ragged.decode_spans_ragged(d, lens, decode, out=out)[1])
 
-        res = ground(atten, boxes, tg, decode, device=d._wss[0].device, lengths=lens,
-                     extra_status=[('cliora_chart_forward_ragged', d._ragged_status), ('cliora_cky_spans_ragged', lambda: cky_status[0])])
+        entry = 'cliora_span_posteriors' if decode == 'mbr' else 'cliora_cky_spans_ragged'
+        res = ground(atten, boxes, tg, decode_into, device=d._wss[0].device, lengths=lens,
+                     extra_status=[('cliora_chart_forward_ragged', d._ragged_status), (entry, lambda: cky_status[0])])
         off = tg.phr_off
         for b, j in enumerate(idx):
             n = ns[b]

@@ -1,0 +1,188 @@
+"""Span posteriors, log-partition and minimum-Bayes-risk trees from the chart's per-split scores (cliora_span_posteriors).
+
+The CKY decode (``DioraBase.cky``) is max-product over the potentials r[cell, k] = s[cell, k] - max_k s[cell, .]; this is the
+sum-product pass over the same potentials (include/cliora_chart.h): how sure the parser is of a bracket
+(``marginals``), how peaked the distribution over trees is (``log_z``: 0 when one tree holds all the mass, log Catalan(n - 1) when
+every split of every cell ties), and the tree with the most expected correct brackets (``mbr=True``).  The reference has no
+counterpart; the distribution is the one whose mode its parser returns.
+
+    post = span_posteriors(net.diora)                    # after a forward; device tensors, nothing synchronised
+    table = marginal_table(post.marginals, L)            # (B, L, L): table[b, start, end]
+    trees = net.diora.mbr()                              # nested tuples, as net.diora.cky()
+
+``posterior_numpy`` (fp64, from the definitions) and ``mbr_numpy`` (fp32, the kernel's operation order) restate the kernel for
+tests, as ``ragged.decode_ragged_numpy`` restates the ragged decode.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _native():
+    lib = _lib.lib()
+    if not hasattr(lib, 'cliora_span_posteriors'):
+        raise _lib.ChartLibError('%s has no cliora_span_posteriors: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
+    return lib
+
+
+def cell_id(L, level, pos):
+    """Cell (level, pos) -- words [pos, pos + level] -- in the cell order of inside_s for a chart of length L."""
+    rem = L - level
+    return L * (L + 1) // 2 - rem * (rem + 1) // 2 + pos
+
+
+def cell_uses(n, level, pos):
+    """The n - 1 - level uses of cell (level, pos) in a sentence of n words, in the kernel's order, as closed forms:
+    -> [(parent level, parent pos, the parent's split, sibling level, sibling pos)]: first as a left child with the right sibling
+    (j, pos + level + 1), then as a right child with the left sibling (j, pos - j - 1)."""
+    uses = [(level + j + 1, pos, level, j, pos + level + 1) for j in range(n - 1 - pos - level)]
+    uses += [(level + j + 1, pos - j - 1, j, j, pos - j - 1) for j in range(pos)]
+    return uses
+
+
+class SpanPosteriors(object):
+    """marginals (B, C) fp32, log_z (B,) fp32, status (number of workspaces,) int32 -- lengths outside [1, L], which the caller of
+    a mixed-length run must check -- and, with mbr=True, spans (B, L-1, 2) / split (B, C) int32 of the MBR tree (else None).  Device
+    tensors; nothing is synchronised."""
+
+    def __init__(self, marginals, log_z, spans, split, status, L):
+        self.marginals, self.log_z, self.spans, self.split, self.status, self.L = marginals, log_z, spans, split, status, L
+
+    def table(self):
+        return marginal_table(self.marginals, self.L)
+
+
+def span_posteriors(diora, lengths=None, mbr=False, out=None):
+    """cliora_span_posteriors on a chart module after its forward.  lengths: None (every sentence has L words) or an int32 tensor
+    (B,) for a right-padded batch; mbr: also decode the MBR tree.  out: a contiguous int32 tensor (B, L-1, 2) on the chart's device
+    to decode the MBR spans into (cliora_amd.evaluate: its output buffer).  -> SpanPosteriors."""
+    lib = _native()
+    plan, wss = diora._plan, diora._wss
+    B, L, Cc = plan.B, plan.L, plan.C
+    nws = len(wss)
+    dev = wss[0].device
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
+        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
+    with torch.cuda.device(dev):
+        if lengths is not None:
+            lengths = lengths.to(dev).contiguous()
+        marg = torch.empty((B * nws, Cc), dtype=torch.float32, device=dev)
+        log_z = torch.empty(B * nws, dtype=torch.float32, device=dev)
+        status = torch.empty(nws, dtype=torch.int32, device=dev)
+        spans = split = None
+        if mbr:
+            if out is not None:
+                if out.shape != (B * nws, L - 1, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+                    raise ValueError('out must be a contiguous int32 tensor (%d, %d, 2) on %s' % (B * nws, L - 1, dev))
+                spans = out
+            else:
+                spans = torch.empty((B * nws, L - 1, 2), dtype=torch.int32, device=dev)
+            split = torch.empty((B * nws, Cc), dtype=torch.int32, device=dev)
+        need = lib.cliora_span_posteriors_scratch_bytes(plan.handle)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        for i, ws in enumerate(wss):
+            sl = slice(i * B, (i + 1) * B)
+            _lib.check(lib.cliora_span_posteriors(plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
+                                                  _p(marg[sl]), _p(log_z[sl]), _p(split[sl]) if mbr else None,
+                                                  _p(spans[sl]) if mbr else None, _p(scratch), C.c_void_p(status[i:i + 1].data_ptr()),
+                                                  _stream()), 'cliora_span_posteriors')
+    return SpanPosteriors(marg, log_z, spans, split, status, L)
+
+
+def marginal_table(marginals, L):
+    """(B, C) posteriors in cell order -> dense (B, L, L) indexed [start, end] (end inclusive, as the spans of cky_spans); 0 below
+    the diagonal.  A torch tensor stays on its device; a numpy array gives a numpy array."""
+    is_np = isinstance(marginals, np.ndarray)
+    m = torch.from_numpy(marginals) if is_np else marginals
+    start, end = torch.triu_indices(L, L, device=m.device)
+    level = end - start
+    rem = L - level
+    cell = L * (L + 1) // 2 - rem * (rem + 1) // 2 + start
+    table = torch.zeros((m.shape[0], L, L), dtype=m.dtype, device=m.device)
+    table[:, start, end] = m[:, cell]
+    return table.numpy() if is_np else table
+
+
+def _logsumexp(x):
+    m = x.max()
+    return m + np.log(np.exp(x - m).sum())
+
+
+def posterior_numpy(pair_s, lengths, L=None):
+    """The posteriors restated in fp64 from the definitions, for tests: `pair_s[level]` (B, L - level, level[, 1]) are the per-split
+    inside scores of the (padded) chart of length L (inferred from level 1 when not given), sentence b its first lengths[b] words.
+    -> (marginals (B, C) float64, 0 outside each triangle; log_z (B,) float64).  Tables indexed [level, pos]; the uses of a cell are
+    those of ``cell_uses``, taken a sibling level j at a time."""
+    lengths = [int(x) for x in lengths]
+    if L is None:
+        L = np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)
+    Cc = L * (L + 1) // 2
+    mu = np.zeros((len(lengths), Cc), dtype=np.float64)
+    log_z = np.zeros(len(lengths), dtype=np.float64)
+    for b, n in enumerate(lengths):
+        r = np.zeros((n, n, n), dtype=np.float64)                       # [level, pos, split]
+        for level in range(1, n):
+            s = np.asarray(pair_s[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
+            r[level, :n - level, :level] = s - s.max(axis=1, keepdims=True)
+        al = np.zeros((n, n), dtype=np.float64)
+        for level in range(1, n):
+            k = np.arange(level)
+            for pos in range(n - level):
+                al[level, pos] = _logsumexp(al[k, pos] + al[level - k - 1, pos + k + 1] + r[level, pos, :level])
+        be = np.zeros((n, n), dtype=np.float64)
+        for level in range(n - 2, -1, -1):
+            for pos in range(n - level):
+                j = np.arange(n - 1 - pos - level)                      # right siblings (j, pos + level + 1): the parent's split is `level`
+                right = be[level + j + 1, pos] + al[j, pos + level + 1 + 0 * j] + r[level + j + 1, pos, level]
+                j = np.arange(pos)                                      # left siblings (j, pos - j - 1): the parent's split is j
+                left = be[level + j + 1, pos - j - 1] + al[j, pos - j - 1] + r[level + j + 1, pos - j - 1, j]
+                be[level, pos] = _logsumexp(np.concatenate([right, left]))
+        log_z[b] = al[n - 1, 0] if n else 0.0
+        for level in range(n):
+            c0 = cell_id(L, level, 0)
+            mu[b, c0:c0 + n - level] = np.exp(al[level, :n - level] + be[level, :n - level] - log_z[b])
+    return mu, log_z
+
+
+def mbr_numpy(marginals, lengths, L):
+    """The MBR decode restated in fp32 in the kernel's operation order, for tests: v[leaf] = 0, v[cell] = max_k(v[left] + v[right])
+    + mu[cell], first maximum wins.  -> (per sentence the list of (start, end), children before parents; split (B, C) int32, -1 at
+    the leaves and outside each triangle)."""
+    marginals = np.asarray(marginals, dtype=np.float32)
+    split = np.full(marginals.shape, -1, dtype=np.int32)
+    out = []
+    for b, n in enumerate(int(x) for x in lengths):
+        val = {(0, p): np.float32(0.0) for p in range(n)}
+        bp = {}
+        for level in range(1, n):
+            for pos in range(n - level):
+                cand = np.array([val[(k, pos)] + val[(level - k - 1, pos + k + 1)] for k in range(level)], dtype=np.float32)
+                k = int(np.argmax(cand))
+                val[(level, pos)] = np.float32(cand[k] + marginals[b, cell_id(L, level, pos)])
+                bp[(level, pos)] = k
+                split[b, cell_id(L, level, pos)] = k
+        spans, stack = [], [(n - 1, 0, 0)] if n > 1 else []
+        while stack:                                  # the kernel's walk: left subtree, right subtree, then the node
+            level, pos, phase = stack.pop()
+            if level == 0:
+                continue
+            k = bp[(level, pos)]
+            if phase == 0:
+                stack += [(level, pos, 1), (k, pos, 0)]
+            elif phase == 1:
+                stack += [(level, pos, 2), (level - k - 1, pos + k + 1, 0)]
+            else:
+                spans.append((pos, pos + level))
+        out.append(spans)
+    return out, split

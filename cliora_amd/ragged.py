@@ -275,26 +275,41 @@ def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, 
     return packs
 
 
-def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L):
+def decode_spans_ragged(diora, lengths, decode='viterbi', out=None):
+    """The span decode of a padded chart by name: 'viterbi' (cliora_cky_spans_ragged) or 'mbr' (cliora_span_posteriors' MBR tree,
+    cliora_amd.posterior).  -> (spans, status, the entry's name for messages), spans decoded into `out` when given."""
+    if decode == 'viterbi':
+        return cky_spans_ragged(diora, lengths, out=out) + ('cliora_cky_spans_ragged',)
+    if decode == 'mbr':
+        from . import posterior
+        post = posterior.span_posteriors(diora, lengths, mbr=True, out=out)
+        return post.spans, post.status, 'cliora_span_posteriors'
+    raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
+
+
+def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L, decode='viterbi'):
     """Best binary tree of every sentence (nested tuples of word positions as ``DioraBase.cky()``; 0 for a single word), in the
     caller's order.  net: a harness.Net; sentences: sequences of token ids of any lengths in 1..max_len (64; up to 128 when asked for:
     a pack whose longest sentence has more than 64 words runs on a forward-only plan); obj_feats: the region features
     (N, R, img_dim) of a CLIORA net, one row per sentence.  Runs in eval mode under no_grad with the outside pass off (both restored
-    afterwards; the module's chart is left as the last pack's, outside_h unwritten).  One device-to-host copy per pack."""
+    afterwards; the module's chart is left as the last pack's, outside_h unwritten).  One device-to-host copy per pack.
+    decode: 'viterbi' (the reference's tree) or 'mbr' (the tree with the most expected correct brackets, cliora_amd.posterior)."""
     diora = net.diora
     trees = [None] * len(sentences)
+    if decode not in ('viterbi', 'mbr'):
+        raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
 
-    def decode(idx, lens):
-        spans, status = cky_spans_ragged(diora, lens)
+    def decode_pack(idx, lens):
+        spans, status, entry = decode_spans_ragged(diora, lens, decode)
         nsp = spans.numel()
         host = torch.cat([spans.reshape(-1), status]).cpu().numpy()         # the pack's one device-to-host copy
         if host[nsp:].any():
-            raise _lib.ChartLibError('cliora_cky_spans_ragged rejected %d sentence length(s)' % int(host[nsp:].sum()))
+            raise _lib.ChartLibError('%s rejected %d sentence length(s)' % (entry, int(host[nsp:].sum())))
         rows = host[:nsp].reshape(spans.shape)
         for b, i in enumerate(idx):
             trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode, obj_feats=obj_feats, max_len=max_len)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
     return trees
 
 

@@ -312,6 +312,31 @@ int cliora_cky_spans(cliora_plan* plan, void* fwd_workspace, int32_t* split_out,
  *   call zeroes first), which the caller must check.  With lengths[b] == L for every b the outputs are those of cliora_cky_spans. */
 int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, int32_t* split_out, int32_t* spans_out,
                             int32_t* status, void* stream);
+/* Span posteriors, log-partition and minimum-Bayes-risk (MBR) tree: the SUM-product pass over the potentials whose MAX-product is
+ * cliora_cky_spans.  Per cell, r[cell, k] = score[cell, k] - max_k score[cell, .] (the per-split inside scores of the last forward);
+ * a binary tree over the sentence weighs exp(sum of r over its internal cells and their splits).  Per sentence of n words:
+ *   inside   a[leaf] = 0,  a[cell] = logsumexp_k(a[left] + a[right] + r[cell, k]);      log_z = a[(n-1, 0)]
+ *   outside  b[(n-1, 0)] = 0,  b[cell] = logsumexp over the n-1-level (parent, sibling) uses of b[parent] + a[sibling] + r[parent, k]
+ *   mu[cell] = exp(a + b - log_z): the probability that the span is a constituent (1 at the leaves and at the sentence's root)
+ *   MBR      v[leaf] = 0,  v[cell] = max_k(v[left] + v[right]) + mu[cell] in fp32, first maximum wins: the tree with the most
+ *            expected correct brackets.
+ * The reference has no counterpart; the distribution is the one whose mode its parser returns.  One workgroup per sentence, gather
+ * form, a and b in fp64, fixed-order reductions, no floating-point atomics: two calls give equal bits.
+ *   lengths (B) int32 device, or NULL: every sentence has L words.  Otherwise the sentences share a right-padded chart, with the
+ *     rules of cliora_cky_spans_ragged: `status` (an int32 on the device, zeroed by the call) is required and counts the lengths
+ *     outside [1, L]; such a sentence gets mu = 0, log_z = 0, every MBR row -1, and none of its scores is read.  With every length
+ *     equal to L the outputs are bitwise those of the lengths == NULL call.  status may be NULL when lengths is.
+ *   marginals (B, C) fp32: mu in the cell order of inside_s, exactly 0 outside a sentence's triangle.  log_z (B) fp32.
+ *   mbr_split (B, C) or NULL: the MBR split per cell, -1 at the leaves and outside the triangle.  mbr_spans (B, L-1, 2) or NULL: the
+ *     n - 1 spans of the MBR tree in cliora_cky_spans' order, the root last, (-1, -1) beyond.  Both NULL: the MBR pass is skipped.
+ *   scratch: device memory of cliora_span_posteriors_scratch_bytes(plan) bytes; NULL when that is 0 (as it is for every plan today:
+ *     the tables fit the LDS up to L = 128, 131 KiB there).
+ * Every plan cliora_cky_spans takes is taken: long plans (two splits / uses per lane) and TreeLSTM plans (the same score rows).
+ * Refused with CLIORA_EINVAL and a message, before any launch: a NULL plan, workspace, marginals or log_z; lengths without status; a
+ * plan that has not run a forward. */
+size_t cliora_span_posteriors_scratch_bytes(const cliora_plan* plan);
+int cliora_span_posteriors(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, float* marginals, float* log_z,
+                           int32_t* mbr_split, int32_t* mbr_spans, void* scratch, int32_t* status, void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
