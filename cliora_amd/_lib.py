@@ -6,8 +6,9 @@ fails, this raises.  Build it with ``python -m cliora_amd.build`` (or
 """
 import collections
 import ctypes as C
-import functools
 import os
+
+import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CLIORA_CHART_LIB') or os.path.join(HERE, 'libcliora_chart.so')   # override: kernel experiments only
@@ -32,7 +33,74 @@ class ChartLibError(RuntimeError):
     pass
 
 
+vp, i32, i64, u64, sz, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float
+pp, pvp, psz = C.POINTER(Params), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+
+# The C ABI of include/cliora_chart.h as data: symbol -> (result type, argument types).  lib() applies it to every symbol the loaded
+# library has; fn() refuses an absent one.  tests/test_abi_table.py holds the arities against the header's prototypes.
+ABI = {
+    'cliora_plan_create': (i32, [i32] * 6 + [pvp]),
+    'cliora_plan_create_ex': (i32, [i32] * 7 + [pvp]),
+    'cliora_plan_destroy': (None, [vp]),
+    'cliora_plan_fwd_workspace_bytes': (sz, [vp]),
+    'cliora_plan_bwd_workspace_bytes': (sz, [vp]),
+    'cliora_plan_pair_states_bytes': (sz, [vp]),
+    'cliora_plan_device_bytes': (sz, [vp]),
+    'cliora_plan_fwd_offset': (sz, [vp, C.c_char_p]),
+    'cliora_plan_table': (i32, [vp, C.c_char_p, C.POINTER(C.POINTER(C.c_int32)), psz]),
+    'cliora_chart_forward': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp]),
+    'cliora_chart_backward': (i32, [vp, pp] + [vp] * 11 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
+    'cliora_chart_forward_ragged': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
+    'cliora_lstm_forward': (i32, [vp, pp] + [vp] * 7 + [vp, sz, i32, vp]),
+    'cliora_lstm_backward': (i32, [vp, pp] + [vp] * 13 + [vp, sz, vp, sz, vp, pp, i32, vp]),
+    'cliora_inside_pair_states': (i32, [vp, vp, i32, pvp, pvp, psz, psz]),
+    'cliora_outside_pair_states': (i32, [vp, vp, i32, pvp, pvp, psz, psz]),
+    'cliora_plan_vl_workspace_bytes': (sz, [vp]),
+    'cliora_vl_scores_forward': (i32, [vp] * 6 + [i32, vp, vp, vp, sz, vp]),
+    'cliora_vl_scores_backward': (i32, [vp] * 6 + [i32] + [vp] * 6 + [vp, sz, vp]),
+    'cliora_vl_scores_max_forward': (i32, [vp] * 4 + [vp, vp, vp, sz, vp]),
+    'cliora_vl_scores_max_backward': (i32, [vp] * 4 + [vp, vp, vp, vp, vp, sz, vp]),
+    'cliora_contrastive_workspace_bytes': (sz, [i32, i32]),
+    'cliora_contrastive_loss': (i32, [i32, i32, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, sz, vp]),
+    'cliora_proj_workspace_bytes': (sz, [i32, i32, i32]),
+    'cliora_proj_forward': (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
+    'cliora_proj_backward': (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    'cliora_recon_workspace_bytes': (sz, [i32, i32, i32, i32]),
+    'cliora_recon_forward': (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, sz, vp]),
+    'cliora_recon_backward': (i32, [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'cliora_rows_scatter_add': (i32, [vp, vp, i32, i32, vp, i64, vp]),
+    'cliora_rows_scatter_add_segments': (i32, [pvp, pvp, C.POINTER(i32), i32, i32, vp, i64, vp]),
+    'cliora_vg_workspace_bytes': (sz, [i32, i32]),
+    'cliora_vg_loss': (i32, [i32, i32, i32, vp, f32, vp, vp, vp, sz, vp]),
+    'cliora_clip_adam_workspace_bytes': (sz, []),
+    'cliora_clip_adam': (i32, [vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, i32, vp, sz, vp]),
+    'cliora_cky_decode': (i32, [vp, vp, vp, vp]),
+    'cliora_cky_spans': (i32, [vp, vp, vp, vp, vp]),
+    'cliora_cky_spans_ragged': (i32, [vp] * 7),
+    'cliora_span_posteriors_scratch_bytes': (sz, [vp]),
+    'cliora_span_posteriors': (i32, [vp] * 10),
+    'cliora_ground_eval': (i32, [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
+    'cliora_ground_eval_ragged': (i32, [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
+    'cliora_phrase_gather': (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp, i64, i64, vp, vp]),
+    'cliora_knn_ip_workspace_bytes': (sz, [i32, i32, i32, i32]),
+    'cliora_knn_ip': (i32, [i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, sz, vp]),
+    'cliora_knn_filter': (i32, [i32, i32, vp, i64, vp, i64, vp, vp, i32, i32, vp, vp, vp, vp]),
+    'cliora_token_counts': (i32, [i64, vp, i32, vp, vp, vp]),
+    'cliora_neg_sample_workspace_bytes': (sz, [i32, i32, i32]),
+    'cliora_neg_sample': (i32, [i32, vp, i32, i32, i32, u64, u64, C.c_uint32, vp, vp, vp, sz, vp]),
+    'cliora_prof_enable': (i32, [i32, i32]),
+    'cliora_prof_read': (i32, [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]),
+    'cliora_last_error': (C.c_char_p, []),
+    'cliora_version': (C.c_char_p, []),
+    'cliora_set_mfma_mode': (i32, [i32]),
+    'cliora_set_wavefront': (i32, [i32]),
+    'cliora_set_resident': (i32, [i32]),
+    'cliora_device_side_stream': (i32, [vp, pvp]),
+    'cliora_resident_trace': (i32, [vp, vp, sz, vp]),
+}
+
 _lib = None
+_bound = {}      # symbol -> bound function of the loaded library, resolved once (fn)
 
 
 def lib():
@@ -42,141 +110,78 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise ChartLibError('HIP extension %s is missing: run `python -m cliora_amd.build` '
                             '(there is no CPU fallback for the chart path)' % LIB_PATH)
-    # torch first: its bundled HIP runtime must be the one already loaded when our library is dlopen'ed, otherwise the
-    # process ends up with two runtimes and ours sees no device ("no ROCm-capable device is detected" at the first hipMalloc)
-    import torch  # noqa: F401
+    # torch is imported first (above): its bundled HIP runtime must be the one already loaded when our library is dlopen'ed, otherwise
+    # the process ends up with two runtimes and ours sees no device ("no ROCm-capable device is detected" at the first hipMalloc)
     L = C.CDLL(LIB_PATH)
-    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
-    L.cliora_plan_create.argtypes = [i32] * 6 + [C.POINTER(vp)]
-    L.cliora_plan_create.restype = i32
-    L.cliora_plan_create_ex.argtypes = [i32] * 7 + [C.POINTER(vp)]
-    L.cliora_plan_create_ex.restype = i32
-    L.cliora_lstm_forward.argtypes = [vp, C.POINTER(Params)] + [vp] * 7 + [vp, sz, i32, vp]
-    L.cliora_lstm_forward.restype = i32
-    L.cliora_lstm_backward.argtypes = [vp, C.POINTER(Params)] + [vp] * 13 + [vp, sz, vp, sz, vp, C.POINTER(Params), i32, vp]
-    L.cliora_lstm_backward.restype = i32
-    L.cliora_plan_destroy.argtypes = [vp]
-    L.cliora_plan_destroy.restype = None
-    L.cliora_plan_fwd_workspace_bytes.argtypes = [vp]
-    L.cliora_plan_fwd_workspace_bytes.restype = sz
-    L.cliora_plan_bwd_workspace_bytes.argtypes = [vp]
-    L.cliora_plan_bwd_workspace_bytes.restype = sz
-    L.cliora_plan_pair_states_bytes.argtypes = [vp]
-    L.cliora_plan_pair_states_bytes.restype = sz
-    L.cliora_plan_device_bytes.argtypes = [vp]
-    L.cliora_plan_device_bytes.restype = sz
-    L.cliora_plan_fwd_offset.argtypes = [vp, C.c_char_p]
-    L.cliora_plan_fwd_offset.restype = sz
-    L.cliora_plan_table.argtypes = [vp, C.c_char_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(sz)]
-    L.cliora_plan_table.restype = i32
-    L.cliora_chart_forward.argtypes = [vp, C.POINTER(Params)] + [vp] * 8 + [vp, sz, i32, vp]
-    L.cliora_chart_forward.restype = i32
-    L.cliora_chart_backward.argtypes = [vp, C.POINTER(Params)] + [vp] * 11 + [vp, sz, vp, sz, vp, vp, C.POINTER(Params), i32, vp]
-    L.cliora_chart_backward.restype = i32
-    L.cliora_inside_pair_states.argtypes = [vp, vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
-    L.cliora_inside_pair_states.restype = i32
-    L.cliora_outside_pair_states.argtypes = [vp, vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
-    L.cliora_outside_pair_states.restype = i32
-    L.cliora_plan_vl_workspace_bytes.argtypes = [vp]
-    L.cliora_plan_vl_workspace_bytes.restype = sz
-    L.cliora_vl_scores_forward.argtypes = [vp] + [vp] * 5 + [i32, vp, vp, vp, sz, vp]
-    L.cliora_vl_scores_forward.restype = i32
-    L.cliora_vl_scores_backward.argtypes = [vp] + [vp] * 5 + [i32] + [vp] * 6 + [vp, sz, vp]
-    L.cliora_vl_scores_backward.restype = i32
-    L.cliora_vl_scores_max_forward.argtypes = [vp] + [vp] * 3 + [vp, vp, vp, sz, vp]
-    L.cliora_vl_scores_max_forward.restype = i32
-    L.cliora_vl_scores_max_backward.argtypes = [vp] + [vp] * 3 + [vp, vp, vp, vp, vp, sz, vp]
-    L.cliora_vl_scores_max_backward.restype = i32
-    L.cliora_contrastive_workspace_bytes.argtypes = [i32, i32]
-    L.cliora_contrastive_workspace_bytes.restype = sz
-    L.cliora_contrastive_loss.argtypes = [i32, i32, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, sz, vp]
-    L.cliora_contrastive_loss.restype = i32
-    L.cliora_proj_workspace_bytes.argtypes = [i32, i32, i32]
-    L.cliora_proj_workspace_bytes.restype = sz
-    L.cliora_proj_forward.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]
-    L.cliora_proj_forward.restype = i32
-    L.cliora_proj_backward.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]
-    L.cliora_proj_backward.restype = i32
-    L.cliora_recon_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    L.cliora_recon_workspace_bytes.restype = sz
-    L.cliora_recon_forward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, sz, vp]
-    L.cliora_recon_forward.restype = i32
-    L.cliora_recon_backward.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.cliora_recon_backward.restype = i32
-    L.cliora_rows_scatter_add.argtypes = [vp, vp, i32, i32, vp, C.c_int64, vp]     # mandatory: heads.scatter_rows has no other path
-    L.cliora_rows_scatter_add.restype = i32
-    if hasattr(L, 'cliora_rows_scatter_add_segments'):          # (absent from older builds loaded through CLIORA_CHART_LIB for A/B runs)
-        L.cliora_rows_scatter_add_segments.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32, i32, vp, C.c_int64, vp]
-        L.cliora_rows_scatter_add_segments.restype = i32
-    L.cliora_vg_workspace_bytes.argtypes = [i32, i32]
-    L.cliora_vg_workspace_bytes.restype = sz
-    L.cliora_vg_loss.argtypes = [i32, i32, i32, vp, C.c_float, vp, vp, vp, sz, vp]
-    L.cliora_vg_loss.restype = i32
-    L.cliora_clip_adam_workspace_bytes.argtypes = []
-    L.cliora_clip_adam_workspace_bytes.restype = sz
-    L.cliora_clip_adam.argtypes = [vp, vp, vp, vp, sz, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, i32, vp, sz, vp]
-    L.cliora_clip_adam.restype = i32
-    L.cliora_cky_decode.argtypes = [vp, vp, vp, vp]
-    L.cliora_cky_decode.restype = i32
-    L.cliora_cky_spans.argtypes = [vp, vp, vp, vp, vp]
-    L.cliora_cky_spans.restype = i32
-    if hasattr(L, 'cliora_ground_eval'):                        # (absent from older builds loaded through CLIORA_CHART_LIB)
-        i64 = C.c_int64
-        L.cliora_ground_eval.argtypes = [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.cliora_ground_eval.restype = i32
-    if hasattr(L, 'cliora_knn_ip'):                             # (absent from older builds loaded through CLIORA_CHART_LIB)
-        i64 = C.c_int64
-        L.cliora_phrase_gather.argtypes = [i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp, i64, i64, vp, vp]
-        L.cliora_phrase_gather.restype = i32
-        L.cliora_knn_ip_workspace_bytes.argtypes = [i32, i32, i32, i32]
-        L.cliora_knn_ip_workspace_bytes.restype = sz
-        L.cliora_knn_ip.argtypes = [i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, sz, vp]
-        L.cliora_knn_ip.restype = i32
-        L.cliora_knn_filter.argtypes = [i32, i32, vp, i64, vp, i64, vp, vp, i32, i32, vp, vp, vp, vp]
-        L.cliora_knn_filter.restype = i32
-    if hasattr(L, 'cliora_neg_sample'):                         # (absent from older builds loaded through CLIORA_CHART_LIB)
-        i64, u64 = C.c_int64, C.c_uint64
-        L.cliora_token_counts.argtypes = [i64, vp, i32, vp, vp, vp]
-        L.cliora_token_counts.restype = i32
-        L.cliora_neg_sample_workspace_bytes.argtypes = [i32, i32, i32]
-        L.cliora_neg_sample_workspace_bytes.restype = sz
-        L.cliora_neg_sample.argtypes = [i32, vp, i32, i32, i32, u64, u64, C.c_uint32, vp, vp, vp, sz, vp]
-        L.cliora_neg_sample.restype = i32
-    if hasattr(L, 'cliora_cky_spans_ragged'):                   # (absent from older builds loaded through CLIORA_CHART_LIB)
-        L.cliora_cky_spans_ragged.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.cliora_cky_spans_ragged.restype = i32
-    if hasattr(L, 'cliora_chart_forward_ragged'):               # (absent from older builds loaded through CLIORA_CHART_LIB)
-        i64 = C.c_int64
-        L.cliora_chart_forward_ragged.argtypes = [vp, C.POINTER(Params)] + [vp] * 8 + [vp, sz, i32, vp, C.c_uint64, vp, vp]
-        L.cliora_chart_forward_ragged.restype = i32
-        L.cliora_ground_eval_ragged.argtypes = [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
-                                                vp]
-        L.cliora_ground_eval_ragged.restype = i32
-    if hasattr(L, 'cliora_span_posteriors'):                    # (absent from older builds loaded through CLIORA_CHART_LIB)
-        L.cliora_span_posteriors_scratch_bytes.argtypes = [vp]
-        L.cliora_span_posteriors_scratch_bytes.restype = sz
-        L.cliora_span_posteriors.argtypes = [vp] * 10
-        L.cliora_span_posteriors.restype = i32
-    L.cliora_prof_enable.argtypes = [i32, i32]
-    L.cliora_prof_enable.restype = i32
-    L.cliora_prof_read.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(C.c_longlong), vp]
-    L.cliora_prof_read.restype = i32
-    L.cliora_last_error.restype = C.c_char_p
-    L.cliora_version.restype = C.c_char_p
-    L.cliora_set_mfma_mode.argtypes = [i32]
-    L.cliora_set_mfma_mode.restype = i32
-    L.cliora_set_wavefront.argtypes = [i32]
-    L.cliora_set_wavefront.restype = i32
-    L.cliora_set_resident.argtypes = [i32]
-    L.cliora_set_resident.restype = i32
-    if hasattr(L, 'cliora_device_side_stream'):
-        L.cliora_device_side_stream.argtypes = [vp, C.POINTER(vp)]
-        L.cliora_device_side_stream.restype = i32
-    if hasattr(L, 'cliora_resident_trace'):
-        L.cliora_resident_trace.argtypes = [vp, vp, sz, vp]
-        L.cliora_resident_trace.restype = i32
+    for name, (restype, argtypes) in ABI.items():      # a symbol this library lacks (an older build through CLIORA_CHART_LIB): fn() refuses it
+        f = getattr(L, name, None)
+        if f is not None:
+            f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
+
+
+def fn(name, L=None):
+    """The bound function of the C-ABI symbol `name` (of the library object L when given, for tests): the one place that refuses a
+    symbol the loaded library does not have.  The size queries and getters are called through it directly, the status-returning
+    entry points through call()."""
+    f = _bound.get(name) if L is None else None
+    if f is None:
+        f = getattr(lib() if L is None else L, name, None)
+        if f is None:
+            raise ChartLibError('%s has no %s: rebuild it (python -m cliora_amd.build)' % (LIB_PATH, name))
+        if L is None:
+            _bound[name] = f
+    return f
+
+
+def call(name, *args):
+    """Run a status-returning entry point; a non-zero status raises with the library's message (check)."""
+    rc = (_bound.get(name) or fn(name))(*args)
+    if rc:
+        check(rc, name)
+
+
+def check(rc, what):
+    if rc != 0:
+        raise ChartLibError('%s failed (%d): %s' % (what, rc, fn('cliora_last_error')().decode()))
+
+
+def ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def ptr_or_null(t):
+    """ptr() that also gives NULL for a tensor without elements (an empty slice still has an address)."""
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+
+
+def stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def param_struct(tensors):
+    return Params(*[(t.data_ptr() if t is not None else None) for t in map(tensors.get, PARAM_FIELDS)])
+
+
+class device_guard(object):
+    """`with device_guard(t)`: run under the device of the tensor `t`, so that the plan's index tables, the kernels' per-device attributes
+    and every allocation land on the tensors' GPU even when it is not the current one.  Nothing to do for None, for a CPU tensor and
+    for the device that is current already: `torch.cuda.device` costs ~10 us of host time per use, and a configs[0]-sized step is
+    bound by the host (tools/host_bench.py).  Around the body of an autograd forward / backward as around any other block."""
+    __slots__ = ('ctx',)
+
+    def __init__(self, t):
+        index = t.device.index if t is not None else None
+        self.ctx = None if index is None or index == torch.cuda.current_device() else torch.cuda.device(index)
+
+    def __enter__(self):
+        if self.ctx is not None:
+            self.ctx.__enter__()
+
+    def __exit__(self, *a):
+        if self.ctx is not None:
+            return self.ctx.__exit__(*a)
 
 
 _side_streams = {}
@@ -185,21 +190,15 @@ _side_streams = {}
 def side_stream(device):
     """torch handle of the library's caller lane on `device` (include/cliora_chart.h: cliora_device_side_stream): a stream that runs beside
     the current stream and the chart's own side streams.  One per device, created at the first request."""
-    import torch
     idx = device.index if device.index is not None else torch.cuda.current_device()
     s = _side_streams.get(idx)
     if s is None:
         out = C.c_void_p()
         with torch.cuda.device(idx):
-            check(lib().cliora_device_side_stream(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(out)), 'cliora_device_side_stream')
+            call('cliora_device_side_stream', stream(), C.byref(out))
         s = torch.cuda.ExternalStream(out.value, device=torch.device('cuda', idx))
         _side_streams[idx] = s
     return s
-
-
-def check(rc, what):
-    if rc != 0:
-        raise ChartLibError('%s failed (%d): %s' % (what, rc, lib().cliora_last_error().decode()))
 
 
 class Plan:
@@ -217,18 +216,18 @@ class Plan:
         self.C = L * (L + 1) // 2
         self.Dp = (D + 15) // 16 * 16
         h = C.c_void_p()
-        check(lib().cliora_plan_create_ex(B, L, D, int(bool(share)), NORM[normalize], R, arch, C.byref(h)), 'cliora_plan_create_ex')
+        call('cliora_plan_create_ex', B, L, D, int(bool(share)), NORM[normalize], R, arch, C.byref(h))
         self.handle = h
-        self.fwd_bytes = lib().cliora_plan_fwd_workspace_bytes(h)
-        self.bwd_bytes = lib().cliora_plan_bwd_workspace_bytes(h)
-        self.pair_bytes = lib().cliora_plan_pair_states_bytes(h)    # optional workspace tail: per-pair compose outputs for the hooks
-        self.table_bytes = lib().cliora_plan_device_bytes(h)     # index tables: this much host memory, and as much HBM after the first forward
+        self.fwd_bytes = fn('cliora_plan_fwd_workspace_bytes')(h)
+        self.bwd_bytes = fn('cliora_plan_bwd_workspace_bytes')(h)
+        self.pair_bytes = fn('cliora_plan_pair_states_bytes')(h)    # optional workspace tail: per-pair compose outputs for the hooks
+        self.table_bytes = fn('cliora_plan_device_bytes')(h)     # index tables: this much host memory, and as much HBM after the first forward
 
     def table(self, name):
         import numpy as np
         ptr = C.POINTER(C.c_int32)()
         n = C.c_size_t()
-        check(lib().cliora_plan_table(self.handle, name.encode(), C.byref(ptr), C.byref(n)), 'cliora_plan_table')
+        call('cliora_plan_table', self.handle, name.encode(), C.byref(ptr), C.byref(n))
         if n.value == 0:
             return np.zeros(0, dtype=np.int32)
         return np.ctypeslib.as_array(ptr, shape=(n.value,)).copy()
@@ -236,7 +235,7 @@ class Plan:
     def __del__(self):
         try:
             if getattr(self, 'handle', None):
-                lib().cliora_plan_destroy(self.handle)
+                fn('cliora_plan_destroy')(self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -266,30 +265,13 @@ def get_plan(B, L, D, share, normalize, R, device_index, arch=0):
     return pl
 
 
-def on_device(pick):
-    """Decorator for the autograd Function bodies: run under the device of the tensor `pick(*args)` returns, so that the
-    plan's index tables, the kernels' per-device attributes and every allocation land on the tensors' GPU even when it is
-    not the current one."""
-    def deco(fn):
-        @functools.wraps(fn)
-        def run(*args):
-            import torch
-            t = pick(*args)
-            if t is None or not t.is_cuda:
-                return fn(*args)
-            with torch.cuda.device(t.device):
-                return fn(*args)
-        return run
-    return deco
-
-
 def prof_enable(kclass, on=True):
-    check(lib().cliora_prof_enable(KCLASS[kclass], int(on)), 'cliora_prof_enable')
+    call('cliora_prof_enable', KCLASS[kclass], int(on))
 
 
 def prof_read(kclass, stream=0):
     ms, n = C.c_double(), C.c_longlong()
-    check(lib().cliora_prof_read(KCLASS[kclass], C.byref(ms), C.byref(n), C.c_void_p(stream)), 'cliora_prof_read')
+    call('cliora_prof_read', KCLASS[kclass], C.byref(ms), C.byref(n), C.c_void_p(stream))
     return ms.value, n.value
 
 
@@ -302,19 +284,19 @@ WAVEFRONT_MODES = {'auto': -1, 'off': 0, 'on': 1}
 def set_wavefront(mode):
     """Scheduling of the inside / outside passes (include/cliora_chart.h: cliora_set_wavefront): 'auto' (default), 'off' (the
     reference's order on the caller's stream alone), 'on' (two streams) or 'merged' (the two passes' launches of a step as one grid on one queue).  Results are bitwise identical.  Returns the previous mode."""
-    prev = lib().cliora_set_wavefront({'merged': 2}.get(mode, WAVEFRONT_MODES.get(mode)))
+    prev = fn('cliora_set_wavefront')({'merged': 2}.get(mode, WAVEFRONT_MODES.get(mode)))
     return {-1: 'auto', 0: 'off', 1: 'on', 2: 'merged'}[prev]
 
 
 def set_resident(mode):
     """One workgroup per sentence for the level loops of a small-D DioraMLP plan (include/cliora_chart.h: cliora_set_resident):
     'auto' (default), 'off', 'on'.  Returns the previous mode's name."""
-    prev = lib().cliora_set_resident(WAVEFRONT_MODES[mode])
+    prev = fn('cliora_set_resident')(WAVEFRONT_MODES[mode])
     return {v: k for k, v in WAVEFRONT_MODES.items()}[prev]
 
 
 def set_mfma_mode(mode):
     """Arithmetic of the compose-layer GEMMs and their weight gradient: 'bf16x3' (default; three bf16 MFMAs per
     product, fp32 accumulate) or 'f32' (fp32-input MFMA, the reference's arithmetic).  Returns the previous mode."""
-    prev = lib().cliora_set_mfma_mode(MFMA_MODES[mode])
+    prev = fn('cliora_set_mfma_mode')(MFMA_MODES[mode])
     return 'f32' if prev == 0 else 'bf16x3'

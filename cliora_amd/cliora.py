@@ -8,92 +8,32 @@ Two autograd nodes, both HIP behind the C ABI: the chart (with the AttentionHead
 the leaves and in every inside aggregate, cliora.py:28-42, 71-80, 140-157) and the
 span-region / word-region scorers.
 """
-import ctypes as C
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .diora import DioraBase, ComposeMLP, Bilinear, Chart, _ptr, _stream, _param_struct, _grad_out, ragged_chart
-from .index import Index
+from ._lib import ptr, stream
+from .diora import DioraBase, ComposeMLP, Bilinear, ChartFunction, _cont
 
 DROPOUT_P = 0.1   # AttentionHead: nn.Dropout(0.1), cliora.py:32
-
-
-class VLChartFunction(torch.autograd.Function):
-    """cliora_chart_forward / _backward with image regions (R > 0)."""
-
-    @staticmethod
-    @_lib.on_device(lambda ctx, plan, holder, run_outside, x_span, *a: x_span)
-    def forward(ctx, plan, holder, run_outside, x_span, obj_span, drop_mask, *params):
-        if not x_span.is_cuda:
-            raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-        B, L, D, Cc = plan.B, plan.L, plan.D, plan.C
-        x_span = x_span.contiguous().float()
-        obj_span = obj_span.contiguous().float()
-        drop_mask = drop_mask.contiguous().float() if drop_mask is not None else None
-        ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
-        dev = x_span.device
-        inside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
-        inside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
-        outside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
-        outside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
-        inside_c = torch.zeros((B, Cc, D), device=dev, dtype=torch.float32)
-        nbytes = plan.fwd_bytes + (plan.pair_bytes if int(run_outside) & _lib.FWD_PAIR_STATES else 0)
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        pst = _param_struct(ptens)
-        rc = _lib.lib().cliora_chart_forward(plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask),
-                                            _ptr(inside_h), _ptr(inside_s), _ptr(outside_h), _ptr(outside_s), _ptr(inside_c),
-                                            _ptr(ws), nbytes, int(run_outside), _stream())
-        _lib.check(rc, 'cliora_chart_forward')
-        ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.drop_mask = plan, int(run_outside) & 1, ws, ptens, drop_mask
-        ctx.save_for_backward(x_span, obj_span, inside_h, inside_s, outside_h, outside_s)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(inside_c)
-        holder.clear()
-        holder.append(ws)
-        return inside_h, inside_s, outside_h, outside_s, inside_c
-
-    @staticmethod
-    @_lib.on_device(lambda ctx, *a: ctx.saved_tensors[0])
-    def backward(ctx, d_ih, d_is, d_oh, d_os, _d_ic):
-        plan = ctx.plan
-        x_span, obj_span, inside_h, inside_s, outside_h, outside_s = ctx.saved_tensors
-        dev = x_span.device
-        cont = lambda g: g.contiguous().float() if g is not None else None
-        d_ih, d_is, d_oh, d_os = cont(d_ih), cont(d_is), cont(d_oh), cont(d_os)
-        grads = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
-        d_x = torch.empty_like(x_span)
-        d_obj = torch.empty_like(obj_span)
-        wsb = torch.empty(plan.bwd_bytes, device=dev, dtype=torch.uint8)
-        pst, gst = _param_struct(ctx.ptens), _param_struct(grads)
-        rc = _lib.lib().cliora_chart_backward(plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask),
-                                             _ptr(inside_h), _ptr(inside_s), _ptr(outside_h), _ptr(outside_s),
-                                             _ptr(d_ih), _ptr(d_is), _ptr(d_oh), _ptr(d_os),
-                                             _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes,
-                                             _ptr(d_x), _ptr(d_obj), C.byref(gst), ctx.run_outside, _stream())
-        _lib.check(rc, 'cliora_chart_backward')
-        return (None, None, None, d_x, d_obj, None) + tuple(grads[n] for n in _lib.PARAM_FIELDS)
 
 
 class VLScoreFunction(torch.autograd.Function):
     """cliora_vl_scores_forward / _backward: the einsum('abx,cdx->acbd') scorers of cliora.py:453-466."""
 
     @staticmethod
-    @_lib.on_device(lambda ctx, plan, training, inside_h, *a: inside_h)
     def forward(ctx, plan, training, inside_h, outside_h, obj_span, x_word, obj_word, want_all):
         """x_word / obj_word None: all_atten only; want_all False (training mode only): vg_atten only."""
         B, L, Cc, R = plan.B, plan.L, plan.C, plan.R
-        tens = [t.contiguous().float() if t is not None else None for t in (inside_h, outside_h, obj_span, x_word, obj_word)]
+        tens = [_cont(t) for t in (inside_h, outside_h, obj_span, x_word, obj_word)]
         dev = tens[0].device
-        all_att = torch.empty((B, B, Cc, R), device=dev, dtype=torch.float32) if want_all else None
-        vg = torch.empty((B, B, L, R), device=dev, dtype=torch.float32) if x_word is not None else None
-        nbytes = _lib.lib().cliora_plan_vl_workspace_bytes(plan.handle)
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        rc = _lib.lib().cliora_vl_scores_forward(plan.handle, *[_ptr(t) for t in tens], int(training), _ptr(all_att), _ptr(vg),
-                                                _ptr(ws), nbytes, _stream())
-        _lib.check(rc, 'cliora_vl_scores_forward')
+        with _lib.device_guard(tens[0]):
+            all_att = torch.empty((B, B, Cc, R), device=dev, dtype=torch.float32) if want_all else None
+            vg = torch.empty((B, B, L, R), device=dev, dtype=torch.float32) if x_word is not None else None
+            nbytes = _lib.fn('cliora_plan_vl_workspace_bytes')(plan.handle)
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            _lib.call('cliora_vl_scores_forward', plan.handle, *map(ptr, tens), int(training), ptr(all_att), ptr(vg), ptr(ws), nbytes, stream())
         ctx.plan, ctx.training, ctx.nbytes = plan, int(training), nbytes
         ctx.have_words = x_word is not None
         ctx.save_for_backward(*[t for t in tens if t is not None])
@@ -101,134 +41,91 @@ class VLScoreFunction(torch.autograd.Function):
         return all_att, vg
 
     @staticmethod
-    @_lib.on_device(lambda ctx, *a: ctx.saved_tensors[0])
     def backward(ctx, d_all, d_vg):
         plan = ctx.plan
         if ctx.have_words:
             inside_h, outside_h, obj_span, x_word, obj_word = ctx.saved_tensors
         else:
             (inside_h, outside_h, obj_span), x_word, obj_word = ctx.saved_tensors, None, None
-        dev = inside_h.device
-        cont = lambda g: g.contiguous().float() if g is not None else None
-        d_all, d_vg = cont(d_all), cont(d_vg)
         need = ctx.needs_input_grad          # (plan, training, inside_h, outside_h, obj_span, x_word, obj_word, want_all)
-        d_sum = torch.empty_like(inside_h) if (need[2] or need[3]) else None
-        d_obj_span = torch.empty_like(obj_span) if need[4] else None
-        d_x_word = torch.empty_like(x_word) if (x_word is not None and need[5]) else None
-        d_obj_word = torch.empty_like(obj_word) if (obj_word is not None and need[6]) else None
-        ws = torch.empty(ctx.nbytes, device=dev, dtype=torch.uint8)
-        rc = _lib.lib().cliora_vl_scores_backward(plan.handle, _ptr(inside_h), _ptr(outside_h), _ptr(obj_span), _ptr(x_word),
-                                                 _ptr(obj_word), ctx.training, _ptr(d_all), _ptr(d_vg), _ptr(d_sum),
-                                                 _ptr(d_obj_span), _ptr(d_x_word), _ptr(d_obj_word), _ptr(ws), ctx.nbytes, _stream())
-        _lib.check(rc, 'cliora_vl_scores_backward')
+        with _lib.device_guard(inside_h):
+            d_all, d_vg = _cont(d_all), _cont(d_vg)
+            d_sum = torch.empty_like(inside_h) if (need[2] or need[3]) else None
+            d_obj_span = torch.empty_like(obj_span) if need[4] else None
+            d_x_word = torch.empty_like(x_word) if (x_word is not None and need[5]) else None
+            d_obj_word = torch.empty_like(obj_word) if (obj_word is not None and need[6]) else None
+            ws = torch.empty(ctx.nbytes, device=inside_h.device, dtype=torch.uint8)
+            _lib.call('cliora_vl_scores_backward', plan.handle, ptr(inside_h), ptr(outside_h), ptr(obj_span), ptr(x_word), ptr(obj_word),
+                      ctx.training, ptr(d_all), ptr(d_vg), ptr(d_sum), ptr(d_obj_span), ptr(d_x_word), ptr(d_obj_word), ptr(ws),
+                      ctx.nbytes, stream())
         return None, None, d_sum, d_sum, d_obj_span, d_x_word, d_obj_word, None
+
+
+def _max_backward(ctx, d_max, want_sum, want_obj):
+    """cliora_vl_scores_max_backward on the current stream for the outputs wanted (the entry takes either as NULL) -> (d_sum, d_obj)."""
+    inside_h, outside_h, obj_span, arg = ctx.saved_tensors
+    with _lib.device_guard(inside_h):
+        d_sum = torch.empty_like(inside_h) if want_sum else None
+        d_obj = torch.empty_like(obj_span) if want_obj else None
+        ws = torch.empty(ctx.nbytes, device=inside_h.device, dtype=torch.uint8)
+        _lib.call('cliora_vl_scores_max_backward', ctx.plan.handle, ptr(inside_h), ptr(outside_h), ptr(obj_span), ptr(d_max), ptr(arg),
+                  ptr(d_sum), ptr(d_obj), ptr(ws), ctx.nbytes, stream())
+    return d_sum, d_obj
 
 
 class VLMaxFunction(torch.autograd.Function):
     """cliora_vl_scores_max_forward / _backward: max over the R regions of einsum('abx,cdx->acbd', inside_h + outside_h, obj)
-    (cliora.py:457 followed by trainer.py:101) without the (B, B, C, R) tensor."""
+    (cliora.py:457 followed by trainer.py:101) without the (B, B, C, R) tensor.  The backward computes the gradients its inputs need:
+    applied to a detached region matrix it owns the gradient of the CHART rows only (d inside_h = d outside_h = d_sum_h), and VLMaxObj
+    the region matrix's (region_max)."""
 
     @staticmethod
-    @_lib.on_device(lambda ctx, plan, inside_h, *a: inside_h)
     def forward(ctx, plan, inside_h, outside_h, obj_span):
         B, Cc = plan.B, plan.C
         tens = [t.contiguous().float() for t in (inside_h, outside_h, obj_span)]
         dev = tens[0].device
-        vmax = torch.empty((B, B, Cc), device=dev, dtype=torch.float32)
-        arg = torch.empty((B, B, Cc), device=dev, dtype=torch.int32)
-        nbytes = _lib.lib().cliora_plan_vl_workspace_bytes(plan.handle)
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        rc = _lib.lib().cliora_vl_scores_max_forward(plan.handle, *[_ptr(t) for t in tens], _ptr(vmax), _ptr(arg), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, 'cliora_vl_scores_max_forward')
+        with _lib.device_guard(tens[0]):
+            vmax = torch.empty((B, B, Cc), device=dev, dtype=torch.float32)
+            arg = torch.empty((B, B, Cc), device=dev, dtype=torch.int32)
+            nbytes = _lib.fn('cliora_plan_vl_workspace_bytes')(plan.handle)
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            _lib.call('cliora_vl_scores_max_forward', plan.handle, *map(ptr, tens), ptr(vmax), ptr(arg), ptr(ws), nbytes, stream())
         ctx.plan, ctx.nbytes = plan, nbytes
         ctx.save_for_backward(*tens, arg)
         ctx.mark_non_differentiable(arg)
         return vmax, arg
 
     @staticmethod
-    @_lib.on_device(lambda ctx, *a: ctx.saved_tensors[0])
     def backward(ctx, d_max, _d_arg):
-        plan = ctx.plan
-        inside_h, outside_h, obj_span, arg = ctx.saved_tensors
+        need = ctx.needs_input_grad          # (plan, inside_h, outside_h, obj_span)
         if d_max is None:
             return None, None, None, None
-        d_max = d_max.contiguous().float()
-        d_sum = torch.empty_like(inside_h)
-        d_obj = torch.empty_like(obj_span)
-        ws = torch.empty(ctx.nbytes, device=inside_h.device, dtype=torch.uint8)
-        rc = _lib.lib().cliora_vl_scores_max_backward(plan.handle, _ptr(inside_h), _ptr(outside_h), _ptr(obj_span), _ptr(d_max), _ptr(arg),
-                                                     _ptr(d_sum), _ptr(d_obj), _ptr(ws), ctx.nbytes, _stream())
-        _lib.check(rc, 'cliora_vl_scores_max_backward')
+        d_sum, d_obj = _max_backward(ctx, d_max.contiguous().float(), need[1] or need[2], need[3])
         return None, d_sum, d_sum, d_obj
 
 
-class VLMaxRows(torch.autograd.Function):
-    """The region-max scorer as the node that owns the gradient of the CHART rows only (d inside_h = d outside_h = d_sum_h): the region
-    matrix comes in detached.  Its twin VLMaxObj owns the region matrix's gradient and runs on the library's caller lane, so that the
-    chart backward -- which needs d_sum_h -- does not wait for the 0.1-0.2 ms of the region-matrix half (cliora_vl_scores_max_backward
-    takes either output as NULL).  JoinGrad hands the one cotangent to both."""
-
-    @staticmethod
-    @_lib.on_device(lambda ctx, plan, inside_h, *a: inside_h)
-    def forward(ctx, plan, inside_h, outside_h, obj_span):
-        B, Cc = plan.B, plan.C
-        tens = [t.contiguous().float() for t in (inside_h, outside_h, obj_span)]
-        dev = tens[0].device
-        vmax = torch.empty((B, B, Cc), device=dev, dtype=torch.float32)
-        arg = torch.empty((B, B, Cc), device=dev, dtype=torch.int32)
-        nbytes = _lib.lib().cliora_plan_vl_workspace_bytes(plan.handle)
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        rc = _lib.lib().cliora_vl_scores_max_forward(plan.handle, *[_ptr(t) for t in tens], _ptr(vmax), _ptr(arg), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, 'cliora_vl_scores_max_forward')
-        ctx.plan, ctx.nbytes = plan, nbytes
-        ctx.save_for_backward(*tens, arg)
-        ctx.mark_non_differentiable(arg)
-        return vmax, arg
-
-    @staticmethod
-    @_lib.on_device(lambda ctx, *a: ctx.saved_tensors[0])
-    def backward(ctx, d_max, _d_arg):
-        plan = ctx.plan
-        inside_h, outside_h, obj_span, arg = ctx.saved_tensors
-        if d_max is None:
-            return None, None, None, None
-        d_max = d_max.contiguous().float()
-        d_sum = torch.empty_like(inside_h)
-        ws = torch.empty(ctx.nbytes, device=inside_h.device, dtype=torch.uint8)
-        rc = _lib.lib().cliora_vl_scores_max_backward(plan.handle, _ptr(inside_h), _ptr(outside_h), _ptr(obj_span), _ptr(d_max), _ptr(arg),
-                                                     _ptr(d_sum), None, _ptr(ws), ctx.nbytes, _stream())
-        _lib.check(rc, 'cliora_vl_scores_max_backward')
-        return None, d_sum, d_sum, None
-
-
 class VLMaxObj(torch.autograd.Function):
-    """The region matrix's half of the region-max scorer's backward.  forward: no work (hands `vmax` through); it is called under the
-    caller lane's stream so that autograd runs the backward there (a node's backward runs on its forward's stream)."""
+    """The region matrix's half of the region-max scorer's backward, on the library's caller lane, so that the chart backward -- which
+    needs d_sum_h -- does not wait for the 0.1-0.2 ms of the region-matrix half.  forward: no work (hands `vmax` through); it is called
+    under the caller lane's stream so that autograd runs the backward there (a node's backward runs on its forward's stream).  JoinGrad
+    hands the one cotangent to this node and to VLMaxFunction."""
 
     @staticmethod
     def forward(ctx, plan, obj_span, inside_h, outside_h, vmax, arg):
         ctx.plan = plan
-        ctx.nbytes = _lib.lib().cliora_plan_vl_workspace_bytes(plan.handle)
+        ctx.nbytes = _lib.fn('cliora_plan_vl_workspace_bytes')(plan.handle)
         ctx.save_for_backward(inside_h, outside_h, obj_span, arg)
         return vmax.view_as(vmax)
 
     @staticmethod
-    @_lib.on_device(lambda ctx, *a: ctx.saved_tensors[0])
     def backward(ctx, d_max):
-        plan = ctx.plan
-        inside_h, outside_h, obj_span, arg = ctx.saved_tensors
         if d_max is None:
             return None, None, None, None, None, None
         d_max = d_max.contiguous().float()
-        lane = torch.cuda.current_stream(inside_h.device)
-        for t in (inside_h, outside_h, obj_span, arg, d_max):       # made on the current stream, read here on the lane (see forward)
+        lane = torch.cuda.current_stream(d_max.device)
+        for t in (*ctx.saved_tensors, d_max):       # made on the current stream, read here on the lane (see forward)
             t.record_stream(lane)
-        d_obj = torch.empty_like(obj_span)
-        ws = torch.empty(ctx.nbytes, device=inside_h.device, dtype=torch.uint8)
-        rc = _lib.lib().cliora_vl_scores_max_backward(plan.handle, _ptr(inside_h), _ptr(outside_h), _ptr(obj_span), _ptr(d_max), _ptr(arg),
-                                                     None, _ptr(d_obj), _ptr(ws), ctx.nbytes, _stream())
-        _lib.check(rc, 'cliora_vl_scores_max_backward')
-        return None, d_obj, None, None, None, None
+        return None, _max_backward(ctx, d_max, False, True)[1], None, None, None, None
 
 
 class JoinGrad(torch.autograd.Function):
@@ -247,7 +144,7 @@ def region_max(plan, inside_h, outside_h, obj_span, lane):
     """(max over regions, its region) of the span-region scores; with a lane: the region matrix's gradient as a node of its own there."""
     if lane is None or not obj_span.requires_grad or not torch.is_grad_enabled():
         return VLMaxFunction.apply(plan, inside_h, outside_h, obj_span)
-    vmax_a, arg = VLMaxRows.apply(plan, inside_h, outside_h, obj_span.detach())
+    vmax_a, arg = VLMaxFunction.apply(plan, inside_h, outside_h, obj_span.detach())
     with torch.cuda.stream(lane):
         vmax_b = VLMaxObj.apply(plan, obj_span, inside_h.detach(), outside_h.detach(), vmax_a.detach(), arg)
     return JoinGrad.apply(vmax_a, vmax_b), arg
@@ -366,45 +263,24 @@ class DioraMLP(DioraBase):
     def get_chart_wrapper(self):
         return self
 
-    def forward(self, x_span, x_word, obj_embed_span=None, obj_embed_word=None):
-        if self.index is None:
-            self.index = Index(cuda=self.is_cuda)
-        self.reset()
+    def _regions(self, obj_embed_span):
         if obj_embed_span is None:
             raise ValueError('the CLIORA module needs obj_embed_span (use cliora_amd.diora.DioraMLP for text only)')
-        B, L, D = x_span.shape
-        R = obj_embed_span.shape[1]
-        assert D == self.size
-        dev_index = x_span.device.index if x_span.is_cuda else -1
-        if L > _lib.MAX_L:       # a forward-only plan (include/cliora_chart.h): refusals before the plan and any launch
-            self._check_long(L, self.training or (torch.is_grad_enabled() and any(
-                t is not None and t.requires_grad for t in [x_span, obj_embed_span] + list(self._param_tensors()))),
-                self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook'))
-        plan = _lib.get_plan(B, L, D, self.share, self.normalize, R, dev_index)
+        return obj_embed_span.shape[1]
+
+    def _run_chart(self, plan, holder, flags, x_span, obj_embed_span, params):
         mask = None
         if self.training:
             mask = self.dropout_mask
             if mask is None:   # same distribution as nn.Dropout(0.1) on the (.., R) probabilities
-                mask = F.dropout(torch.ones((B, plan.C, R), device=x_span.device), DROPOUT_P, True)
-        holder = []
-        params = self._param_tensors()
-        needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [x_span, obj_embed_span] + list(params))
-        hooks = self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook')
-        flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
-        ragged = self.__dict__.get('_ragged')
-        if ragged is not None:      # cliora_amd.ragged: a right-padded batch of mixed lengths, eval only (rows of words >= n are unspecified)
-            self._check_ragged(needs_grad, hooks)
-            ih, is_, oh, os_, ic, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, obj_embed_span, params,
-                                                                                 *ragged)
-        else:
-            ih, is_, oh, os_, ic = VLChartFunction.apply(plan, holder, flags, x_span, obj_embed_span, mask, *params)
-        ch = Chart()
-        ch.inside_h, ch.inside_s, ch.outside_h, ch.outside_s, ch.inside_c = ih, is_, oh, os_, ic
-        ch.outside_c = torch.zeros_like(oh)
-        self.chart = ch
-        self._wss, self._plan = holder, plan
-        self.init_with_batch(ih[:, :L], ic[:, :L])
-        self._serve_hooks(L)
+                mask = F.dropout(torch.ones((plan.B, plan.C, plan.R), device=x_span.device), DROPOUT_P, True)
+        return ChartFunction.apply(plan, holder, flags, x_span, obj_embed_span, mask, *params) + (None,)
+
+    def forward(self, x_span, x_word, obj_embed_span=None, obj_embed_word=None):
+        super().forward(x_span, x_word, obj_embed_span, obj_embed_word)
+        plan, ch = self._plan, self.chart
+        ih, oh = ch.inside_h, ch.outside_h
+        ch.outside_c = torch.zeros_like(oh)       # made with every forward here (the text-only module leaves it to its first reader)
         # cliora.py:453-468
         if self.training and self.lazy_region_scores:
             # training: vg_atten does not read all_atten (cliora.py:459-461) and the contrastive loss only wants its region max
@@ -427,8 +303,6 @@ class DioraMLP(DioraBase):
             all_att = LazyRegionScores(plan, ih, oh, obj_embed_span, lane)
         else:
             all_att, vg = VLScoreFunction.apply(plan, self.training, ih, oh, obj_embed_span, x_word, obj_embed_word, True)
-        self.all_atten_score = all_att
-        self.vg_atten_score_word = vg
-        self.vg_atten_score = vg
-        self.atten_score = torch.diagonal(vg, 0, 0, 1).permute(2, 0, 1)
+        self.__dict__.update(all_atten_score=all_att, vg_atten_score_word=vg, vg_atten_score=vg,
+                             atten_score=torch.diagonal(vg, 0, 0, 1).permute(2, 0, 1))
         return None

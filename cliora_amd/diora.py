@@ -17,33 +17,7 @@ from . import _lib
 from .index import Index
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _param_struct(tensors):
-    return _lib.Params(*[(t.data_ptr() if t is not None else None) for t in map(tensors.get, _lib.PARAM_FIELDS)])
-
-
-class _OnDevice(object):
-    """`with torch.cuda.device(dev)` only when `dev` is not the current device already (the context manager costs ~10 us of host
-    time per use, and a configs[0]-sized step is bound by the host: tools/host_bench.py)."""
-    __slots__ = ('ctx',)
-
-    def __init__(self, dev):
-        self.ctx = None if dev.index is None or dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self.ctx is not None:
-            return self.ctx.__exit__(*a)
+from ._lib import ptr as _ptr, stream as _stream, param_struct as _param_struct      # noqa: F401  (re-exports: the tests import them from here)
 
 
 def _grad_out(t):
@@ -60,99 +34,92 @@ def _grad_out(t):
 _grad_buffer_for = None
 
 
+def chart_buffers(plan, dev, flags, *widths):
+    """The chart outputs of one forward -- an uninitialised fp32 (B, C, w) per width -- and its workspace, with the per-pair tail when
+    `flags` asks for the hooks' states.  -> (outputs, workspace, its bytes)."""
+    outs = [torch.empty((plan.B, plan.C, w), device=dev, dtype=torch.float32) for w in widths]
+    nbytes = plan.fwd_bytes + (plan.pair_bytes if flags & _lib.FWD_PAIR_STATES else 0)
+    return outs, torch.empty(nbytes, device=dev, dtype=torch.uint8), nbytes
+
+
+def _cont(g):
+    return g.contiguous().float() if g is not None else None
+
+
 class ChartFunction(torch.autograd.Function):
-    """One autograd node for the whole inside-outside chart.
+    """One autograd node for the whole inside-outside chart, text-only (obj_span None) or with image regions (a plan of R > 0).
 
     forward  -> cliora_chart_forward   (replaces diora.py:283-398 as executed by DioraBase.forward)
     backward -> cliora_chart_backward  (replaces what autograd replays through those lines)
-    Inputs: plan, holder (list that receives the forward workspace), run_outside, x_span, then the parameter
-    tensors in _lib.PARAM_FIELDS order (None for the out_* set when the weights are shared).
+    Inputs: plan, holder (list that receives the forward workspace), run_outside, x_span, obj_span, drop_mask, then the parameter
+    tensors in _lib.PARAM_FIELDS order (None for the out_* set when the weights are shared).  Without obj_span the library gets NULL
+    for obj_span, drop_mask, inside_c and d_obj_span, and the fifth output, inside_c, is None.
     Every C-ABI call runs under the tensors' device (the plan's index tables and the kernels' LDS attribute are per device).
     """
 
     @staticmethod
-    def forward(ctx, plan, holder, run_outside, x_span, *params):
+    def forward(ctx, plan, holder, run_outside, x_span, obj_span, drop_mask, *params):
         if not x_span.is_cuda:
             raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-        B, L, D, Cc = plan.B, plan.L, plan.D, plan.C
-        x_span = x_span.contiguous().float()
+        D, run_outside, vl = plan.D, int(run_outside), obj_span is not None
+        x_span, obj_span, drop_mask = x_span.contiguous().float(), _cont(obj_span), _cont(drop_mask)
         ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
-        dev = x_span.device
-        with _OnDevice(dev):
-            inside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
-            inside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
-            outside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
-            outside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
-            nbytes = plan.fwd_bytes + (plan.pair_bytes if int(run_outside) & _lib.FWD_PAIR_STATES else 0)
-            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        with _lib.device_guard(x_span):
+            outs, ws, nbytes = chart_buffers(plan, x_span.device, run_outside, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
+            inside_c = outs.pop().zero_() if vl else None
             pst = _param_struct(ptens)
-            rc = _lib.lib().cliora_chart_forward(
-                plan.handle, C.byref(pst), _ptr(x_span), None, None, _ptr(inside_h), _ptr(inside_s),
-                _ptr(outside_h), _ptr(outside_s), None, _ptr(ws), nbytes, int(run_outside), _stream())
-            _lib.check(rc, 'cliora_chart_forward')
-        ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens = plan, int(run_outside) & 1, ws, ptens
-        ctx.save_for_backward(x_span, inside_h, inside_s, outside_h, outside_s)
+            _lib.call('cliora_chart_forward', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask),
+                      *map(_ptr, outs), _ptr(inside_c), _ptr(ws), nbytes, run_outside, _stream())
+        ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.drop_mask, ctx.vl = plan, run_outside & 1, ws, ptens, drop_mask, vl
+        ctx.save_for_backward(x_span, *((obj_span,) if vl else ()), *outs)
         ctx.set_materialize_grads(False)
+        if vl:
+            ctx.mark_non_differentiable(inside_c)
         holder.clear()
         holder.append(ws)
-        return inside_h, inside_s, outside_h, outside_s
+        return (*outs, inside_c)
 
     @staticmethod
-    def backward(ctx, d_ih, d_is, d_oh, d_os):
-        plan = ctx.plan
-        x_span, inside_h, inside_s, outside_h, outside_s = ctx.saved_tensors
-        dev = x_span.device
-        cont = lambda g: g.contiguous().float() if g is not None else None
-        d_ih, d_is, d_oh, d_os = cont(d_ih), cont(d_is), cont(d_oh), cont(d_os)
-        with _OnDevice(dev):
+    def backward(ctx, d_ih, d_is, d_oh, d_os, _d_ic):
+        plan, saved = ctx.plan, ctx.saved_tensors
+        x_span, obj_span = saved[0], (saved[1] if ctx.vl else None)
+        with _lib.device_guard(x_span):
             d_x = torch.empty_like(x_span)
+            d_obj = torch.empty_like(obj_span) if ctx.vl else None
             pst = _param_struct(ctx.ptens)
             g = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
-            wsb = torch.empty(plan.bwd_bytes, device=dev, dtype=torch.uint8)
+            wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
             gst = _param_struct(g)
-            rc = _lib.lib().cliora_chart_backward(
-                plan.handle, C.byref(pst), _ptr(x_span), None, None, _ptr(inside_h), _ptr(inside_s),
-                _ptr(outside_h), _ptr(outside_s), _ptr(d_ih), _ptr(d_is), _ptr(d_oh), _ptr(d_os),
-                _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), None, C.byref(gst),
-                ctx.run_outside, _stream())
-            _lib.check(rc, 'cliora_chart_backward')
-        return (None, None, None, d_x) + tuple(g[n] for n in _lib.PARAM_FIELDS)
+            _lib.call('cliora_chart_backward', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask),
+                      *map(_ptr, saved[-4:]), *[_ptr(_cont(d)) for d in (d_ih, d_is, d_oh, d_os)],
+                      _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst),
+                      ctx.run_outside, _stream())
+        return (None, None, None, d_x, d_obj, None) + tuple(g[n] for n in _lib.PARAM_FIELDS)
 
 
 def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_levels):
     """cliora_chart_forward_ragged (include/cliora_chart.h): both passes of a right-padded batch of mixed lengths, inference only, so no
     autograd node.  lengths: int32 device tensor (B,); root_levels: the bit mask of {n - 1}.  -> inside_h, inside_s, outside_h,
     outside_s, inside_c (None for a text-only plan), status (1,) int32 on the device, which the caller must read."""
-    lib = _lib.lib()
-    if not hasattr(lib, 'cliora_chart_forward_ragged'):
-        raise _lib.ChartLibError('%s has no cliora_chart_forward_ragged: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
     if not x_span.is_cuda:
         raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-    B, Cc, D = plan.B, plan.C, plan.D
-    dev = x_span.device
-    if lengths.dtype != torch.int32 or lengths.numel() != B or lengths.device != dev:
-        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (B, dev))
-    x_span = x_span.detach().contiguous().float()
-    obj_span = obj_span.detach().contiguous().float() if obj_span is not None else None
+    D, dev, vl = plan.D, x_span.device, obj_span is not None
+    if lengths.dtype != torch.int32 or lengths.numel() != plan.B or lengths.device != dev:
+        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (plan.B, dev))
+    x_span, obj_span = x_span.detach().contiguous().float(), _cont(obj_span.detach() if vl else None)
     lengths = lengths.contiguous()
     ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
-    with _OnDevice(dev):
-        inside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
-        inside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
-        outside_h = torch.empty((B, Cc, D), device=dev, dtype=torch.float32)
-        outside_s = torch.empty((B, Cc, 1), device=dev, dtype=torch.float32)
-        inside_c = torch.zeros((B, Cc, D), device=dev, dtype=torch.float32) if obj_span is not None else None
+    with _lib.device_guard(x_span):
+        outs, ws, nbytes = chart_buffers(plan, dev, 0, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
+        inside_c = outs.pop().zero_() if vl else None
         status = torch.empty(1, device=dev, dtype=torch.int32)
-        ws = torch.empty(plan.fwd_bytes, device=dev, dtype=torch.uint8)
         pst = _param_struct(ptens)
-        rc = lib.cliora_chart_forward_ragged(
-            plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), None, _ptr(inside_h), _ptr(inside_s), _ptr(outside_h),
-            _ptr(outside_s), _ptr(inside_c), _ptr(ws), plan.fwd_bytes, int(bool(outside)) | _lib.FWD_NO_BACKWARD, _ptr(lengths),
-            int(root_levels), _ptr(status), _stream())
-        _lib.check(rc, 'cliora_chart_forward_ragged')
+        _lib.call('cliora_chart_forward_ragged', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), None, *map(_ptr, outs),
+                  _ptr(inside_c), _ptr(ws), nbytes, int(bool(outside)) | _lib.FWD_NO_BACKWARD, _ptr(lengths), int(root_levels),
+                  _ptr(status), _stream())
     holder.clear()
     holder.append(ws)
-    return inside_h, inside_s, outside_h, outside_s, inside_c, status
+    return (*outs, inside_c, status)
 
 
 # --------------------------------------------------------------------------------------
@@ -327,12 +294,30 @@ class DioraBase(nn.Module):
                      out_mat=mods['outside_score_func']._parameters['mat'])
         return [t.get(n) for n in _lib.PARAM_FIELDS]
 
+    # ---- what a subclass supplies to forward(): the plan's arch, and the three methods below (with _param_tensors)
+    plan_arch = 0
+
+    def _regions(self, obj_embed_span):
+        """The plan's R for this module's kind of call; refuses an obj_embed_span it cannot take."""
+        if obj_embed_span is not None:
+            raise NotImplementedError('text-only DIORA module; use cliora_amd.cliora.DioraMLP with image regions')
+        return 0
+
+    def _run_chart(self, plan, holder, flags, x_span, obj_embed_span, params):
+        """The one call that runs the chart -> (inside_h, inside_s, outside_h, outside_s, inside_c, outside_c); a cell state None is
+        identically zero (Chart creates it when first read)."""
+        return ChartFunction.apply(plan, holder, flags, x_span, None, None, *params) + (None,)
+
+    def _run_ragged(self, plan, holder, x_span, obj_embed_span, params, ragged):
+        """_run_chart through cliora_chart_forward_ragged (cliora_amd.ragged); the status word is left in _ragged_status."""
+        *charts, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, obj_embed_span, params, *ragged)
+        return (*charts, None)
+
     def forward(self, x_span, x_word=None, obj_embed_span=None, obj_embed_word=None):
         if self.index is None:
             self.index = Index(cuda=self.is_cuda)
         self.reset()
-        if obj_embed_span is not None:
-            raise NotImplementedError('text-only DIORA module; use cliora_amd.cliora.DioraMLP with image regions')
+        R = self._regions(obj_embed_span)
         B, L, D = x_span.shape
         assert D == self.size
         dev_index = x_span.device.index if x_span.is_cuda else -1
@@ -340,23 +325,24 @@ class DioraBase(nn.Module):
         # eval / torch.no_grad: nothing will ask for the backward, so the per-pair state is not written -- unless a hook
         # override wants the per-split tensors (analysis/utils.py:67-95)
         params = self._param_tensors()
-        needs_grad = torch.is_grad_enabled() and (x_span.requires_grad or any(t is not None and t.requires_grad for t in params))
+        needs_grad = torch.is_grad_enabled() and (x_span.requires_grad or (obj_embed_span is not None and obj_embed_span.requires_grad)
+                                                  or any(t is not None and t.requires_grad for t in params))
         hooks = self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook')
         self._check_long(L, needs_grad, hooks)
-        plan = _lib.get_plan(B, L, D, self.share, self.normalize, 0, dev_index)
+        plan = _lib.get_plan(B, L, D, self.share, self.normalize, R, dev_index, arch=self.plan_arch)
         flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
         ragged = self.__dict__.get('_ragged')
         if ragged is not None:
             self._check_ragged(needs_grad, hooks)
-            ih, is_, oh, os_, _, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, None, params, *ragged)
+            charts = self._run_ragged(plan, holder, x_span, obj_embed_span, params, ragged)
         else:
-            ih, is_, oh, os_ = ChartFunction.apply(plan, holder, flags, x_span, *params)
+            charts = self._run_chart(plan, holder, flags, x_span, obj_embed_span, params)
         ch = Chart()
-        ch.inside_h, ch.inside_s, ch.outside_h, ch.outside_s = ih, is_, oh, os_       # the zero cell states: on first read (Chart)
+        ch.inside_h, ch.inside_s, ch.outside_h, ch.outside_s, ch.inside_c, ch.outside_c = charts      # a zero cell state: on first read (Chart)
         d = self.__dict__
         d['chart'], d['_wss'], d['_plan'] = ch, holder, plan
         if self._hook_overridden('init_with_batch'):      # analysis/utils.py:67-76 wraps it: then it gets the reference's arguments
-            self.init_with_batch(ih[:, :L], ch.inside_c[:, :L])
+            self.init_with_batch(ch.inside_h[:, :L], ch.inside_c[:, :L])
         else:
             d['batch_size'], d['length'] = B, L
         if hooks:
@@ -364,19 +350,24 @@ class DioraBase(nn.Module):
         return None
 
     # ---- un-aggregated per-split tensors the hooks receive (diora.py:295-334)
+    def _level_views(self, entry, ws, level):
+        """(scores (rows,), compose outputs (rows, ld)) of one level as fp32 views of the workspace `ws`; entry: cliora_inside_pair_states or
+        cliora_outside_pair_states."""
+        ps, ph, rows, ldh = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
+        _lib.call(entry, self._plan.handle, _ptr(ws), level, C.byref(ps), C.byref(ph), C.byref(rows), C.byref(ldh))
+        wsf = ws.view(torch.float32)
+        so, ho = (ps.value - ws.data_ptr()) // 4, (ph.value - ws.data_ptr()) // 4
+        n, ld = rows.value, ldh.value
+        return wsf[so:so + n], wsf[ho:ho + n * ld].view(n, ld)
+
     def pair_states(self, level):
         """(h, s) of one inside level: h (B*Lc*N, D) compose outputs, s (B, Lc, N, 1) split scores."""
         plan = self._plan
         hs, ss = [], []
         for ws in self._wss:
-            ps, ph, rows, ldh = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
-            _lib.check(_lib.lib().cliora_inside_pair_states(plan.handle, _ptr(ws), level, C.byref(ps), C.byref(ph),
-                                                            C.byref(rows), C.byref(ldh)), 'cliora_inside_pair_states')
-            wsf = ws.view(torch.float32)
-            so, ho = (ps.value - ws.data_ptr()) // 4, (ph.value - ws.data_ptr()) // 4
-            n, ld = rows.value, ldh.value
-            ss.append(wsf[so:so + n].view(plan.B, plan.L - level, level, 1))
-            hs.append(wsf[ho:ho + n * ld].view(n, ld)[:, :plan.D])
+            s, h = self._level_views('cliora_inside_pair_states', ws, level)
+            ss.append(s.view(plan.B, plan.L - level, level, 1))
+            hs.append(h[:, :plan.D])
         if len(hs) == 1:
             return hs[0], ss[0]
         return torch.cat(hs, 0), torch.cat(ss, 0)
@@ -392,17 +383,10 @@ class DioraBase(nn.Module):
         nn_ = torch.where(jj < N - ii, L - 2 - ii - level, N - ii - 1)          # our split of the reference's (i, j)
         hs, ss = [], []
         for ws in self._wss:
-            ps, ph, rows, ldh = C.c_void_p(), C.c_void_p(), C.c_size_t(), C.c_size_t()
-            _lib.check(_lib.lib().cliora_outside_pair_states(plan.handle, _ptr(ws), level, C.byref(ps), C.byref(ph),
-                                                             C.byref(rows), C.byref(ldh)), 'cliora_outside_pair_states')
-            wsf = ws.view(torch.float32)
-            so, ho = (ps.value - ws.data_ptr()) // 4, (ph.value - ws.data_ptr()) // 4
-            n, ld = rows.value, ldh.value
+            s, h = self._level_views('cliora_outside_pair_states', ws, level)
             jd, nd = jj.to(ws.device), nn_.to(ws.device)
-            s_ours = wsf[so:so + n].view(plan.B, Lc, N)
-            h_ours = wsf[ho:ho + n * ld].view(plan.B, Lc, N, ld)
-            ss.append(s_ours[:, jd, nd].unsqueeze(-1))                           # (B, N, Lc, 1)
-            hs.append(h_ours[:, jd, nd][..., :plan.D].reshape(plan.B * N * Lc, plan.D))
+            ss.append(s.view(plan.B, Lc, N)[:, jd, nd].unsqueeze(-1))                           # (B, N, Lc, 1)
+            hs.append(h.view(plan.B, Lc, N, -1)[:, jd, nd][..., :plan.D].reshape(plan.B * N * Lc, plan.D))
         if len(hs) == 1:
             return hs[0], ss[0]
         return torch.cat(hs, 0), torch.cat(ss, 0)
@@ -443,7 +427,7 @@ class DioraBase(nn.Module):
                 else:
                     spans = torch.empty((plan.B, plan.L - 1, 2), device=ws.device, dtype=torch.int32)
                 if plan.L > 1:
-                    _lib.check(_lib.lib().cliora_cky_spans(plan.handle, _ptr(ws), None, _ptr(spans), _stream()), 'cliora_cky_spans')
+                    _lib.call('cliora_cky_spans', plan.handle, _ptr(ws), None, _ptr(spans), _stream())
             parts.append(spans)
         if len(parts) == 1:
             return parts[0]

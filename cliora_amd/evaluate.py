@@ -12,7 +12,6 @@ output.  What stays on the host is what must be bitwise the reference's: the flo
     m = evaluate(net, batches, idx2word, out_path='parse.jsonl')     # net: harness.Net; batches: batch_map dicts
     m['corpus_f1'], m['sent_f1'], m['ground_acc'], m['ccra']
 """
-import ctypes as C
 
 import numpy as np
 import torch
@@ -118,9 +117,6 @@ def ground(atten, boxes, targets, spans, device=None, lengths=None, extra_status
     P, G, NS = targets.P, targets.G, L - 1
     R = atten.shape[2] if atten is not None else 0
     dev = atten.device if atten is not None else device
-    lib = _lib.lib()
-    if not hasattr(lib, 'cliora_ground_eval'):
-        raise _lib.ChartLibError('%s has no cliora_ground_eval: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
     # output buffer: [status | sent B*3 | phrases P*4 | spans B*NS*2 | span boxes B*NS*4 (fp32 bits)]
     extra_status = list(extra_status)
     sizes = [1, B * 3, P * 4, B * NS * 2, B * NS * 4 if atten is not None else 0, len(extra_status)]
@@ -143,21 +139,17 @@ def ground(atten, boxes, targets, spans, device=None, lengths=None, extra_status
             sb, sl, sr = atten.stride()
         else:
             boxes, sb, sl, sr = None, 0, 0, 0
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p, st = _lib.ptr_or_null, _lib.stream()
         if lengths is None:
-            _lib.check(lib.cliora_ground_eval(B, L, R, p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span), p(phr_box), p(d_spans), G,
-                                              p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]), p(sec[1]), p(sec[0]), st),
-                       'cliora_ground_eval')
+            _lib.call('cliora_ground_eval', B, L, R, p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span), p(phr_box), p(d_spans), G,
+                      p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]), p(sec[1]), p(sec[0]), st)
         else:
-            if not hasattr(lib, 'cliora_ground_eval_ragged'):
-                raise _lib.ChartLibError('%s has no cliora_ground_eval_ragged: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
             lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
             if lengths.numel() != B:
                 raise ValueError('lengths holds %d sentences, not %d' % (lengths.numel(), B))
-            _lib.check(lib.cliora_ground_eval_ragged(B, L, R, p(lengths), p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span),
-                                                     p(phr_box), p(d_spans), G, p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]),
-                                                     p(sec[1]), p(sec[0]), st), 'cliora_ground_eval_ragged')
+            _lib.call('cliora_ground_eval_ragged', B, L, R, p(lengths), p(atten), sb, sl, sr, p(boxes), P, p(phr_off), p(phr_span),
+                      p(phr_box), p(d_spans), G, p(gold_off), p(gold_span), p(sec[2]), None, p(sec[4]),
+                      p(sec[1]), p(sec[0]), st)
         for k, (_, t) in enumerate(extra_status):
             sec[5][k:k + 1].copy_((t() if callable(t) else t).reshape(1))
         host = out.cpu().numpy()

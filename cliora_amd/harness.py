@@ -124,19 +124,17 @@ class FusedContrastive(torch.autograd.Function):
     @staticmethod
     def forward(ctx, smax, ins, outs, margin, alpha):
         from . import _lib
-        import ctypes as C
         B, _, Cc = smax.shape
         smax, ins, outs = smax.contiguous().float(), ins.contiguous().float(), outs.contiguous().float()
         dev = smax.device
         loss = torch.empty(1, device=dev)
         d_smax, d_ins, d_outs = torch.empty_like(smax), torch.empty_like(ins), torch.empty_like(outs)
-        nbytes = _lib.lib().cliora_contrastive_workspace_bytes(B, Cc)
+        nbytes = _lib.fn('cliora_contrastive_workspace_bytes')(B, Cc)
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(dev):
-            rc = _lib.lib().cliora_contrastive_loss(B, Cc, p(smax), p(ins), p(outs), float(margin), float(alpha), p(loss), p(d_smax), p(d_ins),
-                                                   p(d_outs), p(ws), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        _lib.check(rc, 'cliora_contrastive_loss')
+        p = _lib.ptr
+        with _lib.device_guard(smax):
+            _lib.call('cliora_contrastive_loss', B, Cc, p(smax), p(ins), p(outs), float(margin), float(alpha), p(loss), p(d_smax), p(d_ins),
+                      p(d_outs), p(ws), nbytes, _lib.stream())
         ctx.save_for_backward(d_smax, d_ins, d_outs)
         return loss.reshape(())
 

@@ -13,19 +13,12 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+from ._lib import ptr, stream, device_guard
 
 
 def _grad_out(t):
     from .diora import _grad_out as g
     return g(t)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def supported(*tensors):
@@ -70,9 +63,8 @@ class DeferredTableGrads(object):
             rows = (C.c_void_p * n)(*[t.data_ptr() for t, _ in segs])
             idx = (C.c_void_p * n)(*[i.data_ptr() for _, i in segs])
             cnt = (C.c_int32 * n)(*[int(i.numel()) for _, i in segs])
-            with torch.cuda.device(view.device):
-                _lib.check(_lib.lib().cliora_rows_scatter_add_segments(rows, idx, cnt, n, int(view.shape[1]), _p(view), int(view.shape[0]), _st()),
-                           'cliora_rows_scatter_add_segments')
+            with device_guard(view):
+                _lib.call('cliora_rows_scatter_add_segments', rows, idx, cnt, n, int(view.shape[1]), ptr(view), int(view.shape[0]), stream())
             # what reached the table outside offer() -- a refused producer's own tensor, a torch-autograd lookup -- is in param.grad
             if param.grad is not None and param.grad.data_ptr() != view.data_ptr():
                 view.add_(param.grad)
@@ -114,9 +106,9 @@ def scatter_rows(d_rows, index, table, producer_lane=None):
         # d_rows is still being written on another stream and the scatter runs here, now
         torch.cuda.current_stream(table.device).wait_stream(producer_lane)
     out = torch.empty_like(table) if held else _grad_out(table)      # held: the arena slice belongs to the deferred flush
-    with torch.cuda.device(table.device):
-        _lib.check(_lib.lib().cliora_rows_scatter_add(_p(d_rows.contiguous()), _p(index.contiguous()), int(index.numel()), int(table.shape[1]), _p(out),
-                                                      int(table.shape[0]), _st()), 'cliora_rows_scatter_add')
+    with device_guard(table):
+        _lib.call('cliora_rows_scatter_add', ptr(d_rows.contiguous()), ptr(index.contiguous()), int(index.numel()), int(table.shape[1]), ptr(out),
+                  int(table.shape[0]), stream())
     return out
 
 
@@ -137,12 +129,11 @@ class Proj(torch.autograd.Function):
         K, D = x.shape[-1], w.shape[0]
         x2 = x.reshape(-1, K)
         nrows = index.numel() if index is not None else x2.shape[0]
-        lib = _lib.lib()
-        with torch.cuda.device(x.device):
+        with device_guard(x):
             y = torch.empty((nrows, D), device=x.device, dtype=torch.float32)
-            nb = lib.cliora_proj_workspace_bytes(nrows, K, D)
+            nb = _lib.fn('cliora_proj_workspace_bytes')(nrows, K, D)
             ws = torch.empty(nb, device=x.device, dtype=torch.uint8)
-            _lib.check(lib.cliora_proj_forward(_p(x2), _p(index), nrows, K, _p(w), _p(bias), D, _p(y), _p(ws), nb, _st()), 'cliora_proj_forward')
+            _lib.call('cliora_proj_forward', ptr(x2), ptr(index), nrows, K, ptr(w), ptr(bias), D, ptr(y), ptr(ws), nb, stream())
         ctx.save_for_backward(x2, index, w)
         ctx.has_bias, ctx.x_shape, ctx.ws, ctx.bias = bias is not None, x.shape, ws, (bias.detach() if bias is not None else None)
         return y
@@ -153,17 +144,16 @@ class Proj(torch.autograd.Function):
         d_y = d_y.contiguous().float()
         nrows, D = d_y.shape
         K = x2.shape[1]
-        lib = _lib.lib()
         need_x = ctx.needs_input_grad[0]
-        with torch.cuda.device(d_y.device):
+        with device_guard(d_y):
             # the parameter's slice of a live flat gradient buffer when there is one (cliora_amd.parallel: the all-reduce and the fused
             # clip + Adam then have nothing to copy), else a fresh tensor
             d_w = _grad_out(w) if ctx.needs_input_grad[2] else None
             d_b = _grad_out(ctx.bias) if (ctx.has_bias and ctx.needs_input_grad[3]) else None
             d_rows = torch.empty((nrows, K), device=d_y.device) if need_x else None
             nb = ctx.ws.numel()
-            _lib.check(lib.cliora_proj_backward(_p(x2), _p(index), nrows, K, _p(w), _p(d_y), D, _p(d_w), _p(d_b), _p(d_rows), _p(ctx.ws), nb, _st()),
-                       'cliora_proj_backward')
+            _lib.call('cliora_proj_backward', ptr(x2), ptr(index), nrows, K, ptr(w), ptr(d_y), D, ptr(d_w), ptr(d_b), ptr(d_rows), ptr(ctx.ws), nb,
+                      stream())
             d_x = None
             if need_x:
                 if index is None:
@@ -193,13 +183,12 @@ class ReconLoss(torch.autograd.Function):
         B, L = tokens.shape
         Cc, D = outside_h.shape[1], outside_h.shape[2]
         E, Kn = emb.shape[1], neg.numel()
-        lib = _lib.lib()
-        with torch.cuda.device(emb.device):
+        with device_guard(emb):
             loss = torch.empty(1, device=emb.device)
-            nb = lib.cliora_recon_workspace_bytes(B * L, Kn, E, D)
+            nb = _lib.fn('cliora_recon_workspace_bytes')(B * L, Kn, E, D)
             ws = torch.empty(nb, device=emb.device, dtype=torch.uint8)
-            _lib.check(lib.cliora_recon_forward(_p(tokens), _p(neg), B, L, Cc, Kn, _p(emb), E, _p(mat), D, _p(outside_h), _p(loss), _p(ws), nb, _st()),
-                       'cliora_recon_forward')
+            _lib.call('cliora_recon_forward', ptr(tokens), ptr(neg), B, L, Cc, Kn, ptr(emb), E, ptr(mat), D, ptr(outside_h), ptr(loss), ptr(ws), nb,
+                      stream())
         ctx.save_for_backward(emb, mat, outside_h, tokens, neg)
         ctx.ws = ws
         return loss.reshape(())
@@ -210,21 +199,21 @@ class ReconLoss(torch.autograd.Function):
         B, L = tokens.shape
         Cc, D = outside_h.shape[1], outside_h.shape[2]
         E, Kn = emb.shape[1], neg.numel()
-        lib = _lib.lib()
-        with torch.cuda.device(emb.device):
+        with device_guard(emb):
             g = g.contiguous().float().reshape(1)
             d_cell = torch.empty((B * L, D), device=emb.device) if ctx.needs_input_grad[2] else None
             d_mat = _grad_out(mat) if ctx.needs_input_grad[1] else None
             d_rows = torch.empty((B * L + Kn, E), device=emb.device) if ctx.needs_input_grad[0] else None
             nb = ctx.ws.numel()
-            args = lambda dc, dm, dr: (_p(tokens), _p(neg), B, L, Cc, Kn, _p(emb), E, _p(mat), D, _p(outside_h), _p(g), _p(dc), _p(dm), _p(dr), _p(ctx.ws), nb, _st())
+            args = lambda dc, dm, dr: (ptr(tokens), ptr(neg), B, L, Cc, Kn, ptr(emb), E, ptr(mat), D, ptr(outside_h), ptr(g), ptr(dc), ptr(dm), ptr(dr),
+                                       ptr(ctx.ws), nb, stream())
             lane = _step_lane(emb.device) if (d_cell is not None and (d_mat is not None or d_rows is not None)) else None
             if lane is None:
-                _lib.check(lib.cliora_recon_backward(*args(d_cell, d_mat, d_rows)), 'cliora_recon_backward')
+                _lib.call('cliora_recon_backward', *args(d_cell, d_mat, d_rows))
             else:
                 # inside harness.Trainer.step: the chart backward waits for d cell only; the projection's and the looked-up rows' gradients
                 # (two GEMMs, 0.07 ms at c2) follow on the caller lane, behind the first call (they share its workspace), beside the chart
-                _lib.check(lib.cliora_recon_backward(*args(d_cell, None, None)), 'cliora_recon_backward')
+                _lib.call('cliora_recon_backward', *args(d_cell, None, None))
                 cur = torch.cuda.current_stream(emb.device)
                 lane.wait_stream(cur)
                 # made on this stream, read on the lane: not reused before the lane is done with them (the cotangent, and the padded
@@ -232,7 +221,7 @@ class ReconLoss(torch.autograd.Function):
                 for t in (g, ctx.ws, emb, mat, tokens, neg):
                     t.record_stream(lane)
                 with torch.cuda.stream(lane):
-                    _lib.check(lib.cliora_recon_backward(*args(None, d_mat, d_rows)), 'cliora_recon_backward')
+                    _lib.call('cliora_recon_backward', *args(None, d_mat, d_rows))
             d_oh = None
             if d_cell is not None:
                 d_oh = torch.zeros_like(outside_h)
@@ -253,13 +242,12 @@ class VGLossFn(torch.autograd.Function):
     def forward(ctx, vg, alpha):
         vg = vg.contiguous().float()
         B, _, L, R = vg.shape
-        lib = _lib.lib()
-        with torch.cuda.device(vg.device):
+        with device_guard(vg):
             loss = torch.empty(1, device=vg.device)
             d_vg = torch.empty_like(vg) if ctx.needs_input_grad[0] else None
-            nb = lib.cliora_vg_workspace_bytes(B, L)
+            nb = _lib.fn('cliora_vg_workspace_bytes')(B, L)
             ws = torch.empty(nb, device=vg.device, dtype=torch.uint8)
-            _lib.check(lib.cliora_vg_loss(B, L, R, _p(vg), float(alpha), _p(loss), _p(d_vg), _p(ws), nb, _st()), 'cliora_vg_loss')
+            _lib.call('cliora_vg_loss', B, L, R, ptr(vg), float(alpha), ptr(loss), ptr(d_vg), ptr(ws), nb, stream())
         ctx.d_vg = d_vg
         return loss.reshape(())
 
@@ -304,7 +292,7 @@ class FusedClipAdam(object):
         # need neither the save / restore of the skipped segments nor a fill per step
         self.ever = [False] * len(self.params)
         self.grads.flat.zero_()
-        self.ws = torch.empty(_lib.lib().cliora_clip_adam_workspace_bytes(), device=dev, dtype=torch.uint8)
+        self.ws = torch.empty(_lib.fn('cliora_clip_adam_workspace_bytes')(), device=dev, dtype=torch.uint8)
 
     def zero_grad(self):
         for p in self.params:
@@ -333,10 +321,10 @@ class FusedClipAdam(object):
         # parameter that receives gradients only on SOME steps is corrected with the global count here, with its own in torch.)
         saved = [(o, n, self.flat_p[o:o + n].clone(), self.m[o:o + n].clone(), self.v[o:o + n].clone()) for o, n in skipped]
         self.t += 1
-        with torch.cuda.device(self.flat_p.device):
-            _lib.check(_lib.lib().cliora_clip_adam(_p(self.flat_p), _p(ar.flat), _p(self.m), _p(self.v), self.flat_p.numel(), float(self.max_norm),
-                                                  float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.t, _p(self.ws),
-                                                  self.ws.numel(), _st()), 'cliora_clip_adam')
+        with device_guard(self.flat_p):
+            _lib.call('cliora_clip_adam', ptr(self.flat_p), ptr(ar.flat), ptr(self.m), ptr(self.v), self.flat_p.numel(), float(self.max_norm),
+                      float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.t, ptr(self.ws),
+                      self.ws.numel(), stream())
         for o, n, p0, m0, v0 in saved:
             self.flat_p[o:o + n].copy_(p0); self.m[o:o + n].copy_(m0); self.v[o:o + n].copy_(v0)
         # the clipped values are what the kernel applied; gradients that live outside the arena (torch-produced, copied in above)

@@ -19,25 +19,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr_or_null as _p, stream as _stream
 from .interchange import postprocess as _postprocess, replace_leaves
 
 MODES = ('entities', 'given', 'latent', 'all-spans')
 MAX_K = 128
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _native():
-    lib = _lib.lib()
-    if not hasattr(lib, 'cliora_knn_ip'):
-        raise _lib.ChartLibError('%s has no cliora_knn_ip: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
-    return lib
 
 
 # ---- spans of one batch ---------------------------------------------------------------------------------------------
@@ -145,14 +131,13 @@ class PhraseSet(object):
         if self.device is None:
             self.device = dev
         N = len(rows)
-        lib = _native()
         with torch.cuda.device(dev):
             self._reserve(self.n + N, dev)
             tab = torch.from_numpy(np.array([r[:3] for r in rows], dtype=np.int32).reshape(-1, 3)).to(dev)
             status = torch.zeros(1, dtype=torch.int32, device=dev)
-            _lib.check(lib.cliora_phrase_gather(B, L, D, _p(inside_h), inside_h.stride(0), inside_h.stride(1), _p(outside_h),
-                                                outside_h.stride(0), outside_h.stride(1), N, _p(tab), int(bool(normalize)), _p(self._buf),
-                                                self._buf.stride(0), self.n, _p(status), _stream()), 'cliora_phrase_gather')
+            _lib.call('cliora_phrase_gather', B, L, D, _p(inside_h), inside_h.stride(0), inside_h.stride(1), _p(outside_h),
+                      outside_h.stride(0), outside_h.stride(1), N, _p(tab), int(bool(normalize)), _p(self._buf),
+                      self._buf.stride(0), self.n, _p(status), _stream())
             bad = int(status.item()) if N else 0
         if bad:
             raise _lib.ChartLibError('cliora_phrase_gather rejected %d phrase(s) outside their sentence' % bad)
@@ -243,7 +228,6 @@ def embed_phrases_ragged(net, sentences, mode, example_ids=None, entity_labels=N
         raise ValueError("mode 'entities' needs entity_labels")
     if mode == 'given' and trees is None:
         raise ValueError("mode 'given' needs the sentences' trees")
-    lib = _native()
     diora = net.diora
     dev = next(net.parameters()).device
     keep = [i for i, s_ in enumerate(sentences) if len(s_) > 2]
@@ -279,9 +263,8 @@ def embed_phrases_ragged(net, sentences, mode, example_ids=None, entity_labels=N
             out = torch.empty((N, 2 * D), dtype=torch.float32, device=dev)
             tab = torch.from_numpy(np.array([r[:3] for r in rows], dtype=np.int32).reshape(-1, 3)).to(dev)
             status = torch.zeros(1, dtype=torch.int32, device=dev)
-            _lib.check(lib.cliora_phrase_gather(B, d._plan.L, D, _p(ih), ih.stride(0), ih.stride(1), _p(oh), oh.stride(0), oh.stride(1), N,
-                                                _p(tab), int(bool(normalize)), _p(out), out.stride(0), 0, _p(status), _stream()),
-                       'cliora_phrase_gather')
+            _lib.call('cliora_phrase_gather', B, d._plan.L, D, _p(ih), ih.stride(0), ih.stride(1), _p(oh), oh.stride(0), oh.stride(1), N,
+                      _p(tab), int(bool(normalize)), _p(out), out.stride(0), 0, _p(status), _stream())
             bad = torch.stack([status[0], d._ragged_status[0]]).cpu().tolist() if N else [0, int(d._ragged_status.item())]
         if any(bad):
             raise _lib.ChartLibError('the padded chart rejected %d phrase(s) / %d sentence length(s)' % tuple(bad))
@@ -318,18 +301,17 @@ def knn_ip(q, keys, k):
             raise ValueError('queries and keys must be fp32 CUDA rows with unit stride along D')
     nq, D = q.shape
     nk = keys.shape[0]
-    lib = _native()
     dev = q.device
     with torch.cuda.device(dev):
         Dout = torch.empty((nq, k), dtype=torch.float32, device=dev)
         Iout = torch.empty((nq, k), dtype=torch.int64, device=dev)
         if nq == 0:
             return Dout, Iout
-        ws = torch.empty(max(1, lib.cliora_knn_ip_workspace_bytes(nq, nk, D, k)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(1, _lib.fn('cliora_knn_ip_workspace_bytes')(nq, nk, D, k)), dtype=torch.uint8, device=dev)
         ldq = q.stride(0) if nq > 1 else D
         ldk = keys.stride(0) if nk > 1 else D
-        _lib.check(lib.cliora_knn_ip(nq, nk, D, k, _p(q), ldq, _p(keys) if nk else C.c_void_p(0), ldk, _p(Dout), k, _p(Iout), k,
-                                     _p(ws), ws.numel(), _stream()), 'cliora_knn_ip')
+        _lib.call('cliora_knn_ip', nq, nk, D, k, _p(q), ldq, _p(keys) if nk else C.c_void_p(0), ldk, _p(Dout), k, _p(Iout), k,
+                  _p(ws), ws.numel(), _stream())
     return Dout, Iout
 
 
@@ -375,14 +357,13 @@ class Neighbours(object):
 def knn_filter(I, D, example_ids, phrase_ids, k_top):
     """cliora_knn_filter on device tensors: (I_out, D_out, count)."""
     nq, kc = I.shape
-    lib = _native()
     dev = I.device
     with torch.cuda.device(dev):
         Io = torch.empty((nq, k_top), dtype=torch.int64, device=dev)
         Do = torch.empty((nq, k_top), dtype=torch.float32, device=dev)
         cnt = torch.empty(nq, dtype=torch.int32, device=dev)
-        _lib.check(lib.cliora_knn_filter(nq, kc, _p(I), I.stride(0) if nq else kc, _p(D), D.stride(0) if nq else kc, _p(example_ids),
-                                         _p(phrase_ids), example_ids.numel(), k_top, _p(Io), _p(Do), _p(cnt), _stream()), 'cliora_knn_filter')
+        _lib.call('cliora_knn_filter', nq, kc, _p(I), I.stride(0) if nq else kc, _p(D), D.stride(0) if nq else kc, _p(example_ids),
+                  _p(phrase_ids), example_ids.numel(), k_top, _p(Io), _p(Do), _p(cnt), _stream())
     return Io, Do, cnt
 
 

@@ -19,21 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _native():
-    lib = _lib.lib()
-    if not hasattr(lib, 'cliora_span_posteriors'):
-        raise _lib.ChartLibError('%s has no cliora_span_posteriors: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
-    return lib
+from ._lib import ptr_or_null as _p, stream as _stream
 
 
 def cell_id(L, level, pos):
@@ -67,7 +53,6 @@ def span_posteriors(diora, lengths=None, mbr=False, out=None):
     """cliora_span_posteriors on a chart module after its forward.  lengths: None (every sentence has L words) or an int32 tensor
     (B,) for a right-padded batch; mbr: also decode the MBR tree.  out: a contiguous int32 tensor (B, L-1, 2) on the chart's device
     to decode the MBR spans into (cliora_amd.evaluate: its output buffer).  -> SpanPosteriors."""
-    lib = _native()
     plan, wss = diora._plan, diora._wss
     B, L, Cc = plan.B, plan.L, plan.C
     nws = len(wss)
@@ -89,14 +74,14 @@ def span_posteriors(diora, lengths=None, mbr=False, out=None):
             else:
                 spans = torch.empty((B * nws, L - 1, 2), dtype=torch.int32, device=dev)
             split = torch.empty((B * nws, Cc), dtype=torch.int32, device=dev)
-        need = lib.cliora_span_posteriors_scratch_bytes(plan.handle)
+        need = _lib.fn('cliora_span_posteriors_scratch_bytes')(plan.handle)
         scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
         for i, ws in enumerate(wss):
             sl = slice(i * B, (i + 1) * B)
-            _lib.check(lib.cliora_span_posteriors(plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
-                                                  _p(marg[sl]), _p(log_z[sl]), _p(split[sl]) if mbr else None,
-                                                  _p(spans[sl]) if mbr else None, _p(scratch), C.c_void_p(status[i:i + 1].data_ptr()),
-                                                  _stream()), 'cliora_span_posteriors')
+            _lib.call('cliora_span_posteriors', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
+                      _p(marg[sl]), _p(log_z[sl]), _p(split[sl]) if mbr else None,
+                      _p(spans[sl]) if mbr else None, _p(scratch), C.c_void_p(status[i:i + 1].data_ptr()),
+                      _stream())
     return SpanPosteriors(marg, log_z, spans, split, status, L)
 
 

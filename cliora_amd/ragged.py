@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr_or_null as _p, stream as _stream
 
 MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L -- the both-pass padded chart (64 root levels in one mask word) and the default of max_len
 MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_len may be raised to for the inside-only entries (parse_ragged, encode_ragged)
@@ -35,21 +36,6 @@ MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_l
 # profiles/ragged_bench.json): the best of the sweep on 64 mixed sentences (5.3x the bucketed path), within
 # 2 % of the best on 1 000.
 DEFAULT_MAX_WASTE = 2.0
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _native():
-    lib = _lib.lib()
-    if not hasattr(lib, 'cliora_cky_spans_ragged'):
-        raise _lib.ChartLibError('%s has no cliora_cky_spans_ragged: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
-    return lib
 
 
 def work(length):
@@ -135,7 +121,6 @@ def cky_spans_ragged(diora, lengths, split_out=False, out=None):
     with (-1, -1) beyond each sentence's n - 1 rows; status (number of workspaces,) int32 counting the lengths outside [1, L], which
     the caller must check; split (B, C) int32, -1 at the leaves and outside each triangle.  Device tensors; nothing is synchronised.
     out: a contiguous int32 tensor (B, L-1, 2) on the chart's device to decode into (cliora_amd.evaluate: its output buffer)."""
-    lib = _native()
     plan, wss = diora._plan, diora._wss
     B, L = plan.B, plan.L
     nws = len(wss)
@@ -153,17 +138,15 @@ def cky_spans_ragged(diora, lengths, split_out=False, out=None):
         status = torch.empty(nws, dtype=torch.int32, device=dev)
         split = torch.empty((B * nws, plan.C), dtype=torch.int32, device=dev) if split_out else None
         for i, ws in enumerate(wss):
-            _lib.check(lib.cliora_cky_spans_ragged(plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[i * B:(i + 1) * B]),
-                                                   _p(split[i * B:(i + 1) * B]) if split_out else C.c_void_p(0),
-                                                   _p(spans[i * B:(i + 1) * B]), C.c_void_p(status[i:i + 1].data_ptr()), _stream()),
-                       'cliora_cky_spans_ragged')
+            _lib.call('cliora_cky_spans_ragged', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[i * B:(i + 1) * B]),
+                      _p(split[i * B:(i + 1) * B]) if split_out else C.c_void_p(0),
+                      _p(spans[i * B:(i + 1) * B]), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
     return (spans, status, split) if split_out else (spans, status)
 
 
 def root_rows(diora, lengths):
     """(B, D) inside vectors of the sentences' own root cells (n - 1, 0) of a padded chart: one cliora_phrase_gather launch over the
     device table (b, 0, lengths[b]), whose outside half is pointed at the inside chart and dropped (the outside pass is off)."""
-    lib = _native()
     ih = diora.chart.inside_h
     B, Cc, D = ih.shape
     L = diora._plan.L
@@ -173,8 +156,8 @@ def root_rows(diora, lengths):
         tab = torch.stack([torch.arange(B, dtype=torch.int32, device=dev), torch.zeros_like(n), n], 1).contiguous()
         out = torch.empty((B, 2 * D), dtype=torch.float32, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.cliora_phrase_gather(B, L, D, _p(ih), ih.stride(0), ih.stride(1), _p(ih), ih.stride(0), ih.stride(1), B, _p(tab),
-                                            0, _p(out), out.stride(0), 0, _p(status), _stream()), 'cliora_phrase_gather')
+        _lib.call('cliora_phrase_gather', B, L, D, _p(ih), ih.stride(0), ih.stride(1), _p(ih), ih.stride(0), ih.stride(1), B, _p(tab),
+                  0, _p(out), out.stride(0), 0, _p(status), _stream())
         bad = int(status.item())
     if bad:
         raise _lib.ChartLibError('%d sentence length(s) outside 1..%d' % (bad, L))

@@ -23,23 +23,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr_or_null as _p, stream as _stream
 
 MAX_K = 1024
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _native():
-    lib = _lib.lib()
-    if not hasattr(lib, 'cliora_neg_sample'):
-        raise _lib.ChartLibError('%s has no cliora_neg_sample: rebuild it (python -m cliora_amd.build)' % _lib.LIB_PATH)
-    return lib
 
 
 def _flat_ids(data):
@@ -57,13 +43,12 @@ def token_counts(ids, vocab_size):
     """cliora_token_counts: (V,) fp32 counts of a 1-D int64 CUDA tensor of ids; raises on ids outside [0, V)."""
     if vocab_size < 1:
         raise ValueError('vocab_size = %d must be positive' % vocab_size)
-    lib = _native()
     dev = ids.device
     with torch.cuda.device(dev):
         ids = ids.contiguous()
         counts = torch.empty(vocab_size, dtype=torch.float32, device=dev)
         bad = torch.empty((), dtype=torch.int64, device=dev)
-        _lib.check(lib.cliora_token_counts(ids.numel(), _p(ids), vocab_size, _p(counts), _p(bad), _stream()), 'cliora_token_counts')
+        _lib.call('cliora_token_counts', ids.numel(), _p(ids), vocab_size, _p(counts), _p(bad), _stream())
         n_bad = int(bad)
     if n_bad:
         raise ValueError('%d token id(s) outside [0, %d): the vocabulary does not cover the corpus' % (n_bad, vocab_size))
@@ -116,17 +101,16 @@ class NegativeSampler(object):
             raise ValueError('k = %d: the device sampler supports 1 <= k <= %d' % (k, MAX_K))
         if k > self.n_positive:
             raise ValueError('Fewer non-zero entries in p than size')
-        lib = _native()
         off = self.draws if offset is None else offset
         with torch.cuda.device(self.device):
             ids = torch.empty((S, k), dtype=torch.int64, device=self.device)
             E = torch.empty((S, k), dtype=torch.float64, device=self.device) if keys else None
-            nbytes = lib.cliora_neg_sample_workspace_bytes(self.V, S, k)
+            nbytes = _lib.fn('cliora_neg_sample_workspace_bytes')(self.V, S, k)
             if nbytes and (self._ws is None or self._ws.numel() < nbytes):
                 self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             ws = self._ws if nbytes else None
-            _lib.check(lib.cliora_neg_sample(self.V, _p(self.weights), self.n_positive, S, k, C.c_uint64(self.seed), C.c_uint64(off),
-                                             C.c_uint32(self.stream_id), _p(ids), _p(E), _p(ws), nbytes, _stream()), 'cliora_neg_sample')
+            _lib.call('cliora_neg_sample', self.V, _p(self.weights), self.n_positive, S, k, C.c_uint64(self.seed), C.c_uint64(off),
+                      C.c_uint32(self.stream_id), _p(ids), _p(E), _p(ws), nbytes, _stream())
         if offset is None:
             self.draws += S
         return (ids, E) if keys else ids

@@ -19,8 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .diora import DioraBase, Bilinear, Chart, _ptr, _stream, _param_struct, _grad_out
-from .index import Index
+from ._lib import ptr
+from .diora import DioraBase, Bilinear, _grad_out, chart_buffers
 
 
 class TreeLSTM(nn.Module):
@@ -39,43 +39,36 @@ class LSTMChartFunction(torch.autograd.Function):
     NAMES = ('lstm_w', 'lstm_u', 'lstm_b', 'in_mat', 'root_h', 'root_c', 'lstm_u_out', 'lstm_b_out', 'out_mat')
 
     @staticmethod
-    @_lib.on_device(lambda ctx, plan, holder, run_outside, x_span, *a: x_span)
     def forward(ctx, plan, holder, run_outside, x_span, *params):
         if not x_span.is_cuda:
             raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-        B, D, Cc = plan.B, plan.D, plan.C
+        D = plan.D
         x_span = x_span.contiguous().float()
         ptens = {n: p.detach().contiguous() for n, p in zip(LSTMChartFunction.NAMES, params) if p is not None}
-        dev = x_span.device
-        new = lambda w: torch.empty((B, Cc, w), device=dev, dtype=torch.float32)
-        ih, ic, is_, oh, oc, os_ = new(D), new(D), new(1), new(D), new(D), new(1)
-        ws = torch.empty(plan.fwd_bytes, device=dev, dtype=torch.uint8)
-        pst = _param_struct(ptens)
-        rc = _lib.lib().cliora_lstm_forward(plan.handle, C.byref(pst), _ptr(x_span), _ptr(ih), _ptr(ic), _ptr(is_), _ptr(oh), _ptr(oc),
-                                           _ptr(os_), _ptr(ws), plan.fwd_bytes, int(run_outside), _stream())
-        _lib.check(rc, 'cliora_lstm_forward')
+        with _lib.device_guard(x_span):
+            outs, ws, nbytes = chart_buffers(plan, x_span.device, 0, D, D, 1, D, D, 1)      # the per-split rows are part of fwd_bytes
+            pst = _lib.param_struct(ptens)
+            _lib.call('cliora_lstm_forward', plan.handle, C.byref(pst), ptr(x_span), *map(ptr, outs), ptr(ws), nbytes, int(run_outside),
+                      _lib.stream())
         ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens = plan, int(run_outside) & 1, ws, ptens
-        ctx.save_for_backward(x_span, ih, ic, is_, oh, oc, os_)
+        ctx.save_for_backward(x_span, *outs)
         ctx.set_materialize_grads(False)
         holder.clear()
         holder.append(ws)
-        return ih, ic, is_, oh, oc, os_
+        return tuple(outs)
 
     @staticmethod
-    @_lib.on_device(lambda ctx, *a: ctx.saved_tensors[0])
     def backward(ctx, *cots):
-        plan = ctx.plan
-        x_span, ih, ic, is_, oh, oc, os_ = ctx.saved_tensors
-        dev = x_span.device
-        cots = [g.contiguous().float() if g is not None else None for g in cots]
-        grads = {n: _grad_out(t) for n, t in ctx.ptens.items()}
-        d_x = torch.empty_like(x_span)
-        wsb = torch.empty(plan.bwd_bytes, device=dev, dtype=torch.uint8)
-        pst, gst = _param_struct(ctx.ptens), _param_struct(grads)
-        rc = _lib.lib().cliora_lstm_backward(plan.handle, C.byref(pst), _ptr(x_span), _ptr(ih), _ptr(ic), _ptr(is_), _ptr(oh), _ptr(oc),
-                                            _ptr(os_), *[_ptr(g) for g in cots], _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb),
-                                            plan.bwd_bytes, _ptr(d_x), C.byref(gst), ctx.run_outside, _stream())
-        _lib.check(rc, 'cliora_lstm_backward')
+        plan, saved = ctx.plan, ctx.saved_tensors
+        x_span = saved[0]
+        with _lib.device_guard(x_span):
+            cots = [g.contiguous().float() if g is not None else None for g in cots]
+            grads = {n: _grad_out(t) for n, t in ctx.ptens.items()}
+            d_x = torch.empty_like(x_span)
+            wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
+            pst, gst = _lib.param_struct(ctx.ptens), _lib.param_struct(grads)
+            _lib.call('cliora_lstm_backward', plan.handle, C.byref(pst), *map(ptr, saved), *map(ptr, cots), ptr(ctx.ws), plan.fwd_bytes,
+                      ptr(wsb), plan.bwd_bytes, ptr(d_x), C.byref(gst), ctx.run_outside, _lib.stream())
         return (None, None, None, d_x) + tuple(grads.get(n) for n in LSTMChartFunction.NAMES)
 
 
@@ -94,32 +87,27 @@ class DioraTreeLSTM(DioraBase):
         self.root_vector_out_h = nn.Parameter(torch.empty(self.size))
         self.root_vector_out_c = nn.Parameter(torch.empty(self.size))
 
-    def forward(self, x_span, x_word=None, obj_embed_span=None, obj_embed_word=None):
-        if self.index is None:
-            self.index = Index(cuda=self.is_cuda)
-        self.reset()
+    plan_arch = 1
+
+    def _check_long(self, L, needs_grad, hooks):
+        pass            # a TreeLSTM plan refuses L > 64 itself (_lib.Plan)
+
+    def _regions(self, obj_embed_span):
         if obj_embed_span is not None:
             raise NotImplementedError('DioraTreeLSTM is text-only')
-        B, L, D = x_span.shape
-        assert D == self.size
-        dev_index = x_span.device.index if x_span.is_cuda else -1
-        plan = _lib.get_plan(B, L, D, self.share, self.normalize, 0, dev_index, arch=1)
+        return 0
+
+    def _param_tensors(self):
         cf, of = self.inside_compose_func, self.outside_compose_func
         outer = (None, None, None) if self.share else (of.U, of.B, self.outside_score_func.mat)
-        holder = []
-        # eval / torch.no_grad without a hook override: the per-split rows h_n, c_n are not written (flag bits of cliora_chart_forward)
-        params = (cf.W, cf.U, cf.B, self.inside_score_func.mat, self.root_vector_out_h, self.root_vector_out_c) + outer
-        needs_grad = torch.is_grad_enabled() and (x_span.requires_grad or any(t is not None and t.requires_grad for t in params))
-        hooks = self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook')
-        flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
-        ih, ic, is_, oh, oc, os_ = LSTMChartFunction.apply(plan, holder, flags, x_span, cf.W, cf.U, cf.B,
-                                                           self.inside_score_func.mat, self.root_vector_out_h, self.root_vector_out_c, *outer)
-        ch = Chart()
-        ch.inside_h, ch.inside_c, ch.inside_s, ch.outside_h, ch.outside_c, ch.outside_s = ih, ic, is_, oh, oc, os_
-        self.chart = ch
-        self._wss, self._plan = holder, plan
-        self.init_with_batch(ih[:, :L], ic[:, :L])
+        return (cf.W, cf.U, cf.B, self.inside_score_func.mat, self.root_vector_out_h, self.root_vector_out_c) + outer
+
+    def _run_chart(self, plan, holder, flags, x_span, obj_embed_span, params):
+        # eval / torch.no_grad without a hook override: the per-split rows h_n, c_n are not written (flag bits of cliora_chart_forward).
         # hooks: per-split h (the pair rows the backward keeps anyway) and scores, in the reference's layout and order
         # (diora.py:331, 398); the per-split cell states are not kept: c is passed as zeros, as for DioraMLP
-        self._serve_hooks(L)
-        return None
+        ih, ic, is_, oh, oc, os_ = LSTMChartFunction.apply(plan, holder, flags, x_span, *params)
+        return ih, is_, oh, os_, ic, oc
+
+    def _run_ragged(self, plan, holder, x_span, obj_embed_span, params, ragged):
+        raise NotImplementedError('DioraTreeLSTM has no padded chart of mixed lengths')

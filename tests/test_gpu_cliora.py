@@ -222,3 +222,46 @@ def test_cliora_wavefront_is_bitwise_the_sequential_order(B, L, D, R, share, mfm
                 assert torch.equal(cur[2][n], res[2][n]), n
     finally:
         _lib.set_wavefront(prev)
+
+
+def test_region_max_backward_computes_the_gradients_its_inputs_need():
+    """The one region-max node hands cliora_vl_scores_max_backward NULL for the output no input needs.  A region matrix without a
+    gradient (d_obj NULL) leaves the values, the regions and the gradients of x_span and of the chart parameters bit for bit those of
+    the run in which it has one; and its gradient is bit for bit the same from the one node (no lane) and from the rows node on the
+    current stream plus the region-matrix node on the caller lane."""
+    from cliora_amd import _lib
+    from cliora_amd.cliora import DioraMLP
+    B, L, D, R = 2, 4, 16, 5
+    C = L * (L + 1) // 2
+    torch.manual_seed(13)
+    m = DioraMLP(D, outside=True, normalize='unit', compress=False, share=True).cuda().train()
+    for p in m.parameters():
+        torch.nn.init.normal_(p, std=0.3)
+    m.dropout_mask = (torch.rand(B, C, R, device='cuda') > 0.1).float() / 0.9
+    g = torch.Generator().manual_seed(17)
+    data = [torch.randn(sh, generator=g).cuda() for sh in ((B, L, D), (B, L, D), (B, R, D), (B, R, D))]
+    w = torch.randn(B, B, C, generator=g).cuda()
+
+    def run(obj_grad, lane):
+        x, xw, obj, ow = (t.clone() for t in data)
+        x.requires_grad_(True)
+        obj.requires_grad_(obj_grad)
+        for p in m.parameters():
+            p.grad = None
+        m.word_lane = lane
+        m(x, xw, obj, ow)
+        r = m.all_atten_score.max(-1)
+        (r.values * w).sum().backward()         # the region matrix's gradient: the chart's and the region max's, two addends in either order
+        torch.cuda.synchronize()
+        pg = {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+        return r.values.detach().clone(), r.indices.clone(), x.grad.clone(), pg, (obj.grad.clone() if obj_grad else None)
+
+    with_grad, without, on_lane = run(True, None), run(False, None), run(True, _lib.side_stream(torch.device('cuda', 0)))
+    m.word_lane = None
+    assert with_grad[3] and with_grad[4] is not None and float(with_grad[4].abs().max()) > 0
+    for other in (without, on_lane):
+        assert torch.equal(with_grad[0], other[0]) and torch.equal(with_grad[1], other[1]) and torch.equal(with_grad[2], other[2])
+        assert sorted(with_grad[3]) == sorted(other[3])
+        for n in with_grad[3]:
+            assert torch.equal(with_grad[3][n], other[3][n]), n
+    assert torch.equal(with_grad[4], on_lane[4])
