@@ -1,4 +1,4 @@
-// C ABI, core unit: plan management, error / profiling plumbing, arithmetic mode, hook views and the CKY decode.
+// C ABI, core unit: plan management, error / profiling plumbing, arithmetic mode and hook views.
 // See include/cliora_chart.h for the contract and the reference lines it replaces.
 #include <set>
 #include <utility>
@@ -268,7 +268,7 @@ int cliora_plan_ready(cliora_plan* plan, hipStream_t st) {
     return CLIORA_OK;
 }
 
-// ------------------------------------------------------------------ hooks / CKY
+// ------------------------------------------------------------------ hooks
 extern "C" int cliora_inside_pair_states(const cliora_plan* plan, void* fwd_ws, int level, const float** scores, const float** h,
                                          size_t* rows, size_t* ldh) {
     if (!plan || !fwd_ws || !scores || !h || !rows || !ldh) return fail(CLIORA_EINVAL, "NULL argument");
@@ -293,109 +293,6 @@ extern "C" int cliora_outside_pair_states(const cliora_plan* plan, void* fwd_ws,
     *rows = (size_t)p.B * (p.L - level) * (p.L - level - 1);
     *ldh = (size_t)p.Dp;
     return CLIORA_OK;
-}
-
-// One wavefront per sentence.  val[] (chart of best scores) lives in LDS; leaves start at 1
-// (analysis/cky.py:24-25, 39).  Candidate = (val_l + val_r) + (s_n - max_n s) in fp32, in that
-// order (cky.py:83, utils.py:89-90); argmax keeps the first maximum (cky.py:86).
-// One workgroup of CKY_WAVES wavefronts per sentence (round 5: was one wavefront walking every cell in turn -- 190 dependent steps at
-// L 20; the cells of a level are independent, so wave w takes the positions w, w + CKY_WAVES, ... and the level ends with one barrier).
-// LONG: a long plan (plan.hpp: L <= 128, up to 127 splits per cell) -- a lane takes the splits `lane` and `lane + 64`, the earlier one on
-// a tie, then the same butterfly.  LDS: 8 C + 12 (L + 1) bytes = 67.6 KB at L 128 (C = 8 256), inside the CU's 160 KB, so the value
-// table stays in LDS; above 64 KB the launch raises the kernel's dynamic-LDS limit (cliora_ensure_max_lds).
-constexpr int CKY_WAVES = 4;
-template <bool LONG = false>
-__global__ __launch_bounds__(CKY_WAVES * 64) void cky_kernel(int L, int C, const int32_t* __restrict__ level_off_tab_a, const int32_t* __restrict__ pair_a,
-                                                 const int32_t* __restrict__ pair_b, const int32_t* __restrict__ lvl_base, int B,
-                                                 const float* __restrict__ Sp, int32_t* __restrict__ split, int32_t* __restrict__ spans) {
-    extern __shared__ float val[];                 // C best scores, then C chosen splits
-    int32_t* bsp = reinterpret_cast<int32_t*>(val + C);
-    (void)level_off_tab_a;
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = threadIdx.x; c < C; c += CKY_WAVES * 64) val[c] = 1.f;
-    for (int c = threadIdx.x; c < L; c += CKY_WAVES * 64) { bsp[c] = -1; if (split) split[(size_t)b * C + c] = -1; }
-    __syncthreads();
-    int off = L;   // cell id of (level 1, pos 0)
-    for (int level = 1; level < L; ++level) {
-        const int Lc = L - level, N = level;
-        for (int pos = wave; pos < Lc; pos += CKY_WAVES) {          // operands live on lower levels: final since the last barrier
-            const int loc = lvl_base[level] + pos * N;
-            const size_t row0 = (size_t)B * lvl_base[level] + ((size_t)b * Lc + pos) * N;
-            const bool an = lane < N;
-            const float s = an ? Sp[row0 + lane] : -INFINITY;
-            const float smax = wave_max(s);
-            float cand = -INFINITY;
-            if (an) cand = (val[pair_a[loc + lane]] + val[pair_b[loc + lane]]) + (s - smax);
-            float best = cand; int bi = an ? lane : 0x7fffffff;
-            if constexpr (LONG) {
-                const bool an1 = lane + 64 < N;
-                const float s1 = an1 ? Sp[row0 + lane + 64] : -INFINITY;
-                const float smax2 = wave_max(fmaxf(s, s1));
-                best = -INFINITY;
-                if (an) best = (val[pair_a[loc + lane]] + val[pair_b[loc + lane]]) + (s - smax2);
-                if (an1) {
-                    const float c1 = (val[pair_a[loc + lane + 64]] + val[pair_b[loc + lane + 64]]) + (s1 - smax2);
-                    if (c1 > best) { best = c1; bi = lane + 64; }
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-                if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-            }
-            if (lane == 0) { val[off + pos] = best; bsp[off + pos] = bi; if (split) split[(size_t)b * C + off + pos] = bi; }
-        }
-        __syncthreads();
-        off += Lc;
-    }
-    // The tree's constituent spans (start, end), children before parents, left subtree first: the order of the REDUCE actions, i.e. what
-    // the reference gets from get_spans(get_actions(tree)) (cliora/analysis/utils.py:3-49) -- L - 1 spans per sentence, the root last.
-    // One lane walks the L - 1 internal nodes with an explicit stack (level, pos, phase) in LDS.
-    if (spans && threadIdx.x == 0 && L > 1) {
-        int32_t* stk = bsp + C;                     // 3 * L ints
-        auto cell = [&](int level, int pos) { const int rem = L - level; return C - rem * (rem + 1) / 2 + pos; };
-        int sp = 0, cnt = 0;
-        stk[0] = L - 1; stk[1] = 0; stk[2] = 0;
-        int32_t* out = spans + (size_t)b * (L - 1) * 2;
-        while (sp >= 0) {
-            const int level = stk[3 * sp], pos = stk[3 * sp + 1], phase = stk[3 * sp + 2];
-            if (level == 0) { --sp; continue; }
-            const int n = bsp[cell(level, pos)];
-            if (phase == 0) { stk[3 * sp + 2] = 1; ++sp; stk[3 * sp] = n; stk[3 * sp + 1] = pos; stk[3 * sp + 2] = 0; }
-            else if (phase == 1) { stk[3 * sp + 2] = 2; ++sp; stk[3 * sp] = level - n - 1; stk[3 * sp + 1] = pos + n + 1; stk[3 * sp + 2] = 0; }
-            else { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; ++cnt; --sp; }
-        }
-    }
-}
-
-static int launch_cky(cliora_plan* plan, void* fwd_ws, int32_t* split_out, int32_t* spans_out, void* stream, const char* who) {
-    if (!plan || !fwd_ws) return fail(CLIORA_EINVAL, "NULL argument");
-    if (!plan->uploaded) return fail(CLIORA_EINVAL, std::string(who) + " called before forward");
-    OKR(cliora_plan_ready(plan, (hipStream_t)stream));
-    Plan& p = plan->p;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)p.C * (sizeof(float) + sizeof(int32_t)) + (size_t)3 * (p.L + 1) * sizeof(int32_t);
-    if (p.is_long()) {
-        if (lds > 64 * 1024) OKR(cliora_ensure_max_lds((const void*)cky_kernel<true>));
-        hipLaunchKernelGGL(cky_kernel<true>, dim3(p.B), dim3(CKY_WAVES * 64), lds, st, p.L, p.C, (const int32_t*)nullptr,
-                           p.d_tables + p.dev.pair_a_in, p.d_tables + p.dev.pair_b_in, p.d_tables + p.dev.lvl_base_in, p.B,
-                           (const float*)fwd_ws + p.fwd.sp, split_out, spans_out);
-    } else
-    hipLaunchKernelGGL(cky_kernel<false>, dim3(p.B), dim3(CKY_WAVES * 64), lds, st, p.L, p.C, (const int32_t*)nullptr,
-                       p.d_tables + p.dev.pair_a_in, p.d_tables + p.dev.pair_b_in, p.d_tables + p.dev.lvl_base_in, p.B,
-                       (const float*)fwd_ws + p.fwd.sp, split_out, spans_out);
-    LAUNCHOK("cky_kernel");
-    return CLIORA_OK;
-}
-
-extern "C" int cliora_cky_decode(cliora_plan* plan, void* fwd_ws, int32_t* split_out, void* stream) {
-    if (!split_out) return fail(CLIORA_EINVAL, "NULL argument");
-    return launch_cky(plan, fwd_ws, split_out, nullptr, stream, "cky");
-}
-
-extern "C" int cliora_cky_spans(cliora_plan* plan, void* fwd_ws, int32_t* split_out, int32_t* spans_out, void* stream) {
-    if (!spans_out) return fail(CLIORA_EINVAL, "NULL argument");
-    return launch_cky(plan, fwd_ws, split_out, spans_out, stream, "cky_spans");
 }
 
 extern "C" const char* cliora_last_error(void) { return g_cliora_err.c_str(); }

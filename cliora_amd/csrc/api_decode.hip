@@ -1,0 +1,74 @@
+// C ABI, decode unit: the best tree (CKY), and the span posteriors, log-partition and MBR tree, from the per-split scores of the last
+// forward -- of every sentence of a chart, or of each sentence's own triangle of a right-padded chart.  See include/cliora_chart.h for
+// the contract, decode_kernels.hpp for the CKY kernel and posterior_kernels.hpp for the sum-product model.
+// TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
+#include "api_common.hpp"
+#include "decode_kernels.hpp"
+#include "posterior_kernels.hpp"
+
+// The one launch of a decode kernel: a workgroup of `waves` wavefronts per sentence, lds_of(L, C) bytes of dynamic LDS, the arguments
+// every decode kernel starts with, then the kernel's own.  f(Bool<LONG>, go) calls go(name, the kernel's instance, its own arguments...).
+// who: the entry's name in the "called before forward" message.  status: zeroed first when given.
+template <class F>
+static int launch_decode(cliora_plan* plan, void* fwd_ws, const char* who, int waves, size_t (*lds_of)(int, int), const int32_t* lengths,
+                         int32_t* split, int32_t* spans, int32_t* status, void* stream, F&& f) {
+    if (!plan->uploaded) return fail(CLIORA_EINVAL, std::string(who) + " called before forward");
+    hipStream_t st = (hipStream_t)stream;
+    OKR(cliora_plan_ready(plan, st));
+    if (status) HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    const Plan& p = plan->p;
+    if (p.L <= 1) spans = nullptr;                   // one word: no constituent, and no row to write
+    const size_t lds = lds_of(p.L, p.C);
+    return with_long(p.is_long(), [&](auto LONG) {
+        return f(LONG, [&](const char* name, auto* kernel, auto... own) {
+            if (lds > 64 * 1024) OKR(cliora_ensure_max_lds((const void*)kernel));
+            hipLaunchKernelGGL(kernel, dim3(p.B), dim3(waves * 64), lds, st, p.L, p.C, p.d_tables + p.dev.lvl_base_in, p.B,
+                               (const float*)fwd_ws + p.fwd.sp, lengths, split, spans, status, own...);
+            LAUNCHOK(name);
+            return CLIORA_OK;
+        });
+    });
+}
+
+static int launch_cky(cliora_plan* plan, void* fwd_ws, const char* who, const int32_t* lengths, int32_t* split_out, int32_t* spans_out,
+                      int32_t* status, void* stream) {
+    return launch_decode(plan, fwd_ws, who, CKY_WAVES, cky_lds, lengths, split_out, spans_out, status, stream, [&](auto LONG, auto&& go) {
+        const Plan& p = plan->p;
+        return go("cky_kernel", cky_kernel<decltype(LONG)::value>, p.d_tables + p.dev.pair_a_in, p.d_tables + p.dev.pair_b_in);
+    });
+}
+
+extern "C" int cliora_cky_decode(cliora_plan* plan, void* fwd_ws, int32_t* split_out, void* stream) {
+    if (!plan || !fwd_ws || !split_out) return fail(CLIORA_EINVAL, "NULL argument");
+    return launch_cky(plan, fwd_ws, "cky", nullptr, split_out, nullptr, nullptr, stream);
+}
+
+extern "C" int cliora_cky_spans(cliora_plan* plan, void* fwd_ws, int32_t* split_out, int32_t* spans_out, void* stream) {
+    if (!plan || !fwd_ws || !spans_out) return fail(CLIORA_EINVAL, "NULL argument");
+    return launch_cky(plan, fwd_ws, "cky_spans", nullptr, split_out, spans_out, nullptr, stream);
+}
+
+extern "C" int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, int32_t* split_out, int32_t* spans_out,
+                                       int32_t* status, void* stream) {
+    if (!plan || !fwd_ws || !lengths || !status) return fail(CLIORA_EINVAL, "cliora_cky_spans_ragged: NULL argument");
+    if (!spans_out && plan->p.L > 1) return fail(CLIORA_EINVAL, "cliora_cky_spans_ragged: NULL spans_out");
+    return launch_cky(plan, fwd_ws, "cky_spans_ragged", lengths, split_out, spans_out, status, stream);
+}
+
+// Every table of the kernel fits the CU's LDS up to L = 128 (posterior_kernels.hpp), so no plan needs device scratch today; the query
+// is part of the contract so that a caller sizes the buffer as it sizes every other one.
+extern "C" size_t cliora_span_posteriors_scratch_bytes(const cliora_plan* plan) {
+    (void)plan;
+    return 0;
+}
+
+extern "C" int cliora_span_posteriors(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, float* marginals, float* log_z,
+                                      int32_t* mbr_split, int32_t* mbr_spans, void* scratch, int32_t* status, void* stream) {
+    (void)scratch;
+    if (!plan || !fwd_ws || !marginals || !log_z) return fail(CLIORA_EINVAL, "cliora_span_posteriors: NULL argument");
+    if (lengths && !status) return fail(CLIORA_EINVAL, "cliora_span_posteriors: lengths given without status");
+    return launch_decode(plan, fwd_ws, "span_posteriors", POST_WAVES, span_posteriors_lds, lengths, mbr_split, mbr_spans, status, stream,
+                         [&](auto LONG, auto&& go) {
+                             return go("span_posteriors_kernel", span_posteriors_kernel<decltype(LONG)::value>, marginals, log_z);
+                         });
+}

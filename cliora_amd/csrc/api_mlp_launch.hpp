@@ -33,11 +33,6 @@ template <class F>
 static int with_parts2(int SP, F&& f) {
     return with_int<1, 2, 4>(SP, f);
 }
-// f(Bool<LONG>): a long plan (plan.hpp), whose riding scores take two splits per lane (score_cell<true>)
-template <class F>
-static int with_long(bool lng, F&& f) {
-    return lng ? f(Bool<true>{}) : f(Bool<false>{});
-}
 
 // ------------------------------------------------------------------ fused level kernels (level_kernels.hpp)
 // LDS of the compose kernels: the column block's weight image (split-bf16: S dwords per column; exact fp32: K) + reduction slots

@@ -1,0 +1,113 @@
+// Tree decode from the per-split scores of the last forward (include/cliora_chart.h; the entry points are in api_decode.hip): the CKY
+// kernel and the pieces it shares with the MBR tail of span_posteriors_kernel (posterior_kernels.hpp) -- the row load, the
+// first-maximum reduction and the span walk, each written once.
+//
+// Cell (level, pos) spans words [pos, pos + level]; split k pairs left (k, pos) with right (level - k - 1, pos + k + 1).  Sentences
+// of different lengths share one right-padded chart of length L: the inside pass is prefix-closed -- cell (level, pos) with
+// pos + level < n reads only cells of words [0, n) -- so the per-split scores of a sentence's own triangle in the padded chart are
+// those of a chart of length n, and a sentence is decoded from that triangle with the cell ids and pair tables of the padded chart.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "chart_kernels.hpp"
+
+namespace cliora {
+
+// cell id of (level, pos) in a chart of length L with C cells
+__device__ __forceinline__ int chart_cell(int L, int C, int level, int pos) {
+    const int rem = L - level;
+    return C - rem * (rem + 1) / 2 + pos;
+}
+
+// This lane's per-split scores of a cell with N splits (row: the cell's first): s = row[lane], and s1 = row[lane + 64] when LONG (a
+// long plan, 64 < L <= 128: up to 127 splits per cell, two per lane); -inf where the cell has no such split.  -> their wave maximum.
+template <bool LONG>
+__device__ __forceinline__ float load_split_scores(const float* __restrict__ row, int N, int lane, float& s, float& s1) {
+    s = lane < N ? row[lane] : -INFINITY;
+    s1 = LONG && lane + 64 < N ? row[lane + 64] : -INFINITY;
+    return wave_max(LONG ? fmaxf(s, s1) : s);
+}
+
+// (best, bi) of every lane <- the wave's maximum value and the smallest split index that holds it: the first maximum wins.
+__device__ __forceinline__ void wave_first_max(float& best, int& bi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+}
+
+// The tree's constituent spans (start, end) from the sentence's root (n - 1, 0), n > 1, children before parents, left subtree first:
+// the order of the REDUCE actions, i.e. what the reference gets from get_spans(get_actions(tree)) (cliora/analysis/utils.py:3-49) --
+// n - 1 spans, the root last.  One lane walks the n - 1 internal nodes with an explicit stack (level, pos, phase) of 3 (L + 1) ints.
+// bsp: the chosen split of every cell of the triangle, by cell id.
+__device__ __forceinline__ void emit_spans(const int32_t* bsp, int L, int C, int n, int32_t* stk, int32_t* __restrict__ out) {
+    int sp = 0, cnt = 0;
+    stk[0] = n - 1; stk[1] = 0; stk[2] = 0;
+    while (sp >= 0) {
+        const int level = stk[3 * sp], pos = stk[3 * sp + 1], phase = stk[3 * sp + 2];
+        if (level == 0) { --sp; continue; }
+        const int k = bsp[chart_cell(L, C, level, pos)];
+        if (phase == 0) { stk[3 * sp + 2] = 1; ++sp; stk[3 * sp] = k; stk[3 * sp + 1] = pos; stk[3 * sp + 2] = 0; }
+        else if (phase == 1) { stk[3 * sp + 2] = 2; ++sp; stk[3 * sp] = level - k - 1; stk[3 * sp + 1] = pos + k + 1; stk[3 * sp + 2] = 0; }
+        else { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; ++cnt; --sp; }
+    }
+}
+
+// Best binary tree per sentence.  val[] (chart of best scores) lives in LDS; leaves start at 1 (analysis/cky.py:24-25, 39).
+// Candidate = (val_l + val_r) + (s_k - max_k s) in fp32, in that order (cky.py:83, utils.py:89-90); argmax keeps the first maximum
+// (cky.py:86).  One workgroup of CKY_WAVES wavefronts per sentence: the cells of a level are independent, so wave w takes the positions
+// w, w + CKY_WAVES, ... and the level ends with one barrier.
+// lengths (B) or NULL (every sentence has L words; status is NULL then too).  split (B, C) or NULL: chosen split per cell, -1 at the
+// leaves and outside the sentence's triangle.  spans (B, L-1, 2) or NULL: the n - 1 constituents in emit_spans' order; (-1, -1) beyond.
+// A length outside [1, L]: every row -1, one count in *status, no chart read.
+// LDS: C best scores, C chosen splits, the walk stack -- sized by the padded chart, indexed by its cell ids: 8 C + 12 (L + 1) bytes =
+// 67.6 KB at L 128 (C = 8 256), inside the CU's 160 KB; above 64 KB the launch raises the kernel's dynamic-LDS limit.
+constexpr int CKY_WAVES = 4;
+template <bool LONG = false>
+static __global__ __launch_bounds__(CKY_WAVES * 64) void cky_kernel(int L, int C, const int32_t* __restrict__ lvl_base, int B,
+                                                                    const float* __restrict__ Sp, const int32_t* __restrict__ lengths,
+                                                                    int32_t* __restrict__ split, int32_t* __restrict__ spans,
+                                                                    int32_t* __restrict__ status, const int32_t* __restrict__ pair_a,
+                                                                    const int32_t* __restrict__ pair_b) {
+    extern __shared__ float val[];
+    int32_t* bsp = reinterpret_cast<int32_t*>(val + C);
+    constexpr int NT = CKY_WAVES * 64;
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int n = lengths ? lengths[b] : L;
+    if (n < 1 || n > L) { n = 0; if (threadIdx.x == 0) atomicAdd(status, 1); }
+    if (split) for (int c = threadIdx.x; c < C; c += NT) split[(size_t)b * C + c] = -1;
+    if (spans) for (int i = threadIdx.x; i < 2 * (L - 1); i += NT) spans[(size_t)b * (L - 1) * 2 + i] = -1;
+    for (int c = threadIdx.x; c < n; c += NT) { val[c] = 1.f; bsp[c] = -1; }      // the sentence's leaves
+    __syncthreads();                                 // also orders the -1 fill before the stores below (same workgroup, same addresses)
+    int off = L;                                     // cell id of (level 1, pos 0) in the padded chart
+    for (int level = 1; level < n; ++level) {
+        const int Lc = L - level, N = level, mine = n - level;     // row geometry: the padded chart's; positions: the sentence's
+        for (int pos = wave; pos < mine; pos += CKY_WAVES) {       // operands live on lower levels: final since the last barrier
+            const int loc = lvl_base[level] + pos * N;
+            float s, s1;
+            const float smax = load_split_scores<LONG>(Sp + (size_t)B * lvl_base[level] + ((size_t)b * Lc + pos) * N, N, lane, s, s1);
+            float best = -INFINITY; int bi = lane < N ? lane : 0x7fffffff;
+            if (lane < N) best = (val[pair_a[loc + lane]] + val[pair_b[loc + lane]]) + (s - smax);
+            if constexpr (LONG) {
+                if (lane + 64 < N) {
+                    const float c1 = (val[pair_a[loc + lane + 64]] + val[pair_b[loc + lane + 64]]) + (s1 - smax);
+                    if (c1 > best) { best = c1; bi = lane + 64; }
+                }
+            }
+            wave_first_max(best, bi);
+            if (lane == 0) { val[off + pos] = best; bsp[off + pos] = bi; if (split) split[(size_t)b * C + off + pos] = bi; }
+        }
+        __syncthreads();
+        off += Lc;
+    }
+    if (spans && threadIdx.x == 0 && n > 1) emit_spans(bsp, L, C, n, bsp + C, spans + (size_t)b * (L - 1) * 2);
+}
+
+// Dynamic LDS of cky_kernel for a chart of length L.
+static inline size_t cky_lds(int L, int C) {
+    return (size_t)C * (sizeof(float) + sizeof(int32_t)) + (size_t)3 * (L + 1) * sizeof(int32_t);
+}
+
+}  // namespace cliora

@@ -28,6 +28,11 @@ template <class F>
 static auto with_colsum(bool colsum, F&& f) {
     return colsum ? f(Bool<true>{}) : f(Bool<false>{});
 }
+// f(Bool<LONG>): a long plan (plan.hpp), whose cells take two splits per lane (score_cell<true>, cky_kernel<true>)
+template <class F>
+static int with_long(bool lng, F&& f) {
+    return lng ? f(Bool<true>{}) : f(Bool<false>{});
+}
 // the widest of {5, 4, 2, 1} sixteen-wide tiles per block that divides the tile count
 static int pick_tiles(int ntiles16) {
     for (int t : {5, 4, 2, 1}) if (ntiles16 % t == 0) return t;

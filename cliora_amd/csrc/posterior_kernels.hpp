@@ -6,7 +6,8 @@
 //   inside    al[leaf] = 0,  al[cell] = logsumexp_k(al[left] + al[right] + r[cell, k]),  log_z = al[(n - 1, 0)]
 //   outside   be[(n - 1, 0)] = 0,  be[cell] = logsumexp over its n - 1 - level uses of be[parent] + al[sibling] + r[parent, split]
 //   posterior mu[cell] = exp(al + be - log_z)
-//   MBR       v[leaf] = 0,  v[cell] = max_k(v[left] + v[right]) + mu[cell] in fp32, first maximum wins; the walk of cky_kernel.
+//   MBR       v[leaf] = 0,  v[cell] = max_k(v[left] + v[right]) + mu[cell] in fp32, first maximum wins; the walk of cky_kernel
+//             (wave_first_max and emit_spans of decode_kernels.hpp, which cky_kernel calls too).
 // Gather form throughout: a wavefront owns a cell and sums what the cell reads, a lane per split (inside, MBR) or per use (outside),
 // a second one at lane + 64 in the LONG instance (64 < L <= 128); no cell is ever added into.  The uses of a cell are closed forms
 // (long plans build no use lists):
@@ -22,7 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "chart_kernels.hpp"
+#include "decode_kernels.hpp"
 
 namespace cliora {
 
@@ -52,16 +53,17 @@ __device__ __forceinline__ post_t post_wave_lse(post_t t0, post_t t1) {
 
 // One workgroup per sentence; POST_WAVES wavefronts, one cell each per turn, one barrier per level of each pass.
 // lengths (B) or NULL (every sentence has L words).  marg (B, C): mu in the cell order of inside_s, exactly 0 outside the sentence's
-// triangle; log_z (B).  split (B, C) / spans (B, L-1, 2), either NULL: the MBR tree in cky_ragged_kernel's layout (-1 at the leaves
+// triangle; log_z (B).  split (B, C) / spans (B, L-1, 2), either NULL: the MBR tree in cky_kernel's layout (-1 at the leaves
 // and outside the triangle; n - 1 spans, children before parents, (-1, -1) beyond).  A length outside [1, L]: mu = 0, log_z = 0,
 // every row -1, one count in *status, no chart read.
 // LDS: al (C), be (C) post_t; lvl (L) ints; walk stack 3 (L + 1) ints.
 template <bool LONG = false>
 static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel(int L, int C, const int32_t* __restrict__ lvl_base, int B,
                                                                                  const float* __restrict__ Sp,
-                                                                                 const int32_t* __restrict__ lengths, float* marg,
-                                                                                 float* __restrict__ log_z, int32_t* __restrict__ split,
-                                                                                 int32_t* __restrict__ spans, int32_t* __restrict__ status) {
+                                                                                 const int32_t* __restrict__ lengths,
+                                                                                 int32_t* __restrict__ split, int32_t* __restrict__ spans,
+                                                                                 int32_t* __restrict__ status, float* marg,
+                                                                                 float* __restrict__ log_z) {
     extern __shared__ __attribute__((aligned(16))) unsigned char post_smem[];
     post_t* al = reinterpret_cast<post_t*>(post_smem);
     post_t* be = al + C;
@@ -72,7 +74,7 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int n = lengths ? lengths[b] : L;
     if (n < 1 || n > L) { n = 0; if (threadIdx.x == 0) atomicAdd(status, 1); }
-    auto coff = [&](int level) { const int rem = L - level; return C - rem * (rem + 1) / 2; };     // cell id of (level, 0)
+    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
     auto row_of = [&](int level, int pos) { return (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level; };
     float* mu = marg + (size_t)b * C;
     for (int c = threadIdx.x; c < C; c += NT) mu[c] = 0.f;
@@ -88,11 +90,9 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel
     for (int level = 1; level < n; ++level) {
         const int off = coff(level), mine = n - level;
         for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const size_t row0 = row_of(level, pos);
             const bool an = lane < level, an1 = LONG && lane + 64 < level;
-            const float s = an ? Sp[row0 + lane] : -INFINITY;
-            const float s1 = an1 ? Sp[row0 + lane + 64] : -INFINITY;
-            const float smax = wave_max(LONG ? fmaxf(s, s1) : s);
+            float s, s1;
+            const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
             post_t t0 = ninf, t1 = ninf;
             if (an) t0 = al[coff(lane) + pos] + al[coff(level - lane - 1) + pos + lane + 1] + ((post_t)s - (post_t)smax);
             if (an1) t1 = al[coff(lane + 64) + pos] + al[coff(level - lane - 65) + pos + lane + 65] + ((post_t)s1 - (post_t)smax);
@@ -122,10 +122,8 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel
                 bt = post_wave_lse<LONG>(t0, t1);
             }
             if (level > 0) {                                                // what the children read: be - rowmax
-                const size_t row0 = row_of(level, pos);
-                const float s = lane < level ? Sp[row0 + lane] : -INFINITY;
-                const float s1 = LONG && lane + 64 < level ? Sp[row0 + lane + 64] : -INFINITY;
-                const float smax = wave_max(LONG ? fmaxf(s, s1) : s);
+                float s, s1;
+                const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
                 if (lane == 0) be[off + pos] = bt - (post_t)smax;
             }
             if (lane == 0) mu[off + pos] = (float)exp(al[off + pos] + bt - lz);
@@ -151,29 +149,12 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel
                     if (c1 > best) { best = c1; bi = lane + 64; }
                 }
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
-                if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-            }
+            wave_first_max(best, bi);
             if (lane == 0) { val[off + pos] = best + mu[off + pos]; bsp[off + pos] = bi; if (split) split[(size_t)b * C + off + pos] = bi; }
         }
         __syncthreads();
     }
-    // Spans in the order of cky_kernel's walk, from the sentence's own root (n - 1, 0).
-    if (spans && threadIdx.x == 0 && n > 1) {
-        int sp = 0, cnt = 0;
-        stk[0] = n - 1; stk[1] = 0; stk[2] = 0;
-        int32_t* out = spans + (size_t)b * (L - 1) * 2;
-        while (sp >= 0) {
-            const int level = stk[3 * sp], pos = stk[3 * sp + 1], phase = stk[3 * sp + 2];
-            if (level == 0) { --sp; continue; }
-            const int k = bsp[coff(level) + pos];
-            if (phase == 0) { stk[3 * sp + 2] = 1; ++sp; stk[3 * sp] = k; stk[3 * sp + 1] = pos; stk[3 * sp + 2] = 0; }
-            else if (phase == 1) { stk[3 * sp + 2] = 2; ++sp; stk[3 * sp] = level - k - 1; stk[3 * sp + 1] = pos + k + 1; stk[3 * sp + 2] = 0; }
-            else { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; ++cnt; --sp; }
-        }
-    }
+    if (spans && threadIdx.x == 0 && n > 1) emit_spans(bsp, L, C, n, stk, spans + (size_t)b * (L - 1) * 2);
 }
 
 // Dynamic LDS of the kernel for a chart of length L.

@@ -42,6 +42,24 @@ def chart_buffers(plan, dev, flags, *widths):
     return outs, torch.empty(nbytes, device=dev, dtype=torch.uint8), nbytes
 
 
+def workspace_slices(diora):
+    """Per forward workspace of a chart module: (workspace, the slice of its B sentences in the module's outputs)."""
+    B = diora._plan.B
+    return [(ws, slice(i * B, (i + 1) * B)) for i, ws in enumerate(diora._wss)]
+
+
+def span_buffer(diora, out=None):
+    """The span output of a decode over a chart module's workspaces: an int32 tensor (B * workspaces, L-1, 2) on the chart's device --
+    `out`, checked, when given, else a fresh one.  -> (spans, workspace_slices(diora))."""
+    plan, dev = diora._plan, diora._wss[0].device
+    L, shape = plan.L, (plan.B * len(diora._wss), plan.L - 1, 2)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=dev)
+    elif out.shape != shape or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous int32 tensor (%d, %d, 2) on %s' % (shape[0], L - 1, dev))
+    return out, workspace_slices(diora)
+
+
 def _cont(g):
     return g.contiguous().float() if g is not None else None
 
@@ -418,24 +436,12 @@ class DioraBase(nn.Module):
         """cky_spans left on the device: an int32 tensor (B, L-1, 2) on the chart's GPU, written into `out` when given (a contiguous
         int32 tensor of that shape; cliora_amd.evaluate decodes into its batch's output buffer)."""
         plan = self._plan
-        parts = []
-        for i, ws in enumerate(self._wss):
-            with torch.cuda.device(ws.device):
-                if out is not None and len(self._wss) == 1:
-                    spans = out
-                    assert spans.shape == (plan.B, plan.L - 1, 2) and spans.dtype == torch.int32 and spans.is_contiguous()
-                else:
-                    spans = torch.empty((plan.B, plan.L - 1, 2), device=ws.device, dtype=torch.int32)
-                if plan.L > 1:
-                    _lib.call('cliora_cky_spans', plan.handle, _ptr(ws), None, _ptr(spans), _stream())
-            parts.append(spans)
-        if len(parts) == 1:
-            return parts[0]
-        res = torch.cat(parts, 0)
-        if out is not None:
-            out.copy_(res)
-            return out
-        return res
+        spans, parts = span_buffer(self, out)
+        if plan.L > 1:
+            with torch.cuda.device(spans.device):
+                for ws, sl in parts:
+                    _lib.call('cliora_cky_spans', plan.handle, _ptr(ws), None, _ptr(spans[sl]), _stream())
+        return spans
 
     @staticmethod
     def trees_from_spans(spans):

@@ -94,8 +94,8 @@ def ground_batch(diora, batch_map, spans=None, decode='viterbi'):
     ``diora.cky_spans_device()``; None decodes them here, into the output buffer.  Text-only DIORA (``atten_score`` None): F1 counts
     only, the phrases are not read (the reference skips them too).  decode: which tree is decoded when `spans` is None -- 'viterbi'
     (cky_spans_device) or 'mbr' (mbr_spans_device, cliora_amd.posterior)."""
-    if decode not in ('viterbi', 'mbr'):
-        raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
+    from . import ragged
+    ragged.decode_entry(decode)
     plan = diora._plan
     B, L = plan.B * len(diora._wss), plan.L
     atten = getattr(diora, 'atten_score', None)
@@ -281,8 +281,7 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
     example, None (skipped) or a dict of spans (n-1, 2), sent (3,), hit / ccr / word / box per phrase and span_xyxy (n-1, 4).
     decode: 'viterbi' or 'mbr', as ``evaluate``."""
     from . import ragged
-    if decode not in ('viterbi', 'mbr'):
-        raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
+    entry = ragged.decode_entry(decode)
     diora = net.diora
     keep = [i for i, ex in enumerate(examples) if len(ex['sentence']) > 2]
     sents = [list(examples[i]['sentence']) for i in keep]
@@ -303,7 +302,6 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
         def decode_into(out):
             cky_status.append(ragged.decode_spans_ragged(d, lens, decode, out=out)[1])
 
-        entry = 'cliora_span_posteriors' if decode == 'mbr' else 'cliora_cky_spans_ragged'
         res = ground(atten, boxes, tg, decode_into, device=d._wss[0].device, lengths=lens,
                      extra_status=[('cliora_chart_forward_ragged', d._ragged_status), (entry, lambda: cky_status[0])])
         off = tg.phr_off

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr_or_null as _p, stream as _stream
+from .diora import span_buffer, workspace_slices
 
 
 def cell_id(L, level, pos):
@@ -67,17 +68,11 @@ def span_posteriors(diora, lengths=None, mbr=False, out=None):
         status = torch.empty(nws, dtype=torch.int32, device=dev)
         spans = split = None
         if mbr:
-            if out is not None:
-                if out.shape != (B * nws, L - 1, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-                    raise ValueError('out must be a contiguous int32 tensor (%d, %d, 2) on %s' % (B * nws, L - 1, dev))
-                spans = out
-            else:
-                spans = torch.empty((B * nws, L - 1, 2), dtype=torch.int32, device=dev)
+            spans = span_buffer(diora, out)[0]
             split = torch.empty((B * nws, Cc), dtype=torch.int32, device=dev)
         need = _lib.fn('cliora_span_posteriors_scratch_bytes')(plan.handle)
         scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        for i, ws in enumerate(wss):
-            sl = slice(i * B, (i + 1) * B)
+        for i, (ws, sl) in enumerate(workspace_slices(diora)):
             _lib.call('cliora_span_posteriors', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
                       _p(marg[sl]), _p(log_z[sl]), _p(split[sl]) if mbr else None,
                       _p(spans[sl]) if mbr else None, _p(scratch), C.c_void_p(status[i:i + 1].data_ptr()),

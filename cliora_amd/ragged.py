@@ -29,6 +29,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr_or_null as _p, stream as _stream
+from .diora import span_buffer
 
 MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L -- the both-pass padded chart (64 root levels in one mask word) and the default of max_len
 MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_len may be raised to for the inside-only entries (parse_ragged, encode_ragged)
@@ -84,11 +85,13 @@ def pack(lengths, max_batch=64, max_waste=DEFAULT_MAX_WASTE):
     return packs
 
 
-def decode_ragged_numpy(pair_s, lengths):
+def decode_ragged_numpy(pair_s, lengths, L=None):
     """The decode of cliora_cky_spans_ragged restated in numpy, for tests: `pair_s[level]` (B, Lmax - level, level) are the per-split
     inside scores of the PADDED chart; sentence b is decoded from levels 1 .. n-1 at positions pos < n - level, candidate
-    (val_l + val_r) + (s - max s) in fp32, first maximum wins.  -> per sentence the list of (start, end), children before parents."""
+    (val_l + val_r) + (s - max s) in fp32, first maximum wins.  -> per sentence the list of (start, end), children before parents;
+    with L, the padded chart's length, also the chosen splits: (spans, split (B, C) int32, -1 at the leaves and outside each triangle)."""
     out = []
+    split = None if L is None else np.full((len(lengths), L * (L + 1) // 2), -1, dtype=np.int32)
     for b, n in enumerate(int(x) for x in lengths):
         val = {(0, p): np.float32(1.0) for p in range(n)}
         bp = {}
@@ -100,6 +103,8 @@ def decode_ragged_numpy(pair_s, lengths):
                 cand = np.array([(val[(k, pos)] + val[(level - k - 1, pos + k + 1)]) + rel[k] for k in range(level)], dtype=np.float32)
                 k = int(np.argmax(cand))
                 val[(level, pos)], bp[(level, pos)] = cand[k], k
+                if split is not None:
+                    split[b, L * (L + 1) // 2 - (L - level) * (L - level + 1) // 2 + pos] = k
         spans = []
 
         def walk(level, pos):
@@ -111,7 +116,7 @@ def decode_ragged_numpy(pair_s, lengths):
             spans.append((pos, pos + level))
         walk(n - 1, 0)
         out.append(spans)
-    return out
+    return out if split is None else (out, split)
 
 
 def cky_spans_ragged(diora, lengths, split_out=False, out=None):
@@ -122,25 +127,18 @@ def cky_spans_ragged(diora, lengths, split_out=False, out=None):
     the caller must check; split (B, C) int32, -1 at the leaves and outside each triangle.  Device tensors; nothing is synchronised.
     out: a contiguous int32 tensor (B, L-1, 2) on the chart's device to decode into (cliora_amd.evaluate: its output buffer)."""
     plan, wss = diora._plan, diora._wss
-    B, L = plan.B, plan.L
-    nws = len(wss)
+    B, nws = plan.B, len(wss)
     if lengths.dtype != torch.int32 or lengths.numel() != B * nws:
         raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
     dev = wss[0].device
     with torch.cuda.device(dev):
         lengths = lengths.to(dev).contiguous()
-        if out is not None:
-            if out.shape != (B * nws, L - 1, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-                raise ValueError('out must be a contiguous int32 tensor (%d, %d, 2) on %s' % (B * nws, L - 1, dev))
-            spans = out
-        else:
-            spans = torch.empty((B * nws, L - 1, 2), dtype=torch.int32, device=dev)
+        spans, parts = span_buffer(diora, out)
         status = torch.empty(nws, dtype=torch.int32, device=dev)
         split = torch.empty((B * nws, plan.C), dtype=torch.int32, device=dev) if split_out else None
-        for i, ws in enumerate(wss):
-            _lib.call('cliora_cky_spans_ragged', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[i * B:(i + 1) * B]),
-                      _p(split[i * B:(i + 1) * B]) if split_out else C.c_void_p(0),
-                      _p(spans[i * B:(i + 1) * B]), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+        for i, (ws, sl) in enumerate(parts):
+            _lib.call('cliora_cky_spans_ragged', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]),
+                      _p(split[sl]) if split_out else C.c_void_p(0), _p(spans[sl]), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
     return (spans, status, split) if split_out else (spans, status)
 
 
@@ -258,16 +256,22 @@ def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, 
     return packs
 
 
+def decode_entry(decode):
+    """The one check of a decode's name: 'viterbi' or 'mbr' -> the C entry that decodes a padded chart that way, for messages."""
+    if decode not in ('viterbi', 'mbr'):
+        raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
+    return 'cliora_span_posteriors' if decode == 'mbr' else 'cliora_cky_spans_ragged'
+
+
 def decode_spans_ragged(diora, lengths, decode='viterbi', out=None):
     """The span decode of a padded chart by name: 'viterbi' (cliora_cky_spans_ragged) or 'mbr' (cliora_span_posteriors' MBR tree,
     cliora_amd.posterior).  -> (spans, status, the entry's name for messages), spans decoded into `out` when given."""
+    entry = decode_entry(decode)
     if decode == 'viterbi':
-        return cky_spans_ragged(diora, lengths, out=out) + ('cliora_cky_spans_ragged',)
-    if decode == 'mbr':
-        from . import posterior
-        post = posterior.span_posteriors(diora, lengths, mbr=True, out=out)
-        return post.spans, post.status, 'cliora_span_posteriors'
-    raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
+        return cky_spans_ragged(diora, lengths, out=out) + (entry,)
+    from . import posterior
+    post = posterior.span_posteriors(diora, lengths, mbr=True, out=out)
+    return post.spans, post.status, entry
 
 
 def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L, decode='viterbi'):
@@ -279,8 +283,7 @@ def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_
     decode: 'viterbi' (the reference's tree) or 'mbr' (the tree with the most expected correct brackets, cliora_amd.posterior)."""
     diora = net.diora
     trees = [None] * len(sentences)
-    if decode not in ('viterbi', 'mbr'):
-        raise ValueError("decode must be 'viterbi' or 'mbr', not %r" % (decode,))
+    decode_entry(decode)                             # a bad name is refused before any pack has run
 
     def decode_pack(idx, lens):
         spans, status, entry = decode_spans_ragged(diora, lens, decode)

@@ -212,6 +212,32 @@ def test_long_padded_chart():
     _check_mbr_bitwise(got, lengths, L)
 
 
+def test_boundary_lengths_share_one_long_chart():
+    """L 65 (a long plan), D 50, lengths [65, 64, 2, 1] in one padded chart: the two callers of the shared walk and the shared
+    first-maximum reduction, at 65 and 64 words (two splits per lane, and the most one lane each holds) and at two words and one.
+    cky_spans_ragged's splits and spans == decode_ragged_numpy on the device's own per-split scores, and the MBR tree of
+    span_posteriors == mbr_numpy on the device's own marginals: integers, row for row, no tolerance."""
+    from cliora_amd import ragged
+    from cliora_amd.posterior import span_posteriors
+    L, D, lengths = 65, 50, [65, 64, 2, 1]
+    xs = [PC.sentence(D, n, 5500 + b) for b, n in enumerate(lengths)]
+    m = PC.text_module(PC.params(D, PC.GPU_SEED), D).cuda().eval()
+    m.outside = False
+    _forward(m, PC.padded(xs, L).cuda())
+    lens = torch.tensor(lengths, dtype=torch.int32).cuda()
+    spans, status, split = ragged.cky_spans_ragged(m, lens, split_out=True)
+    assert status.cpu().tolist() == [0]
+    want_spans, want_split = ragged.decode_ragged_numpy(_scores(m), lengths, L)
+    assert np.array_equal(split.cpu().numpy(), want_split)
+    spans = spans.cpu().numpy()
+    for b, n in enumerate(lengths):
+        assert spans[b, :n - 1].tolist() == [list(s) for s in want_spans[b]], n
+        assert (spans[b, n - 1:] == -1).all()
+    got = _host(span_posteriors(m, lens, mbr=True))
+    assert got['status'] == [0]
+    _check_mbr_bitwise(got, lengths, L)
+
+
 def test_cliora_plan():
     """A CLIORA plan (R 36, L 9): the same score rows, the same bounds."""
     from cliora_amd.cliora import DioraMLP

@@ -123,7 +123,7 @@ def test_bad_lengths_are_counted_and_harm_no_other_sentence():
             assert torch.equal(spans[b], ref_spans[b]) and torch.equal(split[b], ref_split[b])
 
 
-@pytest.mark.parametrize('D,B,L', [(50, 9, 14), (400, 5, 23), (50, 3, 2), (50, 4, 1)])
+@pytest.mark.parametrize('D,B,L', [(50, 9, 14), (400, 5, 23), (50, 3, 2), (50, 4, 1), (50, 2, 65), (50, 2, 128)])
 def test_all_equal_lengths_are_bitwise_cky_spans(D, B, L):
     from cliora_amd import _lib, ragged
     from cliora_amd.diora import _ptr, _stream
