@@ -19,7 +19,13 @@ namespace cliora {
 // saturate correctly through exp -> inf / 0, absolute error ~1e-7 (the cell kernels recompute every gate twice per pair in the
 // backward: c5 at L 40 34.0 -> 31.4 ms, L 20 6.33 -> 5.90 against libm expf / tanhf; fixtures and oracle checks unchanged).
 __device__ __forceinline__ float sigm(float x) { return __frcp_rn(1.f + __expf(-x)); }
-__device__ __forceinline__ float lstm_tanh(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }
+// Near zero the quotient form cancels: its absolute error of one ulp of 1 (6e-8) is 3e-5 of x at |x| = 2^-9 and all of x below 3e-8, so
+// the row tanh(W x) of a sub-eps word came out as zeros, which the unit norm's clamp branch (x 1 / eps) does not forgive
+// (tests/test_gpu_degenerate.py, case c).  Below 2^-9: x - x^3 / 3, relative error 2 x^4 / 15 < 2e-12; tanh(0) stays 0.
+__device__ __forceinline__ float lstm_tanh(float x) {
+    const float q = 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x));
+    return fabsf(x) < 0.001953125f ? x - x * x * x * (1.f / 3.f) : q;
+}
 __device__ __forceinline__ float4 f4map(float4 a, float (*f)(float)) { return make_float4(f(a.x), f(a.y), f(a.z), f(a.w)); }
 __device__ __forceinline__ float4 f4sig(float4 a, float k) { return make_float4(sigm(a.x + k), sigm(a.y + k), sigm(a.z + k), sigm(a.w + k)); }
 __device__ __forceinline__ float4 f4tanh(float4 a) { return make_float4(lstm_tanh(a.x), lstm_tanh(a.y), lstm_tanh(a.z), lstm_tanh(a.w)); }

@@ -145,7 +145,7 @@ def test_c3_cliora_full_size(mfma_mode):
     net = H.build_net(D, torch.nn.Embedding(V, E), obj_feats=True, img_dim=2048, k_neg=K, vg_loss=True, use_contr=True,
                       vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0)
     for p in net.img_encoder.parameters():
-        torch.nn.init.normal_(p, std=0.02)             # the reference's zero init makes every VL score 0
+        torch.nn.init.normal_(p, std=0.02)             # non-zero VL scores here; the zero init as built: test_gpu_degenerate.py (case g)
     g = torch.Generator().manual_seed(22)
     sentences = torch.randint(0, V, (B, L), generator=g)
     neg = torch.randperm(V, generator=g)[:K]
