@@ -1,16 +1,18 @@
-// C ABI, decode unit: the best tree (CKY), and the span posteriors, log-partition and MBR tree, from the per-split scores of the last
-// forward -- of every sentence of a chart, or of each sentence's own triangle of a right-padded chart.  See include/cliora_chart.h for
-// the contract, decode_kernels.hpp for the CKY kernel and posterior_kernels.hpp for the sum-product model.
+// C ABI, decode unit: the best tree (CKY), the K best trees, and the span posteriors, log-partition and MBR tree, from the per-split
+// scores of the last forward -- of every sentence of a chart, or of each sentence's own triangle of a right-padded chart.  See
+// include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY kernel, kbest_kernels.hpp for the k-best lists and
+// posterior_kernels.hpp for the sum-product model.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
 #include "api_common.hpp"
 #include "decode_kernels.hpp"
+#include "kbest_kernels.hpp"
 #include "posterior_kernels.hpp"
 
-// The one launch of a decode kernel: a workgroup of `waves` wavefronts per sentence, lds_of(L, C) bytes of dynamic LDS, the arguments
-// every decode kernel starts with, then the kernel's own.  f(Bool<LONG>, go) calls go(name, the kernel's instance, its own arguments...).
+// The one launch of a decode kernel: a workgroup of `waves` wavefronts per sentence, lds_of(L, C) bytes of dynamic LDS (a function or
+// a closure), the arguments every decode kernel starts with, then the kernel's own.  f(Bool<LONG>, go) calls go(name, the kernel's instance, its own arguments...).
 // who: the entry's name in the "called before forward" message.  status: zeroed first when given.
-template <class F>
-static int launch_decode(cliora_plan* plan, void* fwd_ws, const char* who, int waves, size_t (*lds_of)(int, int), const int32_t* lengths,
+template <class LdsOf, class F>
+static int launch_decode(cliora_plan* plan, void* fwd_ws, const char* who, int waves, LdsOf&& lds_of, const int32_t* lengths,
                          int32_t* split, int32_t* spans, int32_t* status, void* stream, F&& f) {
     if (!plan->uploaded) return fail(CLIORA_EINVAL, std::string(who) + " called before forward");
     hipStream_t st = (hipStream_t)stream;
@@ -70,5 +72,28 @@ extern "C" int cliora_span_posteriors(cliora_plan* plan, void* fwd_ws, const int
     return launch_decode(plan, fwd_ws, "span_posteriors", POST_WAVES, span_posteriors_lds, lengths, mbr_split, mbr_spans, status, stream,
                          [&](auto LONG, auto&& go) {
                              return go("span_posteriors_kernel", span_posteriors_kernel<decltype(LONG)::value>, marginals, log_z);
+                         });
+}
+
+// The tables of a plan's B sentences when they do not fit the LDS (kbest_kernels.hpp: kbest_in_lds), else 0.
+extern "C" size_t cliora_kbest_scratch_bytes(const cliora_plan* plan, int K) {
+    if (!plan || K < 1 || K > KBEST_MAX_K) return 0;
+    const Plan& p = plan->p;
+    return kbest_in_lds(p.L, p.C, K) ? 0 : (size_t)p.B * kbest_table_bytes(p.C, K);
+}
+
+extern "C" int cliora_kbest_spans(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, int K, int32_t* spans_out, float* scores_out,
+                                  int32_t* count_out, void* scratch, int32_t* status, void* stream) {
+    if (K < 1 || K > KBEST_MAX_K) return fail(CLIORA_EINVAL, "cliora_kbest_spans: K outside 1..16");
+    if (!plan || !fwd_ws || !scores_out || !count_out || (!spans_out && plan->p.L > 1))
+        return fail(CLIORA_EINVAL, "cliora_kbest_spans: NULL argument");
+    if (lengths && !status) return fail(CLIORA_EINVAL, "cliora_kbest_spans: lengths given without status");
+    if (!scratch && cliora_kbest_scratch_bytes(plan, K)) return fail(CLIORA_EINVAL, "cliora_kbest_spans: NULL scratch");
+    const bool in_lds = kbest_in_lds(plan->p.L, plan->p.C, K);
+    return launch_decode(plan, fwd_ws, "kbest_spans", KBEST_WAVES, [K](int L, int C) { return kbest_lds(L, C, K); }, lengths, nullptr,
+                         spans_out, status, stream, [&](auto LONG, auto&& go) {
+                             constexpr bool LNG = decltype(LONG)::value;
+                             return in_lds ? go("kbest_kernel", kbest_kernel<LNG, true>, K, scores_out, count_out, (float*)nullptr)
+                                           : go("kbest_kernel", kbest_kernel<LNG, false>, K, scores_out, count_out, (float*)scratch);
                          });
 }

@@ -41,18 +41,31 @@ __device__ __forceinline__ void wave_first_max(float& best, int& bi) {
 // The tree's constituent spans (start, end) from the sentence's root (n - 1, 0), n > 1, children before parents, left subtree first:
 // the order of the REDUCE actions, i.e. what the reference gets from get_spans(get_actions(tree)) (cliora/analysis/utils.py:3-49) --
 // n - 1 spans, the root last.  One lane walks the n - 1 internal nodes with an explicit stack (level, pos, phase) of 3 (L + 1) ints.
-// bsp: the chosen split of every cell of the triangle, by cell id.
-__device__ __forceinline__ void emit_spans(const int32_t* bsp, int L, int C, int n, int32_t* stk, int32_t* __restrict__ out) {
+// node(level, pos, rank, lrank, rrank) -> the split of the cell's derivation `rank`, and the ranks of its children's derivations.
+// RANKED (the k-best lists of kbest_kernels.hpp): a stack entry carries its rank, 4 (L + 1) ints; else every rank is 0 and unread.
+template <bool RANKED, class Node>
+__device__ __forceinline__ void walk_spans(int n, int rank, int32_t* stk, int32_t* __restrict__ out, Node&& node) {
+    constexpr int W = RANKED ? 4 : 3;
     int sp = 0, cnt = 0;
     stk[0] = n - 1; stk[1] = 0; stk[2] = 0;
+    if constexpr (RANKED) stk[3] = rank;
     while (sp >= 0) {
-        const int level = stk[3 * sp], pos = stk[3 * sp + 1], phase = stk[3 * sp + 2];
+        const int level = stk[W * sp], pos = stk[W * sp + 1], phase = stk[W * sp + 2];
         if (level == 0) { --sp; continue; }
-        const int k = bsp[chart_cell(L, C, level, pos)];
-        if (phase == 0) { stk[3 * sp + 2] = 1; ++sp; stk[3 * sp] = k; stk[3 * sp + 1] = pos; stk[3 * sp + 2] = 0; }
-        else if (phase == 1) { stk[3 * sp + 2] = 2; ++sp; stk[3 * sp] = level - k - 1; stk[3 * sp + 1] = pos + k + 1; stk[3 * sp + 2] = 0; }
-        else { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; ++cnt; --sp; }
+        int lr = 0, rr = 0;
+        const int k = node(level, pos, RANKED ? stk[W * sp + 3] : 0, lr, rr);
+        if (phase == 0) {
+            stk[W * sp + 2] = 1; ++sp; stk[W * sp] = k; stk[W * sp + 1] = pos; stk[W * sp + 2] = 0;
+            if constexpr (RANKED) stk[W * sp + 3] = lr;
+        } else if (phase == 1) {
+            stk[W * sp + 2] = 2; ++sp; stk[W * sp] = level - k - 1; stk[W * sp + 1] = pos + k + 1; stk[W * sp + 2] = 0;
+            if constexpr (RANKED) stk[W * sp + 3] = rr;
+        } else { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; ++cnt; --sp; }
     }
+}
+// The walk over one chosen split per cell.  bsp: the chosen split of every cell of the triangle, by cell id.
+__device__ __forceinline__ void emit_spans(const int32_t* bsp, int L, int C, int n, int32_t* stk, int32_t* __restrict__ out) {
+    walk_spans<false>(n, 0, stk, out, [&](int level, int pos, int, int&, int&) { return bsp[chart_cell(L, C, level, pos)]; });
 }
 
 // Best binary tree per sentence.  val[] (chart of best scores) lives in LDS; leaves start at 1 (analysis/cky.py:24-25, 39).

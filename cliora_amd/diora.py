@@ -490,6 +490,23 @@ class DioraBase(nn.Module):
             return [0] * (self._plan.B * len(self._wss))
         return self.trees_from_spans(self.mbr_spans_device().cpu().numpy())
 
+    def kbest_spans_device(self, k, lengths=None):
+        """The k best trees of the last forward, rank 0 the tree of cky() (cliora_amd.kbest.kbest_spans):
+        -> KBest(spans (B, k, L-1, 2), scores (B, k), count (B,), status).  Device tensors."""
+        from . import kbest
+        return kbest.kbest_spans(self, k, lengths=lengths)
+
+    def kbest(self, k):
+        """Per sentence the list of its (tree, score), best first: min(k, Catalan(L - 1)) nested tuples of word positions as cky()
+        returns them, each with the sum of its potentials (<= 0; exp(score - log_z) is the tree's posterior mass)."""
+        kb = self.kbest_spans_device(k)
+        nsp = kb.spans.numel()
+        host = torch.cat([kb.spans.reshape(-1), kb.scores.view(torch.int32).reshape(-1), kb.count]).cpu().numpy()    # one copy
+        spans = host[:nsp].reshape(kb.spans.shape)
+        scores = host[nsp:nsp + kb.scores.numel()].view('float32').reshape(kb.scores.shape)
+        count = host[nsp + kb.scores.numel():]
+        return [list(zip(self.trees_from_spans(spans[b, :count[b]]), scores[b, :count[b]].tolist())) for b in range(len(count))]
+
 
 class DioraMLP(DioraBase):
     def init_parameters(self):

@@ -214,6 +214,41 @@ class Evaluator(object):
         return dict(zip(METRICS, [corpus_f1, sent_f1, ground_acc, ccra] + self.losses()))
 
 
+def oracle_f1(spans_k, count, gold):
+    """Best-of-K ("oracle") span F1 on the host.  spans_k (B, K, L-1, 2) and count (B,): the k-best trees of cliora_amd.kbest (arrays
+    or tensors; (-1, -1) rows are padding); gold: per sentence its constituents, the root excluded.  Each tree is counted as
+    ``SpanF1.add_counts`` counts a sentence -- span sets, the predicted root (the tree's last row) dropped as cliora_ground_eval
+    drops it -- and a sentence keeps its tree with the highest sentence F1, the first on a tie.  -> dict: best_rank and best_f1 per
+    sentence, and the corpus figures of the kept trees, oracle_corpus_f1 and oracle_sent_f1, beside rank 0's own (corpus_f1,
+    sent_f1).  A sentence with count 0 is skipped (best_rank -1, best_f1 nan)."""
+    spans_k = spans_k.cpu().numpy() if isinstance(spans_k, torch.Tensor) else np.asarray(spans_k)
+    count = count.cpu().numpy() if isinstance(count, torch.Tensor) else np.asarray(count)
+    first, best = SpanF1(), SpanF1()
+    best_rank, best_f1 = [], []
+    for b in range(spans_k.shape[0]):
+        g = set((int(s), int(e)) for s, e in gold[b])
+        keep = None
+        for t in range(int(count[b])):
+            rows = [tuple(r) for r in spans_k[b, t].tolist() if r[0] >= 0]
+            pred = set(rows[:-1])
+            one = SpanF1()
+            one.add_counts(len(pred & g), len(pred), len(g))
+            if t == 0:
+                first.add_counts(len(pred & g), len(pred), len(g))
+            if keep is None or one.sentence[0] > keep[1]:
+                keep = (t, one.sentence[0], len(pred & g), len(pred))
+        if keep is None:
+            best_rank.append(-1)
+            best_f1.append(float('nan'))
+            continue
+        best.add_counts(keep[2], keep[3], len(g))
+        best_rank.append(keep[0])
+        best_f1.append(keep[1])
+    mean = lambda f: float(np.mean(np.array(f.sentence))) if f.sentence else float('nan')
+    return dict(best_rank=best_rank, best_f1=best_f1, oracle_corpus_f1=best.corpus_f1, oracle_sent_f1=mean(best),
+                corpus_f1=first.corpus_f1, sent_f1=mean(first))
+
+
 def batch_records(res, trees, sentences, example_ids, idx2word, with_boxes, post=False):
     """The batch's parse.jsonl lines (parse.py:215-280).  pred_spans / gold_spans in the iteration order of the reference's Python
     sets, built the same way (from the span list in reduce order, from GT[b][:-1]); pred_boxes in the order of pred_spans."""

@@ -299,6 +299,35 @@ def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_
     return trees
 
 
+def parse_ragged_kbest(net, sentences, k, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L_INSIDE):
+    """The k best binary trees of every sentence (cliora_amd.kbest), in the caller's order: per sentence the list of its
+    (tree, score), best first -- min(k, Catalan(n - 1)) nested tuples as ``parse_ragged`` returns them (0 for a single word), each
+    with the sum of its potentials.  Packs like ``parse_ragged`` and runs the inside pass only, so sentences of up to 128 words are
+    taken (max_len).  One device-to-host copy per pack."""
+    from . import kbest
+    diora = net.diora
+    out = [None] * len(sentences)
+    k = int(k)
+    if not 1 <= k <= kbest.MAX_K:                    # refused before any pack has run
+        raise ValueError('k must be in 1..%d' % kbest.MAX_K)
+
+    def decode_pack(idx, lens):
+        kb = kbest.kbest_spans(diora, k, lens)
+        nsp, nsc = kb.spans.numel(), kb.scores.numel()
+        host = torch.cat([kb.spans.reshape(-1), kb.scores.view(torch.int32).reshape(-1), kb.count, kb.status]).cpu().numpy()
+        if host[nsp + nsc + kb.count.numel():].any():
+            raise _lib.ChartLibError('cliora_kbest_spans rejected %d sentence length(s)' % int(host[nsp + nsc + kb.count.numel():].sum()))
+        rows = host[:nsp].reshape(kb.spans.shape)
+        scores = host[nsp:nsp + nsc].view(np.float32).reshape(kb.scores.shape)
+        count = host[nsp + nsc:nsp + nsc + kb.count.numel()]
+        for b, i in enumerate(idx):
+            trees = diora.trees_from_spans(rows[b, :count[b], :len(sentences[i]) - 1])
+            out[i] = list(zip(trees, scores[b, :count[b]].tolist()))
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
+    return out
+
+
 def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L):
     """(N, D) fp32 on the device: row i = inside_h of sentence i's root cell (its own length's root, not the padded chart's), the
     vector DIORA users read off the root.  Same plumbing as parse_ragged, max_len included."""

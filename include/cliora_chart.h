@@ -337,6 +337,27 @@ int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_workspace, const int32_
 size_t cliora_span_posteriors_scratch_bytes(const cliora_plan* plan);
 int cliora_span_posteriors(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, float* marginals, float* log_z,
                            int32_t* mbr_split, int32_t* mbr_spans, void* scratch, int32_t* status, void* stream);
+/* The K best binary trees per sentence over the potentials of cliora_cky_spans and cliora_span_posteriors: r[cell, k] = score[cell, k]
+ * - max_k score[cell, .], a tree scores the sum of r over its internal cells (so exp(score - log_z) is its posterior mass).  The
+ * order is the contract: every cell holds at most K derivations (value, split k, left rank i, right rank j);
+ * a leaf holds one, value 1.0f; a candidate is (val_left[i] + val_right[j]) + (s_k - smax) in fp32, in that order; a cell's list is the
+ * first K candidates by value descending, then split, left rank, right rank ascending.  Rank 0 is cliora_cky_spans' tree; no tree
+ * appears twice.  One workgroup per sentence, fixed-order reductions, no floating-point atomics: two calls give equal bits.
+ *   K: 1 .. 16.  lengths (B) int32 device, or NULL: every sentence has L words.  Otherwise the sentences share a right-padded chart,
+ *     with the rules of cliora_cky_spans_ragged: `status` (an int32 on the device, zeroed by the call) is required and counts the
+ *     lengths outside [1, L]; such a sentence gets count 0, scores -inf, every row -1, and none of its scores is read.  With every
+ *     length equal to L the outputs are bitwise those of the lengths == NULL call.  status may be NULL when lengths is.
+ *   count_out (B): min(K, Catalan(n - 1)) trees.  scores_out (B, K) fp32: root value - (float)n, -inf beyond count.  spans_out
+ *     (B, K, L-1, 2) (may be NULL when L = 1): tree t's n - 1 spans in cliora_cky_spans' order, the root last; (-1, -1) beyond a
+ *     tree's n - 1 rows and beyond count.
+ *   scratch: device memory of cliora_kbest_scratch_bytes(plan, K) bytes -- 0 when the lists (8 C K bytes per sentence) fit the LDS
+ *     beside the walk stacks, else B of them; NULL when that is 0.
+ * Every plan cliora_cky_spans takes is taken: long plans, padded charts, TreeLSTM plans.  Refused with CLIORA_EINVAL and a message,
+ * before any launch: K outside 1..16; a NULL plan, workspace or output; lengths without status; NULL scratch when the query is not 0;
+ * a plan that has not run a forward.  Scores that are NaN or infinite give unspecified trees (inside the sentence). */
+size_t cliora_kbest_scratch_bytes(const cliora_plan* plan, int K);
+int cliora_kbest_spans(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, int K, int32_t* spans_out, float* scores_out,
+                       int32_t* count_out, void* scratch, int32_t* status, void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
