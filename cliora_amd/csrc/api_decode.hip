@@ -1,12 +1,15 @@
-// C ABI, decode unit: the best tree (CKY), the K best trees, and the span posteriors, log-partition and MBR tree, from the per-split
+// C ABI, decode unit: the best tree (CKY), the K best trees, sampled trees, and the span posteriors, log-partition and MBR tree, from the per-split
 // scores of the last forward -- of every sentence of a chart, or of each sentence's own triangle of a right-padded chart.  See
-// include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY kernel, kbest_kernels.hpp for the k-best lists and
-// posterior_kernels.hpp for the sum-product model.
+// include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY kernel, kbest_kernels.hpp for the k-best lists,
+// posterior_kernels.hpp for the sum-product model and sample_kernels.hpp for the draws from it.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
+#include <cmath>
+
 #include "api_common.hpp"
 #include "decode_kernels.hpp"
 #include "kbest_kernels.hpp"
 #include "posterior_kernels.hpp"
+#include "sample_kernels.hpp"
 
 // The one launch of a decode kernel: a workgroup of `waves` wavefronts per sentence, lds_of(L, C) bytes of dynamic LDS (a function or
 // a closure), the arguments every decode kernel starts with, then the kernel's own.  f(Bool<LONG>, go) calls go(name, the kernel's instance, its own arguments...).
@@ -95,5 +98,21 @@ extern "C" int cliora_kbest_spans(cliora_plan* plan, void* fwd_ws, const int32_t
                              constexpr bool LNG = decltype(LONG)::value;
                              return in_lds ? go("kbest_kernel", kbest_kernel<LNG, true>, K, scores_out, count_out, (float*)nullptr)
                                            : go("kbest_kernel", kbest_kernel<LNG, false>, K, scores_out, count_out, (float*)scratch);
+                         });
+}
+
+// Every table of the kernel fits the CU's LDS up to L = 128 (sample_kernels.hpp: 81 KiB there), so there is no scratch and no query.
+extern "C" int cliora_sample_trees(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, const int32_t* ids, int S, uint64_t seed,
+                                   uint64_t first_sample, float beta, int32_t* spans_out, float* log_prob_out, float* log_z_out,
+                                   int32_t* status, void* stream) {
+    if (S < 1 || S > SAMPLE_MAX_S) return fail(CLIORA_EINVAL, "cliora_sample_trees: S outside 1..1048576");
+    if (!(beta >= 0.f) || !std::isfinite(beta)) return fail(CLIORA_EINVAL, "cliora_sample_trees: beta negative or not finite");
+    if (!plan || !fwd_ws || !log_prob_out || !log_z_out || (!spans_out && plan->p.L > 1))
+        return fail(CLIORA_EINVAL, "cliora_sample_trees: NULL argument");
+    if (lengths && !status) return fail(CLIORA_EINVAL, "cliora_sample_trees: lengths given without status");
+    return launch_decode(plan, fwd_ws, "sample_trees", POST_WAVES, sample_trees_lds, lengths, nullptr, spans_out, status, stream,
+                         [&](auto LONG, auto&& go) {
+                             return go("sample_trees_kernel", sample_trees_kernel<decltype(LONG)::value>, ids, S, seed, first_sample, beta,
+                                       log_prob_out, log_z_out);
                          });
 }

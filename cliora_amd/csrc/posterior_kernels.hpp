@@ -51,6 +51,32 @@ __device__ __forceinline__ post_t post_wave_lse(post_t t0, post_t t1) {
     return m + log(post_wave_sum(e));
 }
 
+// The inside table of sentence b's n words, levels up: al[leaf] = 0 is the caller's (before a barrier), al[cell] = logsumexp_k(al[left]
+// + al[right] + beta r[cell, k]) with beta r formed in fp64 -- beta = 1 multiplies exactly, so cliora_span_posteriors' table is what
+// it was before the tree sampler (sample_kernels.hpp) shared it.  Called by every thread of a workgroup of POST_WAVES wavefronts: a
+// wavefront per cell, one barrier per level, the last one before it returns.  lvl: the plan's level bases, in LDS.
+template <bool LONG>
+__device__ __forceinline__ void post_inside(post_t* al, const int32_t* lvl, int L, int C, int B, int b, int n,
+                                            const float* __restrict__ Sp, post_t beta) {
+    const post_t ninf = -INFINITY;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
+    for (int level = 1; level < n; ++level) {
+        const int off = coff(level), mine = n - level;
+        for (int pos = wave; pos < mine; pos += POST_WAVES) {
+            const bool an = lane < level, an1 = LONG && lane + 64 < level;
+            float s, s1;
+            const float smax = load_split_scores<LONG>(Sp + (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level, level, lane, s, s1);
+            post_t t0 = ninf, t1 = ninf;
+            if (an) t0 = al[coff(lane) + pos] + al[coff(level - lane - 1) + pos + lane + 1] + beta * ((post_t)s - (post_t)smax);
+            if (an1) t1 = al[coff(lane + 64) + pos] + al[coff(level - lane - 65) + pos + lane + 65] + beta * ((post_t)s1 - (post_t)smax);
+            const post_t a = post_wave_lse<LONG>(t0, t1);
+            if (lane == 0) al[off + pos] = a;
+        }
+        __syncthreads();
+    }
+}
+
 // One workgroup per sentence; POST_WAVES wavefronts, one cell each per turn, one barrier per level of each pass.
 // lengths (B) or NULL (every sentence has L words).  marg (B, C): mu in the cell order of inside_s, exactly 0 outside the sentence's
 // triangle; log_z (B).  split (B, C) / spans (B, L-1, 2), either NULL: the MBR tree in cky_kernel's layout (-1 at the leaves
@@ -86,21 +112,7 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel
     __syncthreads();                                 // also orders the fills before the stores below (same workgroup, same addresses)
     if (n == 0) return;
 
-    // ---- inside, levels up
-    for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const bool an = lane < level, an1 = LONG && lane + 64 < level;
-            float s, s1;
-            const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
-            post_t t0 = ninf, t1 = ninf;
-            if (an) t0 = al[coff(lane) + pos] + al[coff(level - lane - 1) + pos + lane + 1] + ((post_t)s - (post_t)smax);
-            if (an1) t1 = al[coff(lane + 64) + pos] + al[coff(level - lane - 65) + pos + lane + 65] + ((post_t)s1 - (post_t)smax);
-            const post_t a = post_wave_lse<LONG>(t0, t1);
-            if (lane == 0) al[off + pos] = a;
-        }
-        __syncthreads();
-    }
+    post_inside<LONG>(al, lvl, L, C, B, b, n, Sp, (post_t)1);
     const post_t lz = al[coff(n - 1)];
     if (threadIdx.x == 0) log_z[b] = (float)lz;
 

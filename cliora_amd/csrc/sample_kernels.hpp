@@ -1,0 +1,131 @@
+// Draws from the distribution over binary trees whose mode cky_kernel returns (cliora_sample_trees; include/cliora_chart.h, DESIGN.md
+// section 18).  The potentials are those of posterior_kernels.hpp, r[cell, k] = Sp[row(cell) + k] - max_k Sp[row(cell) + .], scaled by
+// an inverse temperature beta >= 0: a tree weighs exp(beta * sum of r over its internal cells).  Per sentence of n words:
+//   inside   post_inside (posterior_kernels.hpp): al[leaf] = 0, al[cell] = logsumexp_k(al[left] + al[right] + beta r[cell, k]), fp64;
+//            log_z = al[(n - 1, 0)].
+//   draws    sample s walks from the root.  At an internal cell (level, pos), N = level splits:
+//              w_k = exp(al[left_k] + al[right_k] + beta r_k - al[cell]),  c_k = w_0 + .. + w_k (a fixed-order inclusive scan),
+//              split = #{k : c_k <= u c_{N-1}}, clamped to N - 1,
+//              u = philox_uniform (philox.hpp) at counter (level * 256 + pos, sample_lo, sample_hi, sentence id), key = seed.
+//            A draw depends on (seed, sentence id, sample index, cell) and the sentence's scores alone: not on the batch, the padding,
+//            the wavefront that walks it or the call's chunking (sample index = first_sample + s).
+//   outputs  the n - 1 spans in emit_spans' order; log_prob = sum of beta r(chosen) - log_z, summed in fp64, stored as fp32.
+// One workgroup of POST_WAVES wavefronts per sentence: the inside pass a wavefront per cell, then wavefront w takes samples w,
+// w + POST_WAVES, ...; its 64 lanes walk one tree together, a lane per split (and lane + 64 when LONG).  The walk is walk_spans' with
+// the drawn split kept in the stack entry (level, pos, phase, split), so a node is drawn once; every lane of the wave holds the same
+// stack values and writes them all, so no lane reads what another wrote.  No atomics but the status count; two calls give equal bits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "philox.hpp"
+#include "posterior_kernels.hpp"
+
+namespace cliora {
+
+constexpr int SAMPLE_MAX_S = 1 << 20;
+
+// Inclusive scan over the 64 lanes in a fixed order (offsets 1, 2, .. 32), every lane active: the same bits on every run.
+__device__ __forceinline__ post_t post_wave_scan(post_t v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const post_t w = __shfl_up(v, o); if (lane >= o) v += w; }
+    return v;
+}
+
+// lengths (B) or NULL; ids (B) or NULL (sentence id = b).  spans (B, S, L-1, 2) (NULL when L = 1): sample s's n - 1 constituents,
+// (-1, -1) beyond; log_prob (B, S); log_z (B).  A length outside [1, L]: every row -1, log_prob 0, log_z 0, one count in *status, no
+// chart read.  `split` is launch_decode's slot and always NULL here.
+// LDS: al (C) post_t; lvl (L) ints; POST_WAVES walk stacks of 4 (L + 1) ints.
+template <bool LONG = false>
+static __global__ __launch_bounds__(POST_WAVES * 64) void sample_trees_kernel(int L, int C, const int32_t* __restrict__ lvl_base, int B,
+                                                                              const float* __restrict__ Sp,
+                                                                              const int32_t* __restrict__ lengths, int32_t* split,
+                                                                              int32_t* __restrict__ spans, int32_t* __restrict__ status,
+                                                                              const int32_t* __restrict__ ids, int S, uint64_t seed,
+                                                                              uint64_t first_sample, float beta_f,
+                                                                              float* __restrict__ log_prob, float* __restrict__ log_z) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sample_smem[];
+    post_t* al = reinterpret_cast<post_t*>(sample_smem);
+    int32_t* lvl = reinterpret_cast<int32_t*>(al + C);
+    constexpr int NT = POST_WAVES * 64;
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t* stk = lvl + L + (size_t)wave * 4 * (L + 1);
+    const post_t beta = (post_t)beta_f;
+    (void)split;
+    int n = lengths ? lengths[b] : L;
+    if (n < 1 || n > L) { n = 0; if (threadIdx.x == 0) atomicAdd(status, 1); }
+    const size_t rows = (size_t)2 * (L - 1);         // ints of one sample's spans
+    if (spans) for (size_t i = threadIdx.x; i < (size_t)S * rows; i += NT) spans[(size_t)b * S * rows + i] = -1;
+    for (int c = threadIdx.x; c < L; c += NT) lvl[c] = lvl_base[c];
+    for (int c = threadIdx.x; c < n; c += NT) al[c] = 0;                                            // the sentence's leaves
+    if (n == 0) {
+        for (int s = threadIdx.x; s < S; s += NT) log_prob[(size_t)b * S + s] = 0.f;
+        if (threadIdx.x == 0) log_z[b] = 0.f;
+    }
+    __syncthreads();                                 // also orders the -1 fill before the stores below (same workgroup, same addresses)
+    if (n == 0) return;
+    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
+
+    post_inside<LONG>(al, lvl, L, C, B, b, n, Sp, beta);
+    const post_t lz = al[coff(n - 1)];
+    if (threadIdx.x == 0) log_z[b] = (float)lz;
+
+    const uint32_t sid = ids ? (uint32_t)ids[b] : (uint32_t)b;
+    for (int s = wave; s < S; s += POST_WAVES) {     // al is read only from here on: the waves go their own ways
+        const uint64_t sample = first_sample + (uint64_t)s;
+        int32_t* out = spans ? spans + ((size_t)b * S + s) * rows : nullptr;
+        post_t acc = 0;                              // sum of beta r over the chosen splits
+        int sp = 0, cnt = 0;
+        stk[0] = n - 1; stk[1] = 0; stk[2] = 0; stk[3] = 0;
+        while (sp >= 0) {
+            const int level = stk[4 * sp], pos = stk[4 * sp + 1], phase = stk[4 * sp + 2];
+            if (level == 0) { --sp; continue; }
+            if (phase == 0) {                        // draw the cell's split
+                const bool an = lane < level, an1 = LONG && lane + 64 < level;
+                float sc, sc1;
+                const float smax = load_split_scores<LONG>(Sp + (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level, level,
+                                                           lane, sc, sc1);
+                const post_t here = al[coff(level) + pos];
+                post_t br0 = 0, br1 = 0, w0 = 0, w1 = 0;
+                if (an) {
+                    br0 = beta * ((post_t)sc - (post_t)smax);
+                    w0 = exp(al[coff(lane) + pos] + al[coff(level - lane - 1) + pos + lane + 1] + br0 - here);
+                }
+                if (an1) {
+                    br1 = beta * ((post_t)sc1 - (post_t)smax);
+                    w1 = exp(al[coff(lane + 64) + pos] + al[coff(level - lane - 65) + pos + lane + 65] + br1 - here);
+                }
+                const post_t c0 = post_wave_scan(w0, lane);
+                post_t total = __shfl(c0, 63);       // lanes without a split add 0: lane 63 holds c_{N-1} of its half
+                post_t c1 = 0;
+                if constexpr (LONG) { c1 = total + post_wave_scan(w1, lane); total = __shfl(c1, 63); }
+                const post_t u = philox_uniform(make_uint4((uint32_t)(level * 256 + pos), (uint32_t)sample, (uint32_t)(sample >> 32), sid), seed);
+                const post_t thr = u * total;
+                int k = __popcll(__ballot(an && c0 <= thr));
+                if constexpr (LONG) k += __popcll(__ballot(an1 && c1 <= thr));
+                k = k < level - 1 ? k : level - 1;
+                const post_t r0 = __shfl(br0, k & 63);
+                post_t r1 = 0;
+                if constexpr (LONG) r1 = __shfl(br1, k & 63);
+                acc += k < 64 ? r0 : r1;
+                stk[4 * sp + 2] = 1; stk[4 * sp + 3] = k;
+                ++sp; stk[4 * sp] = k; stk[4 * sp + 1] = pos; stk[4 * sp + 2] = 0; stk[4 * sp + 3] = 0;
+            } else if (phase == 1) {
+                const int k = stk[4 * sp + 3];
+                stk[4 * sp + 2] = 2;
+                ++sp; stk[4 * sp] = level - k - 1; stk[4 * sp + 1] = pos + k + 1; stk[4 * sp + 2] = 0; stk[4 * sp + 3] = 0;
+            } else {
+                if (lane == 0) { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; }
+                ++cnt; --sp;
+            }
+        }
+        if (lane == 0) log_prob[(size_t)b * S + s] = (float)(acc - lz);
+    }
+}
+
+// Dynamic LDS of the kernel for a chart of length L: 8 C + 4 L + POST_WAVES * 16 (L + 1) bytes, 81 KiB at L 128.
+static inline size_t sample_trees_lds(int L, int C) {
+    return (size_t)C * sizeof(post_t) + ((size_t)L + (size_t)POST_WAVES * 4 * ((size_t)L + 1)) * sizeof(int32_t);
+}
+
+}  // namespace cliora

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "philox.hpp"
+
 namespace cliora {
 
 constexpr int NEG_LDS_BINS = 16384;      // token counts: V up to this is privatised in LDS (64 KiB of uint32)
@@ -63,25 +65,10 @@ __global__ __launch_bounds__(256) void token_count_float_kernel(int V, float* co
     if (i < V) counts[i] = (float)reinterpret_cast<const uint32_t*>(counts)[i];
 }
 
-// ---- Philox4x32-10 ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
-// bits of E = -log(u) / w for id `id` of draw d: u = (m + 0.5) 2^-53 with m the top 53 bits of the first two Philox words.  A zero
+// bits of E = -log(u) / w for id `id` of draw d: u = philox_uniform (philox.hpp) at counter (id, d_lo, d_hi, stream).  A zero
 // E (u rounded to 1) is +0, so that it orders first; w = 0 gives +inf (never among the k smallest while k <= the positive weights).
 __device__ __forceinline__ uint64_t neg_race_key(uint32_t id, uint64_t d, uint32_t stream_id, uint64_t seed, float w) {
-    const uint4 x = philox4x32_10(make_uint4(id, (uint32_t)d, (uint32_t)(d >> 32), stream_id), (uint32_t)seed, (uint32_t)(seed >> 32));
-    const uint64_t m = ((uint64_t)(x.x >> 5) << 26) | (uint64_t)(x.y >> 6);
-    const double u = ((double)m + 0.5) * 0x1p-53;
+    const double u = philox_uniform(make_uint4(id, (uint32_t)d, (uint32_t)(d >> 32), stream_id), seed);
     double e = -log(u) / (double)w;
     if (e == 0.0) e = 0.0;
     return (uint64_t)__double_as_longlong(e);

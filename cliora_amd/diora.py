@@ -507,6 +507,23 @@ class DioraBase(nn.Module):
         count = host[nsp + kb.scores.numel():]
         return [list(zip(self.trees_from_spans(spans[b, :count[b]]), scores[b, :count[b]].tolist())) for b in range(len(count))]
 
+    def sample_spans_device(self, S, seed, lengths=None, ids=None, first_sample=0, beta=1.0):
+        """S trees per sentence drawn from the posterior over parses of the last forward, the distribution whose mode is cky()
+        (cliora_amd.sample.sample_spans): -> TreeSamples(spans (B, S, L-1, 2), log_prob (B, S), log_z (B,),
+        status).  Device tensors."""
+        from . import sample
+        return sample.sample_spans(self, S, seed, lengths=lengths, ids=ids, first_sample=first_sample, beta=beta)
+
+    def sample_trees(self, S, seed, beta=1.0):
+        """Per sentence the list of its S sampled (tree, log_prob): nested tuples of word positions as cky() returns them, each with
+        the log of its probability under the distribution it was drawn from.  One device-to-host copy."""
+        ts = self.sample_spans_device(S, seed, beta=beta)
+        nsp = ts.spans.numel()
+        host = torch.cat([ts.spans.reshape(-1), ts.log_prob.view(torch.int32).reshape(-1)]).cpu().numpy()    # one copy
+        spans = host[:nsp].reshape(ts.spans.shape)
+        log_prob = host[nsp:].view('float32').reshape(ts.log_prob.shape)
+        return [list(zip(self.trees_from_spans(spans[b]), log_prob[b].tolist())) for b in range(spans.shape[0])]
+
 
 class DioraMLP(DioraBase):
     def init_parameters(self):

@@ -249,6 +249,28 @@ def oracle_f1(spans_k, count, gold):
                 corpus_f1=first.corpus_f1, sent_f1=mean(first))
 
 
+def expected_f1(spans_s, gold):
+    """Expected span F1 under sampled trees, on the host.  spans_s (B, S, L-1, 2): the trees of cliora_amd.sample (an array or a
+    tensor; (-1, -1) rows are padding); gold: per sentence its constituents, the root excluded.  Each sample is counted as
+    ``oracle_f1`` counts a tree -- span sets, the predicted root (its last row) dropped -- and a sentence's figure is the mean of its
+    samples' sentence F1: a Monte-Carlo estimate of the expectation of F1 under the distribution the trees were drawn from.
+    -> dict: sentence (per sentence; nan for one without a sampled tree, which is skipped) and expected_sent_f1, their mean."""
+    spans_s = spans_s.cpu().numpy() if isinstance(spans_s, torch.Tensor) else np.asarray(spans_s)
+    sentence = []
+    for b in range(spans_s.shape[0]):
+        g = set((int(s), int(e)) for s, e in gold[b])
+        one = SpanF1()
+        for t in range(spans_s.shape[1]):
+            rows = [tuple(r) for r in spans_s[b, t].tolist() if r[0] >= 0]
+            if not rows:
+                continue
+            pred = set(rows[:-1])
+            one.add_counts(len(pred & g), len(pred), len(g))
+        sentence.append(float(np.mean(np.array(one.sentence))) if one.sentence else float('nan'))
+    kept = [f for f in sentence if f == f]
+    return dict(sentence=sentence, expected_sent_f1=float(np.mean(np.array(kept))) if kept else float('nan'))
+
+
 def batch_records(res, trees, sentences, example_ids, idx2word, with_boxes, post=False):
     """The batch's parse.jsonl lines (parse.py:215-280).  pred_spans / gold_spans in the iteration order of the reference's Python
     sets, built the same way (from the span list in reduce order, from GT[b][:-1]); pred_boxes in the order of pred_spans."""

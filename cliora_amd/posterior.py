@@ -99,6 +99,21 @@ def _logsumexp(x):
     return m + np.log(np.exp(x - m).sum())
 
 
+def inside_numpy(pair_s, b, n, beta=1.0):
+    """Sentence b's first n words in fp64: -> (r[level, pos, split] = s - max_k s, al[level, pos] = the inside table under beta r;
+    beta = 1: the posteriors', other values: cliora_amd.sample)."""
+    r = np.zeros((n, n, max(n, 1)), dtype=np.float64)
+    al = np.zeros((n, n), dtype=np.float64)
+    for level in range(1, n):
+        s = np.asarray(pair_s[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
+        r[level, :n - level, :level] = s - s.max(axis=1, keepdims=True)
+        k = np.arange(level)
+        for pos in range(n - level):
+            t = al[k, pos] + al[level - k - 1, pos + k + 1] + beta * r[level, pos, :level]
+            al[level, pos] = _logsumexp(t)
+    return r, al
+
+
 def posterior_numpy(pair_s, lengths, L=None):
     """The posteriors restated in fp64 from the definitions, for tests: `pair_s[level]` (B, L - level, level[, 1]) are the per-split
     inside scores of the (padded) chart of length L (inferred from level 1 when not given), sentence b its first lengths[b] words.
@@ -111,15 +126,7 @@ def posterior_numpy(pair_s, lengths, L=None):
     mu = np.zeros((len(lengths), Cc), dtype=np.float64)
     log_z = np.zeros(len(lengths), dtype=np.float64)
     for b, n in enumerate(lengths):
-        r = np.zeros((n, n, n), dtype=np.float64)                       # [level, pos, split]
-        for level in range(1, n):
-            s = np.asarray(pair_s[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
-            r[level, :n - level, :level] = s - s.max(axis=1, keepdims=True)
-        al = np.zeros((n, n), dtype=np.float64)
-        for level in range(1, n):
-            k = np.arange(level)
-            for pos in range(n - level):
-                al[level, pos] = _logsumexp(al[k, pos] + al[level - k - 1, pos + k + 1] + r[level, pos, :level])
+        r, al = inside_numpy(pair_s, b, n)
         be = np.zeros((n, n), dtype=np.float64)
         for level in range(n - 2, -1, -1):
             for pos in range(n - level):

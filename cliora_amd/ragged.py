@@ -328,6 +328,38 @@ def parse_ragged_kbest(net, sentences, k, max_batch=64, max_waste=DEFAULT_MAX_WA
     return out
 
 
+def parse_ragged_samples(net, sentences, S, seed, beta=1.0, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None,
+                         max_len=MAX_L_INSIDE):
+    """S binary trees of every sentence drawn from its posterior over parses (cliora_amd.sample), in the caller's order: per sentence
+    the list of its S (tree, log_prob) -- nested tuples as ``parse_ragged`` returns them, ``[(0, 0.0)] * S`` for a single word.  A
+    sentence's id in the draw is its index in `sentences`, so its samples do not depend on the pack it lands in.  Packs like
+    ``parse_ragged`` and runs the inside pass only, so sentences of up to 128 words are taken (max_len).  One device-to-host copy
+    per pack."""
+    from . import sample
+    diora = net.diora
+    out = [None] * len(sentences)
+    S = int(S)
+    if not 1 <= S <= sample.MAX_S:                   # refused before any pack has run
+        raise ValueError('S must be in 1..%d' % sample.MAX_S)
+    if not (beta >= 0 and np.isfinite(beta)):
+        raise ValueError('beta must be finite and >= 0')
+
+    def decode_pack(idx, lens):
+        ts = sample.sample_spans(diora, S, seed, lens, ids=torch.tensor(idx, dtype=torch.int32), beta=beta)
+        nsp, nlp = ts.spans.numel(), ts.log_prob.numel()
+        host = torch.cat([ts.spans.reshape(-1), ts.log_prob.view(torch.int32).reshape(-1), ts.status]).cpu().numpy()
+        if host[nsp + nlp:].any():
+            raise _lib.ChartLibError('cliora_sample_trees rejected %d sentence length(s)' % int(host[nsp + nlp:].sum()))
+        rows = host[:nsp].reshape(ts.spans.shape)
+        log_prob = host[nsp:nsp + nlp].view(np.float32).reshape(ts.log_prob.shape)
+        for b, i in enumerate(idx):
+            trees = diora.trees_from_spans(rows[b, :, :len(sentences[i]) - 1])
+            out[i] = list(zip(trees, log_prob[b].tolist()))
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
+    return out
+
+
 def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L):
     """(N, D) fp32 on the device: row i = inside_h of sentence i's root cell (its own length's root, not the padded chart's), the
     vector DIORA users read off the root.  Same plumbing as parse_ragged, max_len included."""

@@ -358,6 +358,35 @@ int cliora_span_posteriors(cliora_plan* plan, void* fwd_workspace, const int32_t
 size_t cliora_kbest_scratch_bytes(const cliora_plan* plan, int K);
 int cliora_kbest_spans(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, int K, int32_t* spans_out, float* scores_out,
                        int32_t* count_out, void* scratch, int32_t* status, void* stream);
+/* Binary trees SAMPLED from the distribution whose mode is cliora_cky_spans' tree and whose marginals cliora_span_posteriors returns:
+ * r[cell, k] = score[cell, k] - max_k score[cell, .], scaled by an inverse temperature beta >= 0, so a tree weighs exp(beta * sum of
+ * r over its internal cells) -- beta = 1 is that posterior, beta = 0 is uniform over the Catalan(n - 1) trees.  Per sentence of n
+ * words:
+ *   inside   a[leaf] = 0,  a[cell] = logsumexp_k(a[left] + a[right] + beta r[cell, k]) in fp64, beta r formed in fp64;
+ *            log_z = a[(n-1, 0)] -- at beta = 1 the log_z of cliora_span_posteriors, bit for bit.
+ *   draws    sample s walks from the root; at an internal cell (level, pos) with N = level splits,
+ *              w_k = exp(a[left_k] + a[right_k] + beta r_k - a[cell]),  c_k = w_0 + .. + w_k,
+ *              split = the number of k with c_k <= u c_{N-1}, clamped to N - 1,
+ *              u = (m + 0.5) 2^-53, m = (x0 >> 5) 2^26 + (x1 >> 6), x = Philox4x32-10 of counter (level * 256 + pos, sample_lo,
+ *              sample_hi, sentence id) under key (seed_lo, seed_hi): the uniform of cliora_neg_sample.
+ *            So a draw depends on (seed, sentence id, sample index, cell) and the sentence's scores alone -- not on B, the padding,
+ *            the pack a sentence landed in, or how a caller chunks S.  Sample index = first_sample + s.
+ *   lengths (B) int32 device, or NULL: every sentence has L words.  Otherwise the sentences share a right-padded chart, with the
+ *     rules of cliora_cky_spans_ragged: `status` (an int32 on the device, zeroed by the call) is required and counts the lengths
+ *     outside [1, L]; such a sentence gets every row -1, log_prob 0, log_z 0, and none of its scores is read.  With every length
+ *     equal to L the outputs are bitwise those of the lengths == NULL call.  status may be NULL when lengths is.
+ *   ids (B) int32 device, or NULL: the caller's sentence numbers (NULL: sentence id = b), so that a sentence keeps its draws
+ *     wherever a pack puts it.
+ *   spans_out (B, S, L-1, 2) (may be NULL when L = 1): sample s's n - 1 spans in cliora_cky_spans' order, the root last; (-1, -1)
+ *     beyond.  log_prob_out (B, S) fp32: beta * (sum of r over the chosen splits) - log_z, summed in fp64.  log_z_out (B) fp32.
+ * One workgroup per sentence, a wavefront per sample, fixed-order scans, no floating-point atomics: two calls give equal bits.  The
+ * tables fit the LDS up to L = 128 (81 KiB there): no scratch.  Every plan cliora_cky_spans takes is taken: long plans, padded
+ * charts, TreeLSTM plans.  Refused with CLIORA_EINVAL and a message, before any launch: S outside 1 .. 2^20; beta negative or not
+ * finite; a NULL plan, workspace, log_prob_out or log_z_out; NULL spans_out with L > 1; lengths without status; a plan that has not
+ * run a forward. */
+int cliora_sample_trees(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* ids, int S, uint64_t seed,
+                        uint64_t first_sample, float beta, int32_t* spans_out, float* log_prob_out, float* log_z_out, int32_t* status,
+                        void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
