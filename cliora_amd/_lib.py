@@ -82,6 +82,7 @@ ABI = {
     'cliora_kbest_scratch_bytes': (sz, [vp, i32]),
     'cliora_kbest_spans': (i32, [vp, vp, vp, i32] + [vp] * 6),
     'cliora_sample_trees': (i32, [vp, vp, vp, vp, i32, u64, u64, f32] + [vp] * 5),
+    'cliora_constrained_parse': (i32, [vp, vp, vp, vp, i32] + [vp] * 9),
     'cliora_ground_eval': (i32, [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_ground_eval_ragged': (i32, [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_phrase_gather': (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp, i64, i64, vp, vp]),

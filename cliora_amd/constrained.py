@@ -1,0 +1,247 @@
+"""Parsing under required and forbidden brackets (cliora_constrained_parse).
+
+``DioraBase.cky``, ``posterior.span_posteriors``, ``kbest.kbest_spans`` and ``sample.sample_spans`` answer questions about the
+unconditioned distribution over trees, which weighs a tree exp(sum of r over its internal cells), r[cell, k] = s[cell, k] - max_k
+s[cell, .].  This conditions it on what the caller knows about the sentence (include/cliora_chart.h): spans that
+must be constituents -- the annotated phrases of a caption, a partial bracketing -- and spans that must not be.  Per sentence: the
+best tree that qualifies, ``log_prob`` = log_z_c - log_z, the log of the joint probability that every bracket holds at once (which the
+per-span marginals cannot give), and the span posteriors given the brackets.  The reference has no counterpart.
+
+    req = brackets_from_entity_labels(batch_map['entity_labels'])       # per sentence [(start, end)], crossing phrases dropped
+    cp = constrained_parse(net.diora, pack_brackets(req), marginals=True)    # after a forward; device tensors, nothing synchronised
+    trees = net.diora.cky_constrained(req)                              # nested tuples as net.diora.cky(), None where infeasible
+
+A cell [i, j] is allowed iff it crosses no required bracket [s, e] (i < s <= j < e or s < i <= e < j) and equals no forbidden one; in
+a binary tree "nothing crosses [s, e]" is "[s, e] is a constituent", so the qualifying trees are the trees built from allowed cells.
+``constrained_numpy`` restates the kernel for tests: the best tree in fp32 in the kernel's operation order, the rest in fp64 from the
+definitions.
+"""
+import collections
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr_or_null as _p, stream as _stream
+from .diora import span_buffer
+from .posterior import cell_id, cell_uses
+
+MAX_M = 256              # csrc/constrained_kernels.hpp CON_MAX_M: bracket rows per sentence
+REQUIRED, FORBIDDEN = 1, 0
+
+# spans (B, L-1, 2) int32 -- the best qualifying tree's n - 1 spans in cky_spans' order, (-1, -1) beyond and where there is none;
+# score (B,) fp32 -- the sum of its potentials, as KBest.scores; log_z, log_z_c, log_prob (B,) fp32; feasible (B,) int32; marginals
+# (B, C) fp32 or None; status (number of workspaces,) int32 -- sentences with a bad length or a bad row, which the caller must check.
+# Device tensors; nothing is synchronised.  (constrained_numpy: the same fields as numpy arrays, fp64 but spans and score; status an int.)
+ConstrainedParse = collections.namedtuple('ConstrainedParse', 'spans score log_z log_z_c log_prob feasible marginals status')
+
+
+def pack_brackets(required, forbidden=None, M=None):
+    """Per-sentence lists of (start, end) -- inclusive word positions -- -> the int32 (B, M, 3) tensor of rows (start, end, kind) that
+    cliora_constrained_parse takes: a sentence's required spans (kind 1), then its forbidden ones (kind 0), then (-1, -1, -1) rows.
+    M: rows per sentence (default: the most any sentence needs); at most 256."""
+    required = [list(r) for r in required]
+    forbidden = [[] for _ in required] if forbidden is None else [list(f) for f in forbidden]
+    if len(forbidden) != len(required):
+        raise ValueError('required holds %d sentences, forbidden %d' % (len(required), len(forbidden)))
+    need = max([len(r) + len(f) for r, f in zip(required, forbidden)] or [0])
+    M = need if M is None else int(M)
+    if M < need:
+        raise ValueError('M = %d, but a sentence has %d brackets' % (M, need))
+    if not 0 <= M <= MAX_M:
+        raise ValueError('M must be in 0..%d' % MAX_M)
+    out = torch.full((len(required), M, 3), -1, dtype=torch.int32)
+    for b, (req, forb) in enumerate(zip(required, forbidden)):
+        rows = [(int(s), int(e), REQUIRED) for s, e in req] + [(int(s), int(e), FORBIDDEN) for s, e in forb]
+        if rows:
+            out[b, :len(rows)] = torch.tensor(rows, dtype=torch.int32)
+    return out
+
+
+def crosses(a, b):
+    """Whether spans a = (i, j) and b = (s, e) cross: they overlap and neither holds the other."""
+    (i, j), (s, e) = a, b
+    return i < s <= j < e or s < i <= e < j
+
+
+def brackets_from_entity_labels(entity_labels, min_size=2, drop_crossing=True):
+    """batch_map['entity_labels'] -> per sentence the list of its phrases as (start, end): a (label, pos, size) entry is the span
+    (pos, pos + size - 1); ``None`` entries are skipped and sizes below `min_size` dropped, as ``phrases.entity_rows`` does; a phrase
+    listed twice is kept once.  drop_crossing: keep the first-come laminar subset -- a phrase that crosses one kept before it is
+    dropped, so the required set is never infeasible by itself."""
+    out = []
+    for lst in entity_labels:
+        keep = []
+        for el in lst:
+            if el is None:
+                continue
+            pos, size = int(el[1]), int(el[2])
+            span = (pos, pos + size - 1)
+            if size < min_size or span in keep:
+                continue
+            if drop_crossing and any(crosses(span, k) for k in keep):
+                continue
+            keep.append(span)
+        out.append(keep)
+    return out
+
+
+def constrained_parse(diora, brackets, lengths=None, marginals=False, out=None):
+    """cliora_constrained_parse on a chart module after its forward.  brackets: an int32 tensor (B, M, 3) of rows (start, end, kind)
+    (``pack_brackets``), or None for no bracket at all.  lengths: None (every sentence has L words) or an int32 tensor (B,) for a
+    right-padded batch.  marginals: also run the outside pass.  out: a contiguous int32 tensor (B, L-1, 2) on the chart's device to
+    decode the spans into.  -> ConstrainedParse."""
+    plan = diora._plan
+    B, L, Cc = plan.B, plan.L, plan.C
+    spans, parts = span_buffer(diora, out)
+    nws = len(parts)
+    dev = spans.device
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
+        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
+    M = 0
+    if brackets is not None:
+        if brackets.dtype != torch.int32 or brackets.dim() != 3 or brackets.shape[0] != B * nws or brackets.shape[2] != 3:
+            raise ValueError('brackets must be int32 (%d, M, 3)' % (B * nws))
+        M = int(brackets.shape[1])                         # a bad M is the library's to refuse, with its message
+    with torch.cuda.device(dev):
+        if lengths is not None:
+            lengths = lengths.to(dev).contiguous()
+        if brackets is not None:
+            brackets = brackets.to(dev).contiguous()
+        score, log_z, log_zc, log_prob = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(4))
+        feasible = torch.empty(B * nws, dtype=torch.int32, device=dev)
+        marg = torch.empty((B * nws, Cc), dtype=torch.float32, device=dev) if marginals else None
+        status = torch.zeros(nws, dtype=torch.int32, device=dev)
+        for i, (ws, sl) in enumerate(parts):
+            _lib.call('cliora_constrained_parse', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
+                      _p(brackets[sl]) if M else None, M, _p(spans[sl]), _p(score[sl]), _p(log_z[sl]), _p(log_zc[sl]),
+                      _p(log_prob[sl]), _p(feasible[sl]), _p(marg[sl]) if marginals else None,
+                      C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    return ConstrainedParse(spans, score, log_z, log_zc, log_prob, feasible, marg, status)
+
+
+def host_results(cp):
+    """A ConstrainedParse's spans, feasible, log_prob and status in ONE device-to-host copy: -> (spans (B, L-1, 2) int32, feasible (B,)
+    int32, log_prob (B,) float32, the number of rejected sentences)."""
+    nsp, nb = cp.spans.numel(), cp.feasible.numel()
+    host = torch.cat([cp.spans.reshape(-1), cp.feasible, cp.log_prob.view(torch.int32), cp.status]).cpu().numpy()
+    return (host[:nsp].reshape(cp.spans.shape), host[nsp:nsp + nb], host[nsp + nb:nsp + 2 * nb].view(np.float32),
+            int(host[nsp + 2 * nb:].sum()))
+
+
+def refuse_rejected(count):
+    """The one message for a non-zero status of cliora_constrained_parse."""
+    if count:
+        raise _lib.ChartLibError('cliora_constrained_parse rejected %d sentence(s): a length outside the chart, or a bracket that is '
+                                 'not 0 <= start <= end < length with kind 0 or 1' % count)
+
+
+# ---- the restatement --------------------------------------------------------------------------------------------------------------
+def bad_row(row, n):
+    """Whether a row (start, end, kind) is neither unused (start = -1) nor a bracket of a sentence of n words."""
+    s, e, k = (int(v) for v in row)
+    return s != -1 and not (0 <= s <= e < n and k in (REQUIRED, FORBIDDEN))
+
+
+def allowed_cells(n, rows):
+    """The definition, a test per (cell, row): -> (allowed[level, pos], required[level, pos]) bool arrays over the triangle of n words."""
+    allowed = np.zeros((n, n), dtype=bool)
+    required = np.zeros((n, n), dtype=bool)
+    rows = [tuple(int(v) for v in r) for r in rows if int(r[0]) != -1]
+    for level in range(n):
+        for pos in range(n - level):
+            span = (pos, pos + level)
+            allowed[level, pos] = not any((k == REQUIRED and crosses(span, (s, e))) or (k == FORBIDDEN and span == (s, e))
+                                          for s, e, k in rows)
+            required[level, pos] = any(k == REQUIRED and span == (s, e) for s, e, k in rows)
+    return allowed, required
+
+
+def _lse(x):
+    m = x.max() if x.size else -np.inf
+    if not m > -np.inf:
+        return -np.inf
+    return m + np.log(np.exp(x - m).sum())
+
+
+def constrained_numpy(pair_s, lengths, brackets, L=None):
+    """The kernel restated for tests: `pair_s[level]` (B, L - level, level[, 1]) are the per-split inside scores of the (padded) chart
+    of length L (inferred from level 1 when not given), sentence b its first lengths[b] words -- the layout ``posterior_numpy`` takes;
+    brackets (B, M, 3) or None.  The best tree in fp32 in the kernel's operation order (cky_kernel's candidate, first maximum wins, a
+    disallowed cell at -inf); log_z_c, log_z, log_prob and the marginals in fp64 from the definitions, with the mask by one test per
+    (cell, row).  -> ConstrainedParse of numpy arrays as the kernel writes them; status: the number of rejected sentences."""
+    lengths = [int(x) for x in lengths]
+    if L is None:
+        L = np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)
+    Bn, Cc = len(lengths), L * (L + 1) // 2
+    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
+    spans = np.full((Bn, max(L - 1, 0), 2), -1, dtype=np.int32)
+    score = np.full(Bn, -np.inf, dtype=np.float32)
+    log_z = np.zeros(Bn, dtype=np.float64)
+    log_zc = np.full(Bn, -np.inf, dtype=np.float64)
+    log_prob = np.full(Bn, -np.inf, dtype=np.float64)
+    feasible = np.zeros(Bn, dtype=np.int32)
+    mu = np.zeros((Bn, Cc), dtype=np.float64)
+    status = 0
+    ninf32 = np.float32(-np.inf)
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= L or any(bad_row(r, n) for r in brackets[b]):
+            status += 1
+            continue
+        allowed, required = allowed_cells(n, brackets[b])
+        # the best tree, fp32
+        rel, val, bp = {}, np.full((n, n), ninf32, dtype=np.float32), {}
+        val[0, :n] = np.where(allowed[0, :n], np.float32(1.0), ninf32)
+        for level in range(1, n):
+            s = np.asarray(pair_s[level][b], dtype=np.float32).reshape(-1, level)[:n - level]
+            rel[level] = s - s.max(axis=1, keepdims=True)
+            k = np.arange(level)
+            for pos in range(n - level):
+                if not allowed[level, pos]:
+                    continue
+                cand = (val[k, pos] + val[level - k - 1, pos + k + 1]) + rel[level][pos]
+                bp[(level, pos)] = int(np.argmax(cand))
+                val[level, pos] = cand[bp[(level, pos)]]
+        # the sums, fp64
+        r = {}
+        al, au = np.full((n, n), -np.inf), np.zeros((n, n))
+        al[0, :n] = np.where(allowed[0, :n], 0.0, -np.inf)
+        for level in range(1, n):
+            s = np.asarray(pair_s[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
+            r[level] = s - s.max(axis=1, keepdims=True)
+            k = np.arange(level)
+            for pos in range(n - level):
+                au[level, pos] = _lse(au[k, pos] + au[level - k - 1, pos + k + 1] + r[level][pos])
+                if allowed[level, pos]:
+                    al[level, pos] = _lse(al[k, pos] + al[level - k - 1, pos + k + 1] + r[level][pos])
+        log_z[b], log_zc[b] = au[n - 1, 0], al[n - 1, 0]
+        log_prob[b] = log_zc[b] - log_z[b]
+        if not val[n - 1, 0] > ninf32:
+            continue
+        feasible[b] = 1
+        score[b] = val[n - 1, 0] - np.float32(n)
+        rows, stack = [], [(n - 1, 0, 0)] if n > 1 else []
+        while stack:                                  # the kernel's walk: left subtree, right subtree, then the node
+            level, pos, phase = stack.pop()
+            if level == 0:
+                continue
+            k = bp[(level, pos)]
+            if phase == 0:
+                stack += [(level, pos, 1), (k, pos, 0)]
+            elif phase == 1:
+                stack += [(level, pos, 2), (level - k - 1, pos + k + 1, 0)]
+            else:
+                rows.append((pos, pos + level))
+        spans[b, :len(rows)] = np.asarray(rows, dtype=np.int32).reshape(-1, 2)
+        be = np.full((n, n), -np.inf)
+        be[n - 1, 0] = 0.0
+        for level in range(n - 2, -1, -1):
+            for pos in range(n - level):
+                if allowed[level, pos]:
+                    be[level, pos] = _lse(np.array([be[pl, pp] + al[sl, sp] + r[pl][pp, k] for pl, pp, k, sl, sp in cell_uses(n, level, pos)]))
+        for level in range(n):
+            for pos in range(n - level):
+                if allowed[level, pos]:
+                    mu[b, cell_id(L, level, pos)] = 1.0 if required[level, pos] else np.exp(al[level, pos] + be[level, pos] - log_zc[b])
+    return ConstrainedParse(spans, score, log_z, log_zc, log_prob, feasible, mu, status)

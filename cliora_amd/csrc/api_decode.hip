@@ -1,11 +1,13 @@
-// C ABI, decode unit: the best tree (CKY), the K best trees, sampled trees, and the span posteriors, log-partition and MBR tree, from the per-split
-// scores of the last forward -- of every sentence of a chart, or of each sentence's own triangle of a right-padded chart.  See
-// include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY kernel, kbest_kernels.hpp for the k-best lists,
-// posterior_kernels.hpp for the sum-product model and sample_kernels.hpp for the draws from it.
+// C ABI, decode unit: the best tree (CKY), the K best trees, sampled trees, the span posteriors, log-partition and MBR tree, and the
+// parse under required and forbidden brackets, from the per-split scores of the last forward -- of every sentence of a chart, or of
+// each sentence's own triangle of a right-padded chart.  See include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY
+// kernel, kbest_kernels.hpp for the k-best lists, posterior_kernels.hpp for the sum-product model, sample_kernels.hpp for the draws
+// from it and constrained_kernels.hpp for the bracket mask over both.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
 #include <cmath>
 
 #include "api_common.hpp"
+#include "constrained_kernels.hpp"
 #include "decode_kernels.hpp"
 #include "kbest_kernels.hpp"
 #include "posterior_kernels.hpp"
@@ -114,5 +116,21 @@ extern "C" int cliora_sample_trees(cliora_plan* plan, void* fwd_ws, const int32_
                          [&](auto LONG, auto&& go) {
                              return go("sample_trees_kernel", sample_trees_kernel<decltype(LONG)::value>, ids, S, seed, first_sample, beta,
                                        log_prob_out, log_z_out);
+                         });
+}
+
+// Every table of the kernel fits the CU's LDS up to L = 128 and M = 256 (constrained_kernels.hpp: 143 KiB there): no scratch, no query.
+extern "C" int cliora_constrained_parse(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, const int32_t* brackets, int M,
+                                        int32_t* spans_out, float* score_out, float* log_z_out, float* log_zc_out, float* log_prob_out,
+                                        int32_t* feasible_out, float* marginals, int32_t* status, void* stream) {
+    if (M < 0 || M > CON_MAX_M) return fail(CLIORA_EINVAL, "cliora_constrained_parse: M outside 0..256");
+    if (!plan || !fwd_ws || !score_out || !log_z_out || !log_zc_out || !log_prob_out || !feasible_out || !status)
+        return fail(CLIORA_EINVAL, "cliora_constrained_parse: NULL argument");
+    if (!spans_out && plan->p.L > 1) return fail(CLIORA_EINVAL, "cliora_constrained_parse: NULL spans_out");
+    if (!brackets && M > 0) return fail(CLIORA_EINVAL, "cliora_constrained_parse: NULL brackets");
+    return launch_decode(plan, fwd_ws, "constrained_parse", POST_WAVES, [M](int L, int C) { return constrained_lds(L, C, M); }, lengths,
+                         nullptr, spans_out, status, stream, [&](auto LONG, auto&& go) {
+                             return go("constrained_kernel", constrained_kernel<decltype(LONG)::value>, brackets, M, score_out, log_z_out,
+                                       log_zc_out, log_prob_out, feasible_out, marginals);
                          });
 }

@@ -524,6 +524,27 @@ class DioraBase(nn.Module):
         log_prob = host[nsp:].view('float32').reshape(ts.log_prob.shape)
         return [list(zip(self.trees_from_spans(spans[b]), log_prob[b].tolist())) for b in range(spans.shape[0])]
 
+    def cky_constrained(self, required, forbidden=None):
+        """Best binary tree per sentence among those that keep every span of required[b] as a constituent and none of forbidden[b]
+        (per-sentence lists of (start, end), inclusive word positions; cliora_amd.constrained): nested tuples
+        as cky() returns them, None for a sentence no tree qualifies for.  One device-to-host copy."""
+        from . import constrained
+        cp = constrained.constrained_parse(self, constrained.pack_brackets(required, forbidden))
+        spans, feasible, _, rejected = constrained.host_results(cp)
+        constrained.refuse_rejected(rejected)
+        return [self.trees_from_spans(spans[b:b + 1])[0] if feasible[b] else None for b in range(len(feasible))]
+
+    def bracket_log_prob(self, required, forbidden=None):
+        """Per sentence the log of the probability, under the posterior over parses of the last forward, that every span of
+        required[b] is a constituent and none of forbidden[b] is -- jointly, which the per-span marginals cannot give: a list of
+        floats <= 0, -inf where no tree qualifies.  One device-to-host copy."""
+        from . import constrained
+        cp = constrained.constrained_parse(self, constrained.pack_brackets(required, forbidden))
+        host = torch.cat([cp.log_prob.view(torch.int32), cp.status]).cpu().numpy()
+        nb = cp.log_prob.numel()
+        constrained.refuse_rejected(int(host[nb:].sum()))
+        return host[:nb].view('float32').tolist()
+
 
 class DioraMLP(DioraBase):
     def init_parameters(self):

@@ -360,6 +360,36 @@ def parse_ragged_samples(net, sentences, S, seed, beta=1.0, max_batch=64, max_wa
     return out
 
 
+def parse_ragged_constrained(net, sentences, required, forbidden=None, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None,
+                             max_len=MAX_L_INSIDE):
+    """The best binary tree of every sentence under its brackets (cliora_amd.constrained), in the caller's order: per sentence
+    (tree, log_prob) -- the tree nested tuples as ``parse_ragged`` returns them (0 for a single word), None when no tree keeps every
+    span of required[i] and none of forbidden[i] (per-sentence lists of (start, end), inclusive word positions); log_prob the log of
+    the joint probability of the brackets under the sentence's posterior over parses, -inf with None.  A sentence's result does not
+    depend on the pack it lands in.  Packs like ``parse_ragged`` and runs the inside pass only, so sentences of up to 128 words are
+    taken (max_len).  One device-to-host copy per pack; a bracket outside its sentence raises ChartLibError."""
+    from . import constrained
+    diora = net.diora
+    out = [None] * len(sentences)
+    required = [list(r) for r in required]
+    forbidden = [[] for _ in sentences] if forbidden is None else [list(f) for f in forbidden]
+    if len(required) != len(sentences) or len(forbidden) != len(sentences):      # refused before any pack has run
+        raise ValueError('required and forbidden hold one list of spans per sentence (%d)' % len(sentences))
+    if max([len(r) + len(f) for r, f in zip(required, forbidden)] or [0]) > constrained.MAX_M:
+        raise ValueError('at most %d brackets per sentence' % constrained.MAX_M)
+
+    def decode_pack(idx, lens):
+        brackets = constrained.pack_brackets([required[i] for i in idx], [forbidden[i] for i in idx])
+        spans, feasible, log_prob, rejected = constrained.host_results(constrained.constrained_parse(diora, brackets, lens))
+        constrained.refuse_rejected(rejected)
+        for b, i in enumerate(idx):
+            tree = diora.trees_from_spans(spans[b:b + 1, :len(sentences[i]) - 1])[0] if feasible[b] else None
+            out[i] = (tree, float(log_prob[b]))
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
+    return out
+
+
 def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L):
     """(N, D) fp32 on the device: row i = inside_h of sentence i's root cell (its own length's root, not the padded chart's), the
     vector DIORA users read off the root.  Same plumbing as parse_ragged, max_len included."""

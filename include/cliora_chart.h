@@ -387,6 +387,41 @@ int cliora_kbest_spans(cliora_plan* plan, void* fwd_workspace, const int32_t* le
 int cliora_sample_trees(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* ids, int S, uint64_t seed,
                         uint64_t first_sample, float beta, int32_t* spans_out, float* log_prob_out, float* log_z_out, int32_t* status,
                         void* stream);
+/* Parsing under REQUIRED and FORBIDDEN brackets: the best tree, the log-partition and the span posteriors over the binary trees that
+ * keep every required span as a constituent and no forbidden one -- the distribution of cliora_span_posteriors conditioned on what
+ * the caller knows (annotated phrases, a partial bracketing).  The potentials are unchanged: r[cell, k] = score[cell, k] - max_k
+ * score[cell, .], the maximum over every split of the cell, so constrained and unconstrained weights share one scale (DESIGN.md
+ * section 19).  A cell [i, j] is ALLOWED iff it crosses no required bracket [s, e] (i < s <= j < e or s < i <= e < j) and equals no
+ * forbidden one; in a binary tree "nothing crosses [s, e]" is "[s, e] is a constituent", so the qualifying trees are the trees built
+ * from allowed cells.  Per sentence of n words:
+ *   best tree  cliora_cky_spans' recurrence with a disallowed cell at -inf: val[leaf] = 1.0f, candidate (val_l + val_r) + (s_k - smax)
+ *              in fp32 in that order, first maximum wins; score = val[root] - (float)n, as cliora_kbest_spans reports it.
+ *   log_zc     cliora_span_posteriors' inside recurrence in fp64 over the allowed cells; log_z: the unconstrained one, bit for bit
+ *              the log_z of cliora_span_posteriors; log_prob = log_zc - log_z, formed in fp64: the log of the joint probability that
+ *              every bracket holds (<= 0).
+ *   marginals  mu_c[cell] = exp(a_c + b_c - log_zc) by the outside recurrence over the allowed cells: the span posteriors given the
+ *              brackets, exactly 0 on a disallowed cell and 1 on a required one.
+ *   brackets (B, M, 3) int32 device, M in 0 .. 256 (NULL when M = 0): rows (start, end, kind) of inclusive word positions as in
+ *     spans_out; kind 1 = required, kind 0 = forbidden; a row with start = -1 is unused.  A required leaf or root changes nothing.
+ *   lengths (B) int32 device, or NULL: every sentence has L words.  Otherwise the sentences share a right-padded chart, with the
+ *     rules of cliora_cky_spans_ragged.  With every length equal to L the outputs are bitwise those of the lengths == NULL call.
+ *   status: an int32 on the device, zeroed by the call, always required: it counts the sentences with a length outside [1, L] or with
+ *     a row that is neither unused nor 0 <= start <= end < n with kind 0 or 1, each once.  Such a sentence is not decoded: every row
+ *     -1, feasible 0, log_z 0, score / log_zc / log_prob -inf, marginals 0, and none of its scores is read.
+ *   spans_out (B, L-1, 2) (may be NULL when L = 1): the n - 1 spans in cliora_cky_spans' order, the root last, (-1, -1) beyond.
+ *     score_out, log_z_out, log_zc_out, log_prob_out (B) fp32; feasible_out (B) int32.  marginals (B, C) fp32 in the cell order of
+ *     inside_s, exactly 0 outside a sentence's triangle, or NULL: the outside pass is skipped.
+ *   No qualifying tree (crossing required brackets, a span both required and forbidden, a forbidden leaf or root) is no error:
+ *     feasible 0, every row -1, score / log_zc / log_prob -inf, log_z the real value, marginals 0, nothing counted.
+ * Without a disallowed cell the spans are those of cliora_cky_spans, log_z, log_zc and the marginals those of cliora_span_posteriors,
+ * bit for bit, and log_prob is 0.  One workgroup per sentence, fixed-order reductions, no floating-point atomics: two calls give
+ * equal bits.  The tables fit the LDS up to L = 128 (143 KiB there): no scratch.  Every plan cliora_cky_spans takes is taken: long
+ * plans, padded charts, TreeLSTM plans.  Refused with CLIORA_EINVAL and a message, before any launch: M outside 0 .. 256; a NULL
+ * plan, workspace, scalar output, feasible_out or status; NULL spans_out with L > 1; NULL brackets with M > 0; a plan that has not
+ * run a forward. */
+int cliora_constrained_parse(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* brackets, int M,
+                             int32_t* spans_out, float* score_out, float* log_z_out, float* log_zc_out, float* log_prob_out,
+                             int32_t* feasible_out, float* marginals, int32_t* status, void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
