@@ -50,6 +50,7 @@ ABI = {
     'cliora_plan_table': (i32, [vp, C.c_char_p, C.POINTER(C.POINTER(C.c_int32)), psz]),
     'cliora_chart_forward': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp]),
     'cliora_chart_backward': (i32, [vp, pp] + [vp] * 11 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
+    'cliora_chart_backward_split': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_forward_ragged': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
     'cliora_lstm_forward': (i32, [vp, pp] + [vp] * 7 + [vp, sz, i32, vp]),
     'cliora_lstm_backward': (i32, [vp, pp] + [vp] * 13 + [vp, sz, vp, sz, vp, pp, i32, vp]),
@@ -83,6 +84,8 @@ ABI = {
     'cliora_kbest_spans': (i32, [vp, vp, vp, i32] + [vp] * 6),
     'cliora_sample_trees': (i32, [vp, vp, vp, vp, i32, u64, u64, f32] + [vp] * 5),
     'cliora_constrained_parse': (i32, [vp, vp, vp, vp, i32] + [vp] * 9),
+    'cliora_plan_split_score_count': (sz, [vp]),
+    'cliora_bracket_grad': (i32, [vp, vp, vp, vp, i32] + [vp] * 6),
     'cliora_ground_eval': (i32, [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_ground_eval_ragged': (i32, [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_phrase_gather': (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp, i64, i64, vp, vp]),

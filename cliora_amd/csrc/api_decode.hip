@@ -2,11 +2,12 @@
 // parse under required and forbidden brackets, from the per-split scores of the last forward -- of every sentence of a chart, or of
 // each sentence's own triangle of a right-padded chart.  See include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY
 // kernel, kbest_kernels.hpp for the k-best lists, posterior_kernels.hpp for the sum-product model, sample_kernels.hpp for the draws
-// from it and constrained_kernels.hpp for the bracket mask over both.
+// from it, constrained_kernels.hpp for the bracket mask over both and bracket_grad_kernels.hpp for the gradient of its log-probability.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
 #include <cmath>
 
 #include "api_common.hpp"
+#include "bracket_grad_kernels.hpp"
 #include "constrained_kernels.hpp"
 #include "decode_kernels.hpp"
 #include "kbest_kernels.hpp"
@@ -132,5 +133,29 @@ extern "C" int cliora_constrained_parse(cliora_plan* plan, void* fwd_ws, const i
                          nullptr, spans_out, status, stream, [&](auto LONG, auto&& go) {
                              return go("constrained_kernel", constrained_kernel<decltype(LONG)::value>, brackets, M, score_out, log_z_out,
                                        log_zc_out, log_prob_out, feasible_out, marginals);
+                         });
+}
+
+// The inside split-score rows of a batch, level by level: what cliora_bracket_grad writes and cliora_chart_backward_split reads.
+extern "C" size_t cliora_plan_split_score_count(const cliora_plan* plan) {
+    if (!plan) return 0;
+    const Plan& p = plan->p;
+    size_t rows = 0;
+    for (int level = 1; level < p.L; ++level) rows += (size_t)level * (p.L - level);
+    return (size_t)p.B * rows;
+}
+
+// The four fp64 tables fit the CU's LDS up to L = 64 (bracket_grad_kernels.hpp: 71 KiB there at M 256): no scratch, no query.  A long
+// plan has no backward to hand the gradient to, so there is no LONG instance.
+extern "C" int cliora_bracket_grad(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, const int32_t* brackets, int M,
+                                   const float* weights, float* d_split, float* log_prob_out, int32_t* feasible_out, int32_t* status,
+                                   void* stream) {
+    if (M < 0 || M > CON_MAX_M) return fail(CLIORA_EINVAL, "cliora_bracket_grad: M outside 0..256");
+    if (!plan || !fwd_ws || !d_split || !log_prob_out || !feasible_out || !status) return fail(CLIORA_EINVAL, "cliora_bracket_grad: NULL argument");
+    if (!brackets && M > 0) return fail(CLIORA_EINVAL, "cliora_bracket_grad: NULL brackets");
+    if (plan->p.is_long()) return fail(CLIORA_EINVAL, "cliora_bracket_grad: L > 64 is forward only (the backward stops at 64 words, so nothing could take the gradient)");
+    return launch_decode(plan, fwd_ws, "bracket_grad", POST_WAVES, [M](int L, int C) { return bracket_grad_lds(L, C, M); }, lengths, nullptr,
+                         nullptr, status, stream, [&](auto, auto&& go) {
+                             return go("bracket_grad_kernel", bracket_grad_kernel, brackets, M, weights, d_split, log_prob_out, feasible_out);
                          });
 }

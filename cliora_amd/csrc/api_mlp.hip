@@ -610,6 +610,7 @@ struct BwdCall {
     const cliora_params *P, *G;
     const float *x_span, *obj_span, *drop_mask, *inside_h, *IS, *outside_h, *OS;
     const float *d_inside_h, *d_inside_s, *d_outside_h, *d_outside_s;
+    const float* d_split_s;                   // cotangent of the inside split scores (cliora_chart_backward_split), or NULL
     float *ws, *wb, *d_x_span, *d_obj_span;
     int ran_outside;
     hipStream_t st;                           // the caller's stream: head, inside chain, tail
@@ -623,7 +624,7 @@ struct BwdCall {
     // compress = True: the outside root's gradient flows into the inside root, so the outside backward ends before the inside one starts
     const bool compress = P && P->root_mat;
     const BwdSchedule schedule = compress ? BwdSchedule::OutsideThenInside       // the one place that picks the backward's schedule
-                               : resident_pays(plan, vl, compress) ? BwdSchedule::Resident : BwdSchedule::Wavefront;
+                               : !d_split_s && resident_pays(plan, vl, compress) ? BwdSchedule::Resident : BwdSchedule::Wavefront;      // (the resident kernels take no split cotangent)
     const bool resident = schedule == BwdSchedule::Resident;
     const bool two_streams = schedule == BwdSchedule::Wavefront && ran_outside && wavefront_pays(p, g_cliora_wavefront);
     const hipStream_t sb = two_streams ? plan->side : st, sw = plan->side2;      // the outside chain's stream; the GEMM stream
@@ -717,7 +718,7 @@ struct BwdCall {
         }
         const int s_level = L - 2 - level;      // the inside level whose sibling uses are final with this outside level
         const bool sib_last = sibling_runs(s_level);
-        LAUNCH_SIGNALLING(sib_last ? nullptr : done, cell_dsoftmax, dim3(cells_grid(ncell)), dim3(256), 0, sb, g, f.ncb3, DPP, DPB, Sp, Pp, OS, dStoto, DS);
+        LAUNCH_SIGNALLING(sib_last ? nullptr : done, cell_dsoftmax, dim3(cells_grid(ncell)), dim3(256), 0, sb, g, f.ncb3, DPP, DPB, Sp, Pp, OS, dStoto, DS, (const float*)nullptr);
         LAUNCHOK("cell_dsoftmax(out)");
         if (sib_last) {
             const LevelArgs gi = level_args(p, s_level, false);
@@ -974,7 +975,7 @@ struct BwdCall {
             OKR(launch_level_compose_bwd(sa, ws + f.w2iT, ws + f.w2iT3, f.S3, Dp, f.ct3, f.ncb3, pair_level(p, level, false), dG, YM, Pp, PI, ldpi,
                                          PI + Dp, ldpi, ws + f.b2i, DA, DZ, Xp, DPP, DPB, tiled));
         }
-        hipLaunchKernelGGL(cell_dsoftmax, dim3(cells_grid(ncell)), dim3(256), 0, sa, g, f.ncb3, DPP, DPB, Sp, Pp, IS, dStot, DS);
+        hipLaunchKernelGGL(cell_dsoftmax, dim3(cells_grid(ncell)), dim3(256), 0, sa, g, f.ncb3, DPP, DPB, Sp, Pp, IS, dStot, DS, d_split_s);
         LAUNCHOK("cell_dsoftmax(in)");
         if (level == 1 && two_streams) HIPOK(hipEventRecord(plan->ev_join[2], sa));     // the last pair rows (DZ, X) are final
         return CLIORA_OK;
@@ -1060,10 +1061,10 @@ struct BwdCall {
     }
 };
 
-extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+extern "C" int cliora_chart_backward_split(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
                                      const float* drop_mask, const float* inside_h, const float* inside_s,
                                      const float* outside_h, const float* outside_s, const float* d_inside_h,
-                                     const float* d_inside_s, const float* d_outside_h, const float* d_outside_s,
+                                     const float* d_inside_s, const float* d_outside_h, const float* d_outside_s, const float* d_split_s,
                                      void* fwd_ws, size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, float* d_x_span,
                                      float* d_obj_span, const cliora_params* G, int ran_outside, void* stream) {
     // every refusal before the first launch
@@ -1083,6 +1084,17 @@ extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, 
     std::lock_guard<std::mutex> lanes_lock(*plan->lanes_mu);
     ForkGuard fork_guard(st);
     fork_guard.arm(1, plan->side2, plan->ev_join[1]);     // the weight-gradient stream takes work at several points of the call
-    return BwdCall{plan, P, G, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, d_inside_h, d_inside_s, d_outside_h, d_outside_s,
+    return BwdCall{plan, P, G, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, d_inside_h, d_inside_s, d_outside_h, d_outside_s, d_split_s,
                     (float*)fwd_ws, (float*)bwd_ws, d_x_span, d_obj_span, ran_outside, st}.run(fork_guard);
+}
+
+extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                                     const float* drop_mask, const float* inside_h, const float* inside_s,
+                                     const float* outside_h, const float* outside_s, const float* d_inside_h,
+                                     const float* d_inside_s, const float* d_outside_h, const float* d_outside_s,
+                                     void* fwd_ws, size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, float* d_x_span,
+                                     float* d_obj_span, const cliora_params* G, int ran_outside, void* stream) {
+    return cliora_chart_backward_split(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, d_inside_h, d_inside_s,
+                                       d_outside_h, d_outside_s, nullptr, fwd_ws, fwd_ws_bytes, bwd_ws, bwd_ws_bytes, d_x_span, d_obj_span, G,
+                                       ran_outside, stream);
 }

@@ -57,6 +57,93 @@ __device__ __forceinline__ bool con_block_any(bool p, int32_t* slots, int wave, 
     return any != 0;
 }
 
+// The mask of one sentence of n words (0 when its length is bad, with `bad` set): its M rows (start, end, kind) staged in brk and
+// validated, gs / he from the required ones, then a byte per cell of the triangle (the header above).  Called by every thread of the
+// workgroup.  -> -1: a bad length or a bad row (nothing but brk is written), 0: no cell is disallowed, 1: some cell is.  The fills the
+// caller made before the call are ordered before what it stores after it (the first vote's barrier).
+__device__ __forceinline__ int con_build_mask(int L, int C, int n, bool bad, const int32_t* __restrict__ rows, int M, int32_t* brk,
+                                              int32_t* gs, int32_t* he, int32_t* vote, unsigned char* mask) {
+    constexpr int NT = POST_WAVES * 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
+    for (int r = threadIdx.x; r < M; r += NT) {
+        const int32_t* row = rows + (size_t)r * 3;
+        int s = row[0], e = row[1], k = row[2];
+        if (s == -1) { e = -1; k = -1; }                                    // unused
+        else if (s < 0 || s > e || e >= n || (k != 0 && k != 1)) bad = true;
+        brk[3 * r] = s; brk[3 * r + 1] = e; brk[3 * r + 2] = k;
+    }
+    bad = con_block_any(bad, vote, wave, lane);      // also orders the fills before the stores below (same workgroup, same addresses)
+    if (bad) return -1;
+    for (int p = threadIdx.x; p < 2 * n; p += NT) {  // gs[q] (p < n) and he[q]: every row against one word
+        const bool left = p < n;
+        const int q = left ? p : p - n;
+        int v = left ? -1 : L;
+        for (int r = 0; r < M; ++r) {
+            const int s = brk[3 * r], e = brk[3 * r + 1];
+            if (brk[3 * r + 2] != 1) continue;
+            if (left) { if (s <= q && q < e && s > v) v = s; }
+            else if (s < q && q <= e && e < v) v = e;
+        }
+        (left ? gs : he)[q] = v;
+    }
+    __syncthreads();
+    bool dis = false;                                // this thread disallowed a cell
+    for (int level = 0; level < n; ++level)
+        for (int pos = threadIdx.x; pos < n - level; pos += NT) {
+            const bool ok = gs[pos + level] <= pos && he[pos] >= pos + level;
+            mask[coff(level) + pos] = ok ? CON_ALLOWED : 0;
+            dis |= !ok;
+        }
+    __syncthreads();
+    for (int r = threadIdx.x; r < M; r += NT)
+        if (brk[3 * r + 2] == 0) { mask[chart_cell(L, C, brk[3 * r + 1] - brk[3 * r], brk[3 * r])] = 0; dis = true; }
+    __syncthreads();
+    for (int r = threadIdx.x; r < M; r += NT)
+        if (brk[3 * r + 2] == 1) {
+            const int cell = chart_cell(L, C, brk[3 * r + 1] - brk[3 * r], brk[3 * r]);
+            if (mask[cell]) mask[cell] = CON_ALLOWED | CON_REQUIRED;        // every writer of a cell stores this value
+        }
+    return con_block_any(dis, vote, wave, lane) ? 1 : 0;
+}
+
+// The inside tables of sentence b's n words, levels up: al over the allowed cells and, where `constrained`, au over every cell --
+// post_inside's operations in its order, in one level loop.  The leaves are the caller's (before a barrier).  Called by every thread of
+// the workgroup; one barrier per level, the last one before it returns.  lvl: the plan's level bases, in LDS.
+template <bool LONG>
+__device__ __forceinline__ void con_inside(post_t* al, post_t* au, const unsigned char* mask, bool constrained, const int32_t* lvl, int L,
+                                           int C, int B, int b, int n, const float* __restrict__ Sp) {
+    const post_t ninf = -INFINITY;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
+    auto row_of = [&](int level, int pos) { return (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level; };
+    for (int level = 1; level < n; ++level) {
+        const int off = coff(level), mine = n - level;
+        for (int pos = wave; pos < mine; pos += POST_WAVES) {
+            const bool an = lane < level, an1 = LONG && lane + 64 < level;
+            float s, s1;
+            const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
+            const post_t r0 = (post_t)s - (post_t)smax, r1 = (post_t)s1 - (post_t)smax;
+            const int l0 = coff(lane) + pos, q0 = an ? coff(level - lane - 1) + pos + lane + 1 : 0;
+            const int l1 = an1 ? coff(lane + 64) + pos : 0, q1 = an1 ? coff(level - lane - 65) + pos + lane + 65 : 0;
+            post_t a = ninf;
+            if (mask[off + pos] & CON_ALLOWED) {
+                const post_t t0 = an ? al[l0] + al[q0] + r0 : ninf;
+                const post_t t1 = an1 ? al[l1] + al[q1] + r1 : ninf;
+                a = con_wave_lse<LONG>(t0, t1);
+            }
+            if (constrained) {
+                const post_t t0 = an ? au[l0] + au[q0] + r0 : ninf;
+                const post_t t1 = an1 ? au[l1] + au[q1] + r1 : ninf;
+                const post_t u = post_wave_lse<LONG>(t0, t1);
+                if (lane == 0) au[off + pos] = u;
+            }
+            if (lane == 0) al[off + pos] = a;
+        }
+        __syncthreads();
+    }
+}
+
 // lengths (B) or NULL (every sentence has L words).  brackets (B, M, 3) rows (start, end, kind): kind 1 required, 0 forbidden, start
 // -1 unused; NULL when M = 0.  spans (B, L-1, 2) (NULL when L = 1): the best qualifying tree in emit_spans' order, (-1, -1) beyond;
 // score, log_z, log_zc, log_prob (B); feasible (B); marg (B, C) or NULL (no outside pass): mu_c, exactly 0 outside the triangle and
@@ -96,52 +183,16 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void constrained_kernel(int
     if (spans) for (int i = threadIdx.x; i < 2 * (L - 1); i += NT) spans[(size_t)b * (L - 1) * 2 + i] = -1;
     for (int c = threadIdx.x; c < L; c += NT) lvl[c] = lvl_base[c];
 
-    // ---- the mask: stage and validate the rows
-    for (int r = threadIdx.x; r < M; r += NT) {
-        const int32_t* row = brackets + ((size_t)b * M + r) * 3;
-        int s = row[0], e = row[1], k = row[2];
-        if (s == -1) { e = -1; k = -1; }                                    // unused
-        else if (s < 0 || s > e || e >= n || (k != 0 && k != 1)) bad = true;
-        brk[3 * r] = s; brk[3 * r + 1] = e; brk[3 * r + 2] = k;
-    }
-    bad = con_block_any(bad, vote, wave, lane);      // also orders the fills before the stores below (same workgroup, same addresses)
-    if (bad) {
+    // ---- the mask
+    const int masked = con_build_mask(L, C, n, bad, brackets + (size_t)b * M * 3, M, brk, gs, he, vote, mask);
+    if (masked < 0) {
         if (threadIdx.x == 0) {
             atomicAdd(status, 1);
             feasible[b] = 0; log_z[b] = 0.f; score[b] = -INFINITY; log_zc[b] = -INFINITY; log_prob[b] = -INFINITY;
         }
         return;
     }
-    for (int p = threadIdx.x; p < 2 * n; p += NT) {  // gs[q] (p < n) and he[q]: every row against one word
-        const bool left = p < n;
-        const int q = left ? p : p - n;
-        int v = left ? -1 : L;
-        for (int r = 0; r < M; ++r) {
-            const int s = brk[3 * r], e = brk[3 * r + 1];
-            if (brk[3 * r + 2] != 1) continue;
-            if (left) { if (s <= q && q < e && s > v) v = s; }
-            else if (s < q && q <= e && e < v) v = e;
-        }
-        (left ? gs : he)[q] = v;
-    }
-    __syncthreads();
-    bool dis = false;                                // this thread disallowed a cell
-    for (int level = 0; level < n; ++level)
-        for (int pos = threadIdx.x; pos < n - level; pos += NT) {
-            const bool ok = gs[pos + level] <= pos && he[pos] >= pos + level;
-            mask[coff(level) + pos] = ok ? CON_ALLOWED : 0;
-            dis |= !ok;
-        }
-    __syncthreads();
-    for (int r = threadIdx.x; r < M; r += NT)
-        if (brk[3 * r + 2] == 0) { mask[chart_cell(L, C, brk[3 * r + 1] - brk[3 * r], brk[3 * r])] = 0; dis = true; }
-    __syncthreads();
-    for (int r = threadIdx.x; r < M; r += NT)
-        if (brk[3 * r + 2] == 1) {
-            const int cell = chart_cell(L, C, brk[3 * r + 1] - brk[3 * r], brk[3 * r]);
-            if (mask[cell]) mask[cell] = CON_ALLOWED | CON_REQUIRED;        // every writer of a cell stores this value
-        }
-    const bool constrained = con_block_any(dis, vote, wave, lane);    // some cell of the triangle is disallowed
+    const bool constrained = masked > 0;             // some cell of the triangle is disallowed
 
     // ---- the best tree, levels up: cky_kernel over the allowed cells
     float* val = reinterpret_cast<float*>(con_smem);
@@ -187,31 +238,7 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void constrained_kernel(int
         if (constrained) au[c] = 0;
     }
     __syncthreads();
-    for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const bool an = lane < level, an1 = LONG && lane + 64 < level;
-            float s, s1;
-            const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
-            const post_t r0 = (post_t)s - (post_t)smax, r1 = (post_t)s1 - (post_t)smax;
-            const int l0 = coff(lane) + pos, q0 = an ? coff(level - lane - 1) + pos + lane + 1 : 0;
-            const int l1 = an1 ? coff(lane + 64) + pos : 0, q1 = an1 ? coff(level - lane - 65) + pos + lane + 65 : 0;
-            post_t a = ninf;
-            if (mask[off + pos] & CON_ALLOWED) {
-                const post_t t0 = an ? al[l0] + al[q0] + r0 : ninf;
-                const post_t t1 = an1 ? al[l1] + al[q1] + r1 : ninf;
-                a = con_wave_lse<LONG>(t0, t1);
-            }
-            if (constrained) {
-                const post_t t0 = an ? au[l0] + au[q0] + r0 : ninf;
-                const post_t t1 = an1 ? au[l1] + au[q1] + r1 : ninf;
-                const post_t u = post_wave_lse<LONG>(t0, t1);
-                if (lane == 0) au[off + pos] = u;
-            }
-            if (lane == 0) al[off + pos] = a;
-        }
-        __syncthreads();
-    }
+    con_inside<LONG>(al, au, mask, constrained, lvl, L, C, B, b, n, Sp);
     const post_t lzc = al[coff(n - 1)], lz = constrained ? au[coff(n - 1)] : lzc;
     if (threadIdx.x == 0) { log_zc[b] = (float)lzc; log_z[b] = (float)lz; log_prob[b] = (float)(lzc - lz); }
     if (!mu || !(lzc > ninf)) return;

@@ -1290,11 +1290,12 @@ static __global__ __launch_bounds__(256) void cell_dnorm(LevelArgs g, const floa
 
 // Softmax / score backward of the level's cells (diora.py:125-149 differentiated), one wave per cell:
 //   dp_n = sum_blocks DPP[row][block] + DPB[row]                        (= dG . y_n, see level_compose_bwd)
-//   ds_n = p_n [ (dp_n - sum_m p_m dp_m) + dS_tot (1 + s_n - S) ]
+//   ds_n = p_n [ (dp_n - sum_m p_m dp_m) + dS_tot (1 + s_n - S) ]  (+ dsplit[row] when given: a cotangent on the split scores themselves,
+//   cliora_chart_backward_split; the test is uniform over the grid)
 static __global__ __launch_bounds__(256) void cell_dsoftmax(LevelArgs g, int ncb, const float* __restrict__ DPP, const float* __restrict__ DPB,
                                                             const float* __restrict__ Sp, const float* __restrict__ Pp,
                                                             const float* __restrict__ Schart, const float* __restrict__ dStot,
-                                                            float* __restrict__ DS) {
+                                                            float* __restrict__ DS, const float* __restrict__ dsplit) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= g.B * g.Lc || g.N == 0) return;
@@ -1311,7 +1312,7 @@ static __global__ __launch_bounds__(256) void cell_dsoftmax(LevelArgs g, int ncb
     // 1 + (s_n - S), in that order: the scores reach 1e8 without unit normalisation, where (1 + s_n) - S loses the 1 (found by
     // tools/fuzz_parity.py: every gradient through outside_s of a cell with |S| > 2^24 vanished)
     const float ds = pn * ((dp - mean) + dStot[crow] * (1.f + (sn - Schart[crow])));
-    if (an) DS[row0 + lane] = ds;
+    if (an) DS[row0 + lane] = dsplit ? ds + dsplit[row0 + lane] : ds;
 }
 
 }  // namespace cliora

@@ -64,11 +64,23 @@ def _cont(g):
     return g.contiguous().float() if g is not None else None
 
 
+class ChartWorkspaces(list):
+    """The holder of a forward's workspace(s), made anew by every forward of a chart module, with the slot through which
+    cliora_amd.structured hands the chart node a cotangent on the inside split scores: `split_cot` is a one-element list that the
+    node of that forward shares (ChartFunction keeps it in its ctx), so a cotangent left there can reach that forward's backward only."""
+    __slots__ = ('split_cot',)
+
+    def __init__(self):
+        super().__init__()
+        self.split_cot = [None]
+
+
 class ChartFunction(torch.autograd.Function):
     """One autograd node for the whole inside-outside chart, text-only (obj_span None) or with image regions (a plan of R > 0).
 
     forward  -> cliora_chart_forward   (replaces diora.py:283-398 as executed by DioraBase.forward)
-    backward -> cliora_chart_backward  (replaces what autograd replays through those lines)
+    backward -> cliora_chart_backward  (replaces what autograd replays through those lines), or cliora_chart_backward_split when a
+                bracket loss of the same forward left a cotangent on the split scores (cliora_amd.structured)
     Inputs: plan, holder (list that receives the forward workspace), run_outside, x_span, obj_span, drop_mask, then the parameter
     tensors in _lib.PARAM_FIELDS order (None for the out_* set when the weights are shared).  Without obj_span the library gets NULL
     for obj_span, drop_mask, inside_c and d_obj_span, and the fifth output, inside_c, is None.
@@ -89,6 +101,7 @@ class ChartFunction(torch.autograd.Function):
             _lib.call('cliora_chart_forward', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask),
                       *map(_ptr, outs), _ptr(inside_c), _ptr(ws), nbytes, run_outside, _stream())
         ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.drop_mask, ctx.vl = plan, run_outside & 1, ws, ptens, drop_mask, vl
+        ctx.split_cot = getattr(holder, 'split_cot', None)      # cliora_amd.structured leaves d_split there (a plain list: no such input)
         ctx.save_for_backward(x_span, *((obj_span,) if vl else ()), *outs)
         ctx.set_materialize_grads(False)
         if vl:
@@ -108,10 +121,18 @@ class ChartFunction(torch.autograd.Function):
             g = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
             wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
             gst = _param_struct(g)
-            _lib.call('cliora_chart_backward', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask),
-                      *map(_ptr, saved[-4:]), *[_ptr(_cont(d)) for d in (d_ih, d_is, d_oh, d_os)],
-                      _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst),
-                      ctx.run_outside, _stream())
+            d_split = ctx.split_cot[0] if ctx.split_cot is not None else None
+            if d_split is None:
+                _lib.call('cliora_chart_backward', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask),
+                          *map(_ptr, saved[-4:]), *[_ptr(_cont(d)) for d in (d_ih, d_is, d_oh, d_os)],
+                          _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst),
+                          ctx.run_outside, _stream())
+            else:                                         # a bracket loss of this forward left a cotangent on the split scores: taken once
+                ctx.split_cot[0] = None
+                _lib.call('cliora_chart_backward_split', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask),
+                          *map(_ptr, saved[-4:]), *[_ptr(_cont(d)) for d in (d_ih, d_is, d_oh, d_os)], _ptr(d_split),
+                          _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst),
+                          ctx.run_outside, _stream())
         return (None, None, None, d_x, d_obj, None) + tuple(g[n] for n in _lib.PARAM_FIELDS)
 
 
@@ -339,7 +360,7 @@ class DioraBase(nn.Module):
         B, L, D = x_span.shape
         assert D == self.size
         dev_index = x_span.device.index if x_span.is_cuda else -1
-        holder = []
+        holder = ChartWorkspaces()
         # eval / torch.no_grad: nothing will ask for the backward, so the per-pair state is not written -- unless a hook
         # override wants the per-split tensors (analysis/utils.py:67-95)
         params = self._param_tensors()
@@ -544,6 +565,20 @@ class DioraBase(nn.Module):
         nb = cp.log_prob.numel()
         constrained.refuse_rejected(int(host[nb:].sum()))
         return host[:nb].view('float32').tolist()
+
+
+    def bracket_nll(self, required, forbidden=None, reduction='mean'):
+        """The loss -log_prob of the brackets, in the autograd graph of the last forward (cliora_amd.structured.bracket_nll; DESIGN.md
+        section 20): required / forbidden as cky_constrained takes them -- per-sentence lists of (start, end); a gold tree is its inner
+        brackets.  The mean (or 'sum') over the sentences some tree qualifies for.  A span outside its sentence raises here, on the
+        host; nothing is synchronised."""
+        from . import constrained, structured
+        L = self._plan.L
+        for lst in list(required) + list(forbidden or ()):
+            for s, e in lst:
+                if not 0 <= int(s) <= int(e) < L:
+                    raise ValueError('bracket (%d, %d) is not 0 <= start <= end < %d' % (s, e, L))
+        return structured.bracket_nll(self, constrained.pack_brackets(required, forbidden), reduction=reduction)
 
 
 class DioraMLP(DioraBase):

@@ -226,9 +226,11 @@ class LossDict(dict):
 
 
 class Net(nn.Module):
-    def __init__(self, embed, image_encoder, diora, obj_feats, loss_funcs=()):
+    def __init__(self, embed, image_encoder, diora, obj_feats, loss_funcs=(), bracket_loss_weight=0.0):
         super().__init__()
         self.obj_feats = obj_feats
+        # > 0: a batch that carries entity_labels adds weight * bracket_nll of its annotated phrases (cliora_amd.structured) to the total
+        self.bracket_loss_weight = float(bracket_loss_weight)
         self.overlap_word_branch = True      # vision-language training steps: the word branch on the library's caller lane (forward())
         if obj_feats:
             self.img_encoder = image_encoder
@@ -237,7 +239,7 @@ class Net(nn.Module):
         for m in loss_funcs:
             setattr(self, m.name, m)
 
-    def forward(self, tokens, obj_feats=None, neg_samples=None, compute_loss=True):
+    def forward(self, tokens, obj_feats=None, neg_samples=None, compute_loss=True, entity_labels=None):
         # The word branch of a vision-language training step -- Embed's word projection, ImageEncoder's fc_vis, the word-region scorer and,
         # in the backward, their gradients and the region matrix's half of the region-max backward -- shares nothing with the chart
         # (cliora.py:459-461, trainer.py:139-171): it runs on the library's caller lane beside the chart's forward and backward
@@ -288,6 +290,11 @@ class Net(nn.Module):
                 v = fn(self.diora.vg_atten_score)
             ret[name] = v
             parts.append(v)
+        if entity_labels is not None and self.bracket_loss_weight > 0:
+            from .constrained import brackets_from_entity_labels
+            v = self.bracket_loss_weight * self.diora.bracket_nll(brackets_from_entity_labels(entity_labels))
+            ret['bracket_nll'] = v
+            parts.append(v)
         ret.parts = parts
         return ret
 
@@ -308,7 +315,7 @@ def select_diora(arch, obj_feats):
 
 
 def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=True, normalize='unit',
-              vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp'):
+              vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp', bracket_loss_weight=0.0):
     """What trainer.py:504-582 assembles, on the native chart modules."""
     embed = Embed(embeddings, embeddings.weight.shape[1], size)
     enc = ImageEncoder(img_dim, size)
@@ -320,7 +327,7 @@ def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=
         losses.append(ContrastiveLoss(vl_margin, alpha_contr))
     if obj_feats:
         embeddings.weight.requires_grad = False              # trainer.py:541
-    return Net(embed, enc, diora, obj_feats, losses)
+    return Net(embed, enc, diora, obj_feats, losses, bracket_loss_weight=bracket_loss_weight)
 
 
 class Trainer(object):
@@ -347,7 +354,11 @@ class Trainer(object):
         if neg_samples is None and self.negative_sampler is not None:       # drawn on the current stream, ahead of the forward
             neg_samples = self.negative_sampler.sample(self.k_neg)
         with torch.set_grad_enabled(train):
-            out = self.net(batch_map['sentences'], batch_map.get('obj_feats'), neg_samples, compute_loss)
+            if getattr(self.net, 'bracket_loss_weight', 0.0) > 0 and train and compute_loss and batch_map.get('entity_labels') is not None:
+                out = self.net(batch_map['sentences'], batch_map.get('obj_feats'), neg_samples, compute_loss,
+                               entity_labels=batch_map['entity_labels'])
+            else:
+                out = self.net(batch_map['sentences'], batch_map.get('obj_feats'), neg_samples, compute_loss)
         total = out.total() if isinstance(out, LossDict) else out['total_loss'].mean(dim=0).sum()
         # sync=True returns the loss as a Python float like the reference's `.item()` (trainer.py:463).  Its value is final once the FORWARD is:
         # it is copied to pinned host memory here, behind the forward, and read at the end of the step by waiting for THAT copy only -- the

@@ -152,6 +152,23 @@ int cliora_chart_backward(cliora_plan* plan, const cliora_params* params,
                           void* bwd_workspace, size_t bwd_workspace_bytes,
                           float* d_x_span, float* d_obj_span, const cliora_params* grads,
                           int ran_outside, void* stream);
+/* cliora_chart_backward with one more cotangent: d_split_s, on the per-split INSIDE scores before the softmax -- the rows
+ * cliora_bracket_grad writes, cliora_plan_split_score_count floats: row B * lvl_base[level] + (b * (L - level) + pos) * level + k for
+ * split k of cell (level, pos) of sentence b.  NULL = zero, and the call is then cliora_chart_backward itself (which is this entry
+ * called with NULL): the same launches, the same bits.  Otherwise the row is added to the score gradient where the inside chain's
+ * softmax backward forms it, so that everything downstream of a split score sees the sum; a plan the
+ * sentence-resident kernels would take runs the launch path for such a call (either path runs on either path's workspace).  Refused
+ * as cliora_chart_backward refuses: TreeLSTM plans (cliora_lstm_backward takes no such input), long plans, a missing forward. */
+int cliora_chart_backward_split(cliora_plan* plan, const cliora_params* params,
+                                const float* x_span, const float* obj_span, const float* drop_mask,
+                                const float* inside_h, const float* inside_s,
+                                const float* outside_h, const float* outside_s,
+                                const float* d_inside_h, const float* d_inside_s,
+                                const float* d_outside_h, const float* d_outside_s, const float* d_split_s,
+                                void* fwd_workspace, size_t fwd_workspace_bytes,
+                                void* bwd_workspace, size_t bwd_workspace_bytes,
+                                float* d_x_span, float* d_obj_span, const cliora_params* grads,
+                                int ran_outside, void* stream);
 
 /* DioraTreeLSTM (BASELINE config 5).  PARITY UNPINNED: the reference ships this composition only
  * as commented-out text (cliora/net/vg.py:28-76); what is implemented is that text on the
@@ -422,6 +439,31 @@ int cliora_sample_trees(cliora_plan* plan, void* fwd_workspace, const int32_t* l
 int cliora_constrained_parse(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* brackets, int M,
                              int32_t* spans_out, float* score_out, float* log_z_out, float* log_zc_out, float* log_prob_out,
                              int32_t* feasible_out, float* marginals, int32_t* status, void* stream);
+/* The gradient of cliora_constrained_parse's log_prob with respect to the per-split inside scores: what a loss -log_prob (distant
+ * supervision from annotated phrases, the log-likelihood of a gold tree as its n - 2 inner brackets, forbidden-bracket penalties)
+ * hands to cliora_chart_backward_split.  With a_x / b_x the inside / outside tables of the constrained (x = c,
+ * over the allowed cells) and the unconstrained (x = u) distribution, for split k of a cell with children left_k, right_k:
+ *   nu_x[cell, k]    = exp(b_x[cell] + a_x[left_k] + a_x[right_k] + r[cell, k] - log_z_x), 0 where the cell or a child is disallowed
+ *   d_split[cell, k] = w[b] * ((nu_c - nu_u)[cell, k] - [k == k*] * sum_k (nu_c - nu_u)[cell, .])
+ * k* is the first maximum of the cell's scores (the rule of cliora_cky_spans): it carries the derivative of the row maximum in r, so
+ * every row sums to zero.  Tables and sums in fp64, fixed order; d_split in fp32.
+ *   d_split: cliora_plan_split_score_count floats in the layout of the inside split-score rows: row B * lvl_base[level] + (b * (L -
+ *     level) + pos) * level + k.  EVERY element is written (no memset is needed); cells beyond a sentence's triangle get zeros.
+ *   weights (B) fp32 device, or NULL = 1: in a backward, the cotangent of log_prob.
+ *   brackets, M, lengths, status: as cliora_constrained_parse takes them.  With every length equal to L the outputs are bitwise those
+ *     of the lengths == NULL call.
+ *   log_prob_out (B) fp32: bitwise the log_prob of cliora_constrained_parse on the same chart; feasible_out (B) int32.
+ *   A sentence with no qualifying tree (feasible 0, log_prob -inf), with a bad length or a bad row (feasible 0, log_prob -inf, one
+ *     count in *status) gets a zero gradient, and its weight is not read.  Without a disallowed cell the gradient is exactly 0 and
+ *     log_prob is 0.
+ * One workgroup per sentence, a wavefront per cell, each element written by one lane, no floating-point atomics: two calls give equal
+ * bits.  The four tables fit the LDS (71 KiB at L 64 and M 256): no scratch.  Refused with CLIORA_EINVAL and a message, before any
+ * launch: a long plan (L > 64: the backward stops at 64 words, so nothing could take the gradient); M outside 0 .. 256; a NULL plan,
+ * workspace, d_split, log_prob_out, feasible_out or status; NULL brackets with M > 0; a plan that has not run a forward. */
+size_t cliora_plan_split_score_count(const cliora_plan* plan);   /* floats in the inside split-score rows of a batch: B * sum_level level * (L - level) */
+int cliora_bracket_grad(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* brackets, int M,
+                        const float* weights, float* d_split, float* log_prob_out, int32_t* feasible_out, int32_t* status,
+                        void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
