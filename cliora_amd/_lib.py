@@ -86,6 +86,7 @@ ABI = {
     'cliora_constrained_parse': (i32, [vp, vp, vp, vp, i32] + [vp] * 9),
     'cliora_plan_split_score_count': (sz, [vp]),
     'cliora_bracket_grad': (i32, [vp, vp, vp, vp, i32] + [vp] * 6),
+    'cliora_tree_expectation': (i32, [vp] * 12),
     'cliora_ground_eval': (i32, [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_ground_eval_ragged': (i32, [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_phrase_gather': (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp, i64, i64, vp, vp]),

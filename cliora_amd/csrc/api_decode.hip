@@ -2,7 +2,8 @@
 // parse under required and forbidden brackets, from the per-split scores of the last forward -- of every sentence of a chart, or of
 // each sentence's own triangle of a right-padded chart.  See include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY
 // kernel, kbest_kernels.hpp for the k-best lists, posterior_kernels.hpp for the sum-product model, sample_kernels.hpp for the draws
-// from it, constrained_kernels.hpp for the bracket mask over both and bracket_grad_kernels.hpp for the gradient of its log-probability.
+// from it, constrained_kernels.hpp for the bracket mask over both, bracket_grad_kernels.hpp for the gradient of its log-probability
+// and expectation_kernels.hpp for the expected cost, the entropy and their gradient.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
 #include <cmath>
 
@@ -10,6 +11,7 @@
 #include "bracket_grad_kernels.hpp"
 #include "constrained_kernels.hpp"
 #include "decode_kernels.hpp"
+#include "expectation_kernels.hpp"
 #include "kbest_kernels.hpp"
 #include "posterior_kernels.hpp"
 #include "sample_kernels.hpp"
@@ -157,5 +159,20 @@ extern "C" int cliora_bracket_grad(cliora_plan* plan, void* fwd_ws, const int32_
     return launch_decode(plan, fwd_ws, "bracket_grad", POST_WAVES, [M](int L, int C) { return bracket_grad_lds(L, C, M); }, lengths, nullptr,
                          nullptr, status, stream, [&](auto, auto&& go) {
                              return go("bracket_grad_kernel", bracket_grad_kernel, brackets, M, weights, d_split, log_prob_out, feasible_out);
+                         });
+}
+
+// The four fp64 tables and the row maxima fit the CU's LDS up to L = 64 (expectation_kernels.hpp: 73.5 KiB there): no scratch, no
+// query.  A long plan has no backward to hand the gradient to, so there is no LONG instance.
+extern "C" int cliora_tree_expectation(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, const float* cost, const float* w_cost,
+                                       const float* w_entropy, float* d_split, float* risk_out, float* entropy_out, float* log_z_out,
+                                       int32_t* status, void* stream) {
+    if (!plan || !fwd_ws || !d_split || !risk_out || !entropy_out || !log_z_out || !status)
+        return fail(CLIORA_EINVAL, "cliora_tree_expectation: NULL argument");
+    if (plan->p.is_long()) return fail(CLIORA_EINVAL, "cliora_tree_expectation: L > 64 is forward only (the backward stops at 64 words, so nothing could take the gradient)");
+    return launch_decode(plan, fwd_ws, "tree_expectation", POST_WAVES, tree_expectation_lds, lengths, nullptr, nullptr, status, stream,
+                         [&](auto, auto&& go) {
+                             return go("tree_expectation_kernel", tree_expectation_kernel, cost, w_cost, w_entropy, d_split, risk_out,
+                                       entropy_out, log_z_out);
                          });
 }

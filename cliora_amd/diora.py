@@ -580,6 +580,24 @@ class DioraBase(nn.Module):
                     raise ValueError('bracket (%d, %d) is not 0 <= start <= end < %d' % (s, e, L))
         return structured.bracket_nll(self, constrained.pack_brackets(required, forbidden), reduction=reduction)
 
+    def tree_objective(self, cost=None):
+        """(risk, entropy) of the distribution over parses of the last forward, two (B,) tensors in its autograd graph
+        (cliora_amd.structured.tree_objective): the expected value of the per-cell cost -- fp32 (B, C) in the cell
+        order of inside_s, ``structured.span_costs``; None = 0 -- and the entropy.  Nothing is synchronised."""
+        from . import structured
+        return structured.tree_objective(self, cost)
+
+    def parse_entropy(self, reduction='mean'):
+        """The entropy of the distribution over parses, its mean (or 'sum') over the batch: a 0-d tensor in the graph."""
+        from . import structured
+        return structured.parse_entropy(self, reduction=reduction)
+
+    def expected_cost(self, cost, reduction='mean'):
+        """The expected cost of the parse (cost as tree_objective takes it), its mean (or 'sum') over the batch: a 0-d tensor in the
+        graph.  With ``structured.span_costs`` of the annotated phrases: minus the expected number of them recovered."""
+        from . import structured
+        return structured.expected_cost(self, cost, reduction=reduction)
+
 
 class DioraMLP(DioraBase):
     def init_parameters(self):

@@ -226,11 +226,15 @@ class LossDict(dict):
 
 
 class Net(nn.Module):
-    def __init__(self, embed, image_encoder, diora, obj_feats, loss_funcs=(), bracket_loss_weight=0.0):
+    def __init__(self, embed, image_encoder, diora, obj_feats, loss_funcs=(), bracket_loss_weight=0.0, risk_loss_weight=0.0,
+                 entropy_loss_weight=0.0):
         super().__init__()
         self.obj_feats = obj_feats
         # > 0: a batch that carries entity_labels adds weight * bracket_nll of its annotated phrases (cliora_amd.structured) to the total
         self.bracket_loss_weight = float(bracket_loss_weight)
+        # > 0: such a batch adds weight * the mean expected cost under span_costs of ALL its phrases, crossing ones included (minus the
+        # expected number of them recovered); != 0, either sign: a training step adds weight * the mean entropy of the parse distribution
+        self.risk_loss_weight, self.entropy_loss_weight = float(risk_loss_weight), float(entropy_loss_weight)
         self.overlap_word_branch = True      # vision-language training steps: the word branch on the library's caller lane (forward())
         if obj_feats:
             self.img_encoder = image_encoder
@@ -295,6 +299,21 @@ class Net(nn.Module):
             v = self.bracket_loss_weight * self.diora.bracket_nll(brackets_from_entity_labels(entity_labels))
             ret['bracket_nll'] = v
             parts.append(v)
+        use_risk = entity_labels is not None and self.risk_loss_weight > 0
+        use_entropy = self.entropy_loss_weight != 0 and self.training and torch.is_grad_enabled()
+        if use_risk or use_entropy:                             # one node for both: one kernel launch each way
+            from .constrained import brackets_from_entity_labels
+            from .structured import span_costs
+            cost = None
+            if use_risk:
+                cost = span_costs(brackets_from_entity_labels(entity_labels, drop_crossing=False), L=tokens.shape[1], device=tokens.device)
+            risk, entropy = self.diora.tree_objective(cost)
+            if use_risk:
+                ret['risk'] = v = self.risk_loss_weight * risk.mean()
+                parts.append(v)
+            if use_entropy:
+                ret['entropy'] = v = self.entropy_loss_weight * entropy.mean()
+                parts.append(v)
         ret.parts = parts
         return ret
 
@@ -315,7 +334,8 @@ def select_diora(arch, obj_feats):
 
 
 def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=True, normalize='unit',
-              vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp', bracket_loss_weight=0.0):
+              vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp', bracket_loss_weight=0.0,
+              risk_loss_weight=0.0, entropy_loss_weight=0.0):
     """What trainer.py:504-582 assembles, on the native chart modules."""
     embed = Embed(embeddings, embeddings.weight.shape[1], size)
     enc = ImageEncoder(img_dim, size)
@@ -327,7 +347,8 @@ def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=
         losses.append(ContrastiveLoss(vl_margin, alpha_contr))
     if obj_feats:
         embeddings.weight.requires_grad = False              # trainer.py:541
-    return Net(embed, enc, diora, obj_feats, losses, bracket_loss_weight=bracket_loss_weight)
+    return Net(embed, enc, diora, obj_feats, losses, bracket_loss_weight=bracket_loss_weight, risk_loss_weight=risk_loss_weight,
+               entropy_loss_weight=entropy_loss_weight)
 
 
 class Trainer(object):
@@ -354,7 +375,8 @@ class Trainer(object):
         if neg_samples is None and self.negative_sampler is not None:       # drawn on the current stream, ahead of the forward
             neg_samples = self.negative_sampler.sample(self.k_neg)
         with torch.set_grad_enabled(train):
-            if getattr(self.net, 'bracket_loss_weight', 0.0) > 0 and train and compute_loss and batch_map.get('entity_labels') is not None:
+            if ((getattr(self.net, 'bracket_loss_weight', 0.0) > 0 or getattr(self.net, 'risk_loss_weight', 0.0) > 0) and train and compute_loss
+                    and batch_map.get('entity_labels') is not None):
                 out = self.net(batch_map['sentences'], batch_map.get('obj_feats'), neg_samples, compute_loss,
                                entity_labels=batch_map['entity_labels'])
             else:

@@ -26,6 +26,9 @@ respect to inside_s itself -- leaves its cotangent in the slot of that forward.)
 module that has run no forward, a forward under ``no_grad`` / in eval mode without gradients (no backward state was kept), a plan of
 L > 64 (the backward stops at 64 words), a TreeLSTM module (its backward takes no such input), and a module whose
 ``workspace_slices`` yields more than one workspace (one chart node, one slot: run the loss per forward).
+
+The second half of the module reads the same distribution as an expectation (cliora_tree_expectation): the
+expected value of a per-cell cost and the entropy of the distribution over trees, ``tree_objective``, with the same hand-off.
 """
 import collections
 import ctypes as C
@@ -37,6 +40,7 @@ from . import _lib
 from ._lib import ptr_or_null as _p, stream as _stream
 from .constrained import allowed_cells, bad_row
 from .diora import workspace_slices
+from .posterior import cell_id
 
 # d_split (cliora_plan_split_score_count * workspaces,) fp32 -- G in the layout of the inside split-score rows; log_prob (B,) fp32;
 # feasible (B,) int32; status (number of workspaces,) int32.  Device tensors; nothing is synchronised.
@@ -223,3 +227,198 @@ def bracket_grad_numpy(pair_s, lengths, brackets, weights=None):
             d[np.arange(n - level), np.argmax(s[level], axis=1)] -= d.sum(axis=1)
             out[level][b, :n - level] = weights[b] * d
     return out
+
+
+# ---- expectations: the expected cost and the entropy of the parse distribution (cliora_tree_expectation) ------
+# The same distribution read as an expectation: risk = E_T[sum of cost over T's cells] -- with cost -1 on the annotated phrases, minus
+# the expected number of gold brackets recovered, a soft counterpart of bracket_nll that takes crossing phrases and is never infeasible
+# -- and the entropy H = -sum_T p(T) log p(T).  Both gradients are covariances that the kernel forms from an expectation-semiring
+# inside-outside pass (csrc/expectation_kernels.hpp); the hand-off to the chart is the bracket loss's slot, into which they ADD.
+#
+#     risk, entropy = tree_objective(net.diora, span_costs(phrases, L=L, device=dev))        # (B,) each, in the graph
+#     loss = recon + 0.5 * risk.mean() - 0.01 * entropy.mean()
+#
+# d_split (cliora_plan_split_score_count * workspaces,) fp32; risk, entropy, log_z (B,) fp32; status (number of workspaces,) int32.
+TreeExpectation = collections.namedtuple('TreeExpectation', 'd_split risk entropy log_z status')
+
+
+def tree_expectation(diora, cost=None, w_cost=None, w_entropy=None, lengths=None):
+    """cliora_tree_expectation on a chart module after its forward (any forward: this call needs no backward state).  cost: fp32
+    (B, C) in the cell order of inside_s or None = 0; w_cost: fp32 (B,) or None = 1; w_entropy: fp32 (B,) or None = 0; lengths: int32
+    (B,) or None.  d_split = d (w_cost risk + w_entropy entropy) / d s, one buffer per workspace of ``workspace_slices``, back to
+    back.  -> TreeExpectation of device tensors; nothing is synchronised."""
+    if diora._plan is None:
+        raise _lib.ChartLibError('tree_expectation: the module has run no forward')
+    plan, parts = diora._plan, workspace_slices(diora)
+    nws, B = len(parts), plan.B
+    dev = parts[0][0].device
+    if cost is not None and (cost.dim() != 2 or tuple(cost.shape) != (B * nws, plan.C)):
+        raise ValueError('cost must be (%d, %d): one value per cell of the chart' % (B * nws, plan.C))
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
+        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
+    for name, w in (('w_cost', w_cost), ('w_entropy', w_entropy)):
+        if w is not None and w.numel() != B * nws:
+            raise ValueError('%s must hold one value per sentence of the chart (%d)' % (name, B * nws))
+    with torch.cuda.device(dev):
+        count = split_score_count(plan)
+        lengths = lengths.to(dev).contiguous() if lengths is not None else None
+        cost = cost.to(dev).float().contiguous() if cost is not None else None
+        w_cost = w_cost.to(dev).contiguous().float().reshape(-1) if w_cost is not None else None
+        w_entropy = w_entropy.to(dev).contiguous().float().reshape(-1) if w_entropy is not None else None
+        buf = torch.empty(max(count * nws, 1), dtype=torch.float32, device=dev)      # (one word: no row, but the library wants an address)
+        risk, entropy, log_z = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(3))
+        status = torch.zeros(nws, dtype=torch.int32, device=dev)
+        sub = lambda t, sl: _p(t[sl]) if t is not None else None
+        for i, (ws, sl) in enumerate(parts):
+            _lib.call('cliora_tree_expectation', plan.handle, C.c_void_p(ws.data_ptr()), sub(lengths, sl), sub(cost, sl), sub(w_cost, sl),
+                      sub(w_entropy, sl), C.c_void_p(buf.data_ptr() + 4 * i * count), _p(risk[sl]), _p(entropy[sl]), _p(log_z[sl]),
+                      C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    return TreeExpectation(buf[:count * nws], risk, entropy, log_z, status)
+
+
+class _TreeObjective(torch.autograd.Function):
+    """(risk, entropy) as functions of the chart (formally: of its inside_s, as _BracketLogProb)."""
+
+    @staticmethod
+    def forward(ctx, inside_s, diora, cost):
+        res = tree_expectation(diora, cost)
+        ctx.chart = _ChartView(diora._plan, diora._wss)            # the plan and the forward's holder (workspace + slot)
+        ctx.cost, ctx.shape = cost, inside_s.shape
+        ctx.set_materialize_grads(False)
+        return res.risk, res.entropy
+
+    @staticmethod
+    def backward(ctx, g_risk, g_entropy):
+        if g_risk is None and g_entropy is None:
+            return None, None, None
+        holder = ctx.chart._wss
+        some = g_risk if g_risk is not None else g_entropy
+        zeros = torch.zeros_like(some)
+        d = tree_expectation(ctx.chart, ctx.cost, w_cost=zeros if g_risk is None else g_risk,
+                             w_entropy=zeros if g_entropy is None else g_entropy).d_split
+        slot = holder.split_cot
+        slot[0] = d if slot[0] is None else slot[0] + d
+        return torch.zeros(ctx.shape, dtype=torch.float32, device=d.device), None, None
+
+
+def tree_objective(diora, cost=None):
+    """(risk, entropy), two (B,) fp32 tensors in the autograd graph of the last forward of `diora`: the expected value of the
+    per-cell cost (fp32 (B, C) in the cell order of inside_s, ``span_costs``; None = 0) over the trees, and the entropy of the
+    distribution over trees.  Their cotangents reach the chart through the bracket loss's slot, into which they add: the objective
+    sums with ``bracket_log_prob`` and with a second call on the same forward.  The refusals are ``bracket_log_prob``'s."""
+    plan = diora._plan
+    if plan is None:
+        raise _lib.ChartLibError('tree_objective: the module has run no forward')
+    if plan.L > _lib.MAX_L:
+        raise _lib.ChartLibError('tree_objective: L = %d > %d is inference only (the backward stops at %d words), so the objective has '
+                                 'nothing to train through' % (plan.L, _lib.MAX_L, _lib.MAX_L))
+    if getattr(diora, 'plan_arch', 0) != 0:
+        raise _lib.ChartLibError('tree_objective: a TreeLSTM chart takes no cotangent on its split scores (cliora_lstm_backward has no such input)')
+    holder = diora._wss
+    if len(holder) != 1 or getattr(holder, 'split_cot', None) is None:
+        raise _lib.ChartLibError('tree_objective: the module holds %d workspaces that no single chart node owns; call it after each '
+                                 'forward of its own' % len(holder))
+    inside_s = diora.chart.inside_s
+    if not inside_s.requires_grad:
+        raise _lib.ChartLibError('tree_objective: the forward kept no backward state (it ran under torch.no_grad(), in eval mode '
+                                 'without gradients, or on a padded chart); tree_expectation gives the values alone')
+    return _TreeObjective.apply(inside_s, diora, cost)
+
+
+def _reduce(v, reduction):
+    if reduction not in ('mean', 'sum'):
+        raise ValueError("reduction must be 'mean' or 'sum'")
+    return v.mean() if reduction == 'mean' else v.sum()
+
+
+def expected_cost(diora, cost, reduction='mean'):
+    """The expected cost of the parse over the batch, a 0-d tensor in the graph: its mean ('mean') or sum ('sum')."""
+    return _reduce(tree_objective(diora, cost)[0], reduction)
+
+
+def parse_entropy(diora, reduction='mean'):
+    """The entropy of the distribution over trees over the batch, a 0-d tensor in the graph: its mean ('mean') or sum ('sum')."""
+    return _reduce(tree_objective(diora, None)[1], reduction)
+
+
+def span_costs(required, forbidden=None, L=None, device=None):
+    """Per-sentence lists of (start, end) spans (``brackets_from_entity_labels(..., drop_crossing=False)``: crossing phrases are
+    welcome) -> (B, C) fp32 costs in the cell order of inside_s for a chart of length L: [span is forbidden] - [span is required],
+    i.e. -1 on a required span, +1 on a forbidden one, 0 elsewhere.  A span that is not 0 <= start <= end < L is ignored."""
+    if L is None:
+        raise ValueError('span_costs: L, the length of the chart, is required')
+    L = int(L)
+    out = np.zeros((len(required), L * (L + 1) // 2), dtype=np.float32)
+    for lists, value in ((required, -1.0), (forbidden, 1.0)):
+        for b, spans in enumerate(lists or ()):
+            for s, e in set((int(s), int(e)) for s, e in spans):
+                if 0 <= s <= e < L:
+                    out[b, cell_id(L, e - s, s)] += value
+    t = torch.from_numpy(out)
+    return t.to(device) if device is not None else t
+
+
+def tree_expectation_numpy(pair_s, lengths, cost, w_cost=None, w_entropy=None):
+    """cliora_tree_expectation restated in fp64 from the definitions (tests): `pair_s[level]` (B, L - level, level[, 1]) the per-split
+    inside scores of the (padded) chart, sentence b its first lengths[b] words; cost (B, C) or None; w_cost (B,) or None = 1;
+    w_entropy (B,) or None = 0.  -> (G {level: (B, L - level, level)}, risk (B,), entropy (B,), log_z (B,)), zeros for a bad length.
+
+    The expectation semiring in the linear domain, with no logarithm but log_z: a cell carries the pair (Z, Zv) = (sum of the weights
+    of its subtrees, sum of weight x value), a product of pairs is (a b, a bv + av b); the outside pair (O, Ov) is pushed from every
+    parent to its two children.  Then sum over the trees through edge e of weight x V(T) is Ov Z_l Z_r w + O (Z_l Z_r w)v."""
+    lengths = [int(x) for x in lengths]
+    Bn = len(lengths)
+    levels = sorted(int(lv) for lv in pair_s)
+    L = (max(levels) + 1) if levels else 1
+    cost = np.zeros((Bn, L * (L + 1) // 2)) if cost is None else np.asarray(cost, dtype=np.float64)
+    w_cost = np.ones(Bn) if w_cost is None else np.asarray(w_cost, dtype=np.float64)
+    w_entropy = np.zeros(Bn) if w_entropy is None else np.asarray(w_entropy, dtype=np.float64)
+    G = {level: np.zeros((Bn, L - level, level)) for level in range(1, L)}
+    risk, entropy, log_z = np.zeros(Bn), np.zeros(Bn), np.zeros(Bn)
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= L:
+            continue
+        wc, we = w_cost[b], w_entropy[b]
+        c = np.zeros((n, n))
+        for level in range(n):
+            c0 = cell_id(L, level, 0)
+            c[level, :n - level] = cost[b, c0:c0 + n - level]
+        s, r, w, v = {}, {}, {}, {}
+        for level in range(1, n):
+            s[level] = np.asarray(pair_s[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
+            r[level] = s[level] - s[level].max(axis=1, keepdims=True)
+            w[level] = np.exp(r[level])
+            v[level] = wc * c[level, :n - level, None] - we * r[level]
+        Z, Zv = np.zeros((n, n)), np.zeros((n, n))
+        Z[0, :n], Zv[0, :n] = 1.0, wc * c[0, :n]
+        edge, edge_v = {}, {}                               # per edge: Z_l Z_r w and its value part
+        for level in range(1, n):
+            k, pos = np.arange(level)[None, :], np.arange(n - level)[:, None]
+            left, right = (k, pos), (level - k - 1, pos + k + 1)
+            edge[level] = Z[left] * Z[right] * w[level]
+            edge_v[level] = (Zv[left] * Z[right] + Z[left] * Zv[right]) * w[level] + edge[level] * v[level]
+            Z[level, :n - level], Zv[level, :n - level] = edge[level].sum(axis=1), edge_v[level].sum(axis=1)
+        O, Ov = np.zeros((n, n)), np.zeros((n, n))
+        O[n - 1, 0] = 1.0
+        for level in range(n - 1, 0, -1):
+            k = np.arange(level)
+            for pos in range(n - level):
+                left, right = (k, pos), (level - k - 1, pos + k + 1)
+                o = O[level, pos] * w[level][pos]
+                ov = Ov[level, pos] * w[level][pos] + o * v[level][pos]
+                O[left], Ov[left] = O[left] + o * Z[right], Ov[left] + ov * Z[right] + o * Zv[right]
+                O[right], Ov[right] = O[right] + o * Z[left], Ov[right] + ov * Z[left] + o * Zv[left]
+        total = Z[n - 1, 0]
+        mean_v = Zv[n - 1, 0] / total
+        log_z[b] = np.log(total)
+        risk[b] = sum(float((O[level, :n - level] * Z[level, :n - level] * c[level, :n - level]).sum()) for level in range(n)) / total
+        mean_r = 0.0
+        for level in range(1, n):
+            o, ov = O[level, :n - level, None], Ov[level, :n - level, None]
+            nu = o * edge[level] / total
+            d = (ov * edge[level] + o * edge_v[level]) / total - nu * mean_v
+            mean_r += float((nu * r[level]).sum())
+            d[np.arange(n - level), np.argmax(s[level], axis=1)] -= d.sum(axis=1)
+            G[level][b, :n - level] = d
+        entropy[b] = log_z[b] - mean_r
+    return G, risk, entropy, log_z

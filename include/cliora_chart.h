@@ -464,6 +464,33 @@ size_t cliora_plan_split_score_count(const cliora_plan* plan);   /* floats in th
 int cliora_bracket_grad(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* brackets, int M,
                         const float* weights, float* d_split, float* log_prob_out, int32_t* feasible_out, int32_t* status,
                         void* stream);
+/* Expectations under the same distribution over binary trees, with their gradient: per sentence
+ *   risk    = E_T[sum of cost[cell] over the cells of T, leaves and root included] = sum over the triangle of mu[cell] * cost[cell]
+ *   entropy = -sum_T p(T) log p(T) = log_z - E_T[sum of r over T's edges]
+ *   d_split = d (w_cost[b] * risk + w_entropy[b] * entropy) / d s over the per-split inside scores.
+ * With v[cell, k] = w_cost * cost[cell] - w_entropy * r[cell, k], V(T) its sum over the tree's edges plus w_cost * cost over its leaves:
+ *   d_split[cell, k] = G_r[cell, k] - [k == k*] * sum_k G_r[cell, .],   G_r[e] = nu[e] * (E[V | e in T] - E[V])
+ * nu the edge marginal and k* the first maximum of the cell's scores, as cliora_bracket_grad has them: every row sums to zero.  The
+ * conditional means come from an inside and an outside mean table beside the two log-space tables (an expectation-semiring pass),
+ * all in fp64, sums in a fixed order; the outputs are fp32.
+ *   cost (B, C) fp32 device in the cell order of inside_s / the marginals of cliora_span_posteriors, or NULL = 0; costs of cells
+ *     beyond a sentence's triangle are never read.  w_cost (B) fp32 device or NULL = 1; w_entropy (B) fp32 device or NULL = 0: in a
+ *     backward, the cotangents of risk and entropy.
+ *   d_split: cliora_plan_split_score_count floats in the layout cliora_bracket_grad writes.  EVERY element is written (no memset is
+ *     needed); cells beyond a sentence's triangle get zeros.
+ *   risk_out, entropy_out, log_z_out (B) fp32; none depends on the weights.  One word: risk = cost[leaf], entropy = 0.  Two words:
+ *     risk is the sum of the three costs, entropy = 0 and the gradient is exactly 0.
+ *   lengths (B) int32 device or NULL; status: an int32 on the device, zeroed by the call, always required: it counts the lengths
+ *     outside [1, L].  Such a sentence gets a zero gradient and risk = entropy = log_z = 0; its weights, costs and scores are not
+ *     read.  With every length equal to L the outputs are bitwise those of the lengths == NULL call.
+ * One workgroup per sentence, a wavefront per cell, each element written by one lane, no floating-point atomics: two calls give equal
+ * bits, and a sentence of a padded chart gets the bits it gets alone.  The tables fit the LDS (36 C + 4 L + 128 bytes: 73.5 KiB at
+ * L 64): no scratch.  Refused with CLIORA_EINVAL and a message, before any launch: a long plan (L > 64: the backward stops at 64
+ * words, so nothing could take the gradient); a NULL plan, workspace, d_split, scalar output or status; a plan that has not run a
+ * forward. */
+int cliora_tree_expectation(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const float* cost, const float* w_cost,
+                            const float* w_entropy, float* d_split, float* risk_out, float* entropy_out, float* log_z_out,
+                            int32_t* status, void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
