@@ -11,9 +11,9 @@ pytestmark = pytest.mark.gpu
 KEYS = ('inside_h', 'inside_c', 'inside_s', 'outside_h', 'outside_c', 'outside_s')
 
 
-def _module(P, D, share=True):
+def _module(P, D, share=True, outside=True):
     from cliora_amd.treelstm import DioraTreeLSTM
-    m = DioraTreeLSTM(D, share=share)
+    m = DioraTreeLSTM(D, share=share, outside=outside)
     sd = m.state_dict()
     for k in sd:
         sd[k] = P[k if k in P else 'inside_' + k[len('outside_'):]].detach().clone()
