@@ -52,6 +52,8 @@ ABI = {
     'cliora_chart_backward': (i32, [vp, pp] + [vp] * 11 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_backward_split': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_forward_ragged': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
+    'cliora_chart_forward_ragged_train': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
+    'cliora_chart_backward_ragged': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp, u64] + [vp] * 4 + [vp]),
     'cliora_lstm_forward': (i32, [vp, pp] + [vp] * 7 + [vp, sz, i32, vp]),
     'cliora_lstm_backward': (i32, [vp, pp] + [vp] * 13 + [vp, sz, vp, sz, vp, pp, i32, vp]),
     'cliora_inside_pair_states': (i32, [vp, vp, i32, pvp, pvp, psz, psz]),

@@ -91,6 +91,15 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
                              float* inside_h, float* inside_s, float* outside_h, float* outside_s, float* inside_c, void* fwd_ws,
                              size_t fwd_ws_bytes, int run_outside, void* stream, const RaggedFwd* rg);
 
+// cliora_chart_backward_ragged's extra arguments (api_ragged.hip), handed to the backward's body (api_mlp.hip: BwdCall): the caller's
+// four chart cotangents (inside_h, inside_s, outside_h, outside_s; NULL = zero) and the buffers their masked copies go to
+struct RaggedBwd { const int32_t* lengths; uint64_t root_levels; const float* cot[4]; float* masked[4]; };
+int cliora_chart_backward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span, const float* drop_mask,
+                              const float* inside_h, const float* inside_s, const float* outside_h, const float* outside_s,
+                              const float* d_inside_h, const float* d_inside_s, const float* d_outside_h, const float* d_outside_s,
+                              const float* d_split_s, void* fwd_ws, size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, float* d_x_span,
+                              float* d_obj_span, const cliora_params* G, int ran_outside, void* stream, const RaggedBwd* rg);
+
 constexpr size_t TRACE_BYTES = (size_t)256 * 4 * (CLIORA_MAX_L + 1) * 10 * 8;   // diagnostic stamp words per device
 
 // ------------------------------------------------------------------ profiling (HIP events)

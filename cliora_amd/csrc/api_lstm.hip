@@ -254,8 +254,8 @@ extern "C" int cliora_lstm_backward(cliora_plan* plan, const cliora_params* P, c
             OKR(launch_rows_direct(sb, ws + f.w1roT, PROJ_IMG(f.w1roT3), ldpo, Dp, ncell, LevelRowsA{dPO, ldpo, C, g.off, g.Lc},
                                    StoreLevelE{VHo, Dp, C, g.off, g.Lc, nullptr, 1}));
         if (level == L - 1) {
-            hipLaunchKernelGGL(root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, sb, B, C, Dp, VHo, OH, ws + f.nrmo, p.normalize, wb + bw.groot);
-            hipLaunchKernelGGL(root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, sb, B, C, Dp, VCo, OC, ws + f.nrmoc, p.normalize, wb + bw.grootc);
+            hipLaunchKernelGGL(root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, sb, B, C, Dp, VHo, OH, ws + f.nrmo, p.normalize, wb + bw.groot, (const int32_t*)nullptr, L);
+            hipLaunchKernelGGL(root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, sb, B, C, Dp, VCo, OC, ws + f.nrmoc, p.normalize, wb + bw.grootc, (const int32_t*)nullptr, L);
             LAUNCHOK("root_bwd");
             return CLIORA_OK;
         }

@@ -614,6 +614,7 @@ struct BwdCall {
     float *ws, *wb, *d_x_span, *d_obj_span;
     int ran_outside;
     hipStream_t st;                           // the caller's stream: head, inside chain, tail
+    const RaggedBwd* rg;                      // cliora_chart_backward_ragged: mixed lengths in one padded chart (the d_* above are its masked copies), or NULL
 
     const Plan& p = plan->p;
     const FwdLayout& f = p.fwd;
@@ -624,7 +625,7 @@ struct BwdCall {
     // compress = True: the outside root's gradient flows into the inside root, so the outside backward ends before the inside one starts
     const bool compress = P && P->root_mat;
     const BwdSchedule schedule = compress ? BwdSchedule::OutsideThenInside       // the one place that picks the backward's schedule
-                               : !d_split_s && resident_pays(plan, vl, compress) ? BwdSchedule::Resident : BwdSchedule::Wavefront;      // (the resident kernels take no split cotangent)
+                               : !d_split_s && !rg && resident_pays(plan, vl, compress) ? BwdSchedule::Resident : BwdSchedule::Wavefront;      // (the resident kernels take no split cotangent and no padded chart)
     const bool resident = schedule == BwdSchedule::Resident;
     const bool two_streams = schedule == BwdSchedule::Wavefront && ran_outside && wavefront_pays(p, g_cliora_wavefront);
     const hipStream_t sb = two_streams ? plan->side : st, sw = plan->side2;      // the outside chain's stream; the GEMM stream
@@ -689,9 +690,13 @@ struct BwdCall {
     int outside_bwd_step(int level, hipEvent_t done) const {
         const LevelArgs g = level_args(p, level, true);     // N == 0 at the root level
         const int ncell = B * g.Lc;
+        // A padded chart (ragged_kernels.hpp): the level holds some sentence's own root cell (level, 0).  What accumulates in that cell's
+        // VHo is the root vector's (root_bwd reads it at the last step), so the level keeps the unfused pair -- the fused epilogue
+        // leaves VHo without the projection's share -- and the cell is cut out of the compose and softmax backward below.
+        const bool root_level = rg && level < L - 1 && ((rg->root_levels >> level) & 1);
         // levels 1 .. L-2: the unit-norm backward rides in the projection-backward GEMM's epilogue (NormBwdLevelE; the gather leaves
         // H . vH behind), no cell_dnorm launch
-        const bool fused_norm = fuse_dnorm && level >= 1 && level <= L - 2;
+        const bool fused_norm = fuse_dnorm && level >= 1 && level <= L - 2 && !root_level;
         hipLaunchKernelGGL(cell_gather_bwd_out, dim3(ncell), dim3(256), 0, sb, g, p.D, d_outside_h,
                            level == L - 1 ? nullptr : d_outside_s, dv.use[ROLE_OUTB], DA, DS, PI, ldpi, p.blk_qlo, dPO, VHo, dStoto,
                            OH, ws + f.po, fused_norm ? wb + bw.dots_o : nullptr);
@@ -703,13 +708,18 @@ struct BwdCall {
                 LAUNCHOK("cell_dnorm(root)");
                 return CLIORA_OK;
             }
-            LAUNCH_SIGNALLING(done, root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, sb, B, C, Dp, VHo, OH, ws + f.nrmo, p.normalize, wb + bw.groot);
+            LAUNCH_SIGNALLING(done, root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, sb, B, C, Dp, VHo, OH, ws + f.nrmo, p.normalize, wb + bw.groot,
+                              rg ? rg->lengths : (const int32_t*)nullptr, L);
             LAUNCHOK("root_bwd");
             return CLIORA_OK;
         }
         if (!fused_norm) {
             hipLaunchKernelGGL(cell_dnorm, dim3(cells_grid(ncell)), dim3(256), 0, sb, g, VHo, OH, ws + f.nrmo, p.normalize, dGo);
             LAUNCHOK("cell_dnorm(out)");
+        }
+        if (root_level) {
+            hipLaunchKernelGGL(ragged_root_cut, dim3(B), dim3(64), 0, sb, level, g.off, C, Dp, rg->lengths, dGo, dStoto);
+            LAUNCHOK("ragged_root_cut");
         }
         {
             ProfScope ps(CLIORA_KCLASS_COMPOSE_BWD, sb);
@@ -1022,7 +1032,8 @@ struct BwdCall {
             LAUNCHOK("resident_bwd");
         }
         if (ran_outside) {
-            hipLaunchKernelGGL(root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, st, p.B, p.C, p.Dp, VHo, OH, ws + f.nrmo, p.normalize, wb + bw.groot);
+            hipLaunchKernelGGL(root_bwd, dim3(1), dim3(ROOT_WAVES * 64), 0, st, p.B, p.C, p.Dp, VHo, OH, ws + f.nrmo, p.normalize, wb + bw.groot,
+                               (const int32_t*)nullptr, p.L);
             LAUNCHOK("root_bwd");
         }
         return CLIORA_OK;
@@ -1032,6 +1043,12 @@ struct BwdCall {
         WgradPlacement w = wgrad_placement();
         if (!resident && plan->take_imageless(ws))            // the forward ran on the resident kernels and left the weight images out
             OKR(build_chart_images(plan, ws, compress, st));
+        if (rg) {      // the cotangents of the cells beyond each sentence's triangle must not leak: the chains read the masked copies
+            RaggedCots rc;
+            for (int k = 0; k < 4; ++k) { rc.src[k] = rg->cot[k]; rc.dst[k] = rg->masked[k]; }
+            hipLaunchKernelGGL(ragged_mask_cotangents, dim3(cells_grid(B * C)), dim3(256), 0, st, B, L, C, D, rg->lengths, rc);
+            LAUNCHOK("ragged_mask_cotangents");
+        }
         if (two_streams) {
             HIPOK(hipEventRecord(plan->ev_fork[0], st));
             HIPOK(hipStreamWaitEvent(sb, plan->ev_fork[0], 0));
@@ -1061,12 +1078,14 @@ struct BwdCall {
     }
 };
 
-extern "C" int cliora_chart_backward_split(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
-                                     const float* drop_mask, const float* inside_h, const float* inside_s,
-                                     const float* outside_h, const float* outside_s, const float* d_inside_h,
-                                     const float* d_inside_s, const float* d_outside_h, const float* d_outside_s, const float* d_split_s,
-                                     void* fwd_ws, size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, float* d_x_span,
-                                     float* d_obj_span, const cliora_params* G, int ran_outside, void* stream) {
+// The body of cliora_chart_backward_split.  rg == nullptr: that entry, launch for launch.  rg != nullptr: cliora_chart_backward_ragged
+// (api_ragged.hip, which has checked its own refusals); d_inside_h .. d_outside_s are then the buffers of the masked cotangents.
+int cliora_chart_backward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                              const float* drop_mask, const float* inside_h, const float* inside_s,
+                              const float* outside_h, const float* outside_s, const float* d_inside_h,
+                              const float* d_inside_s, const float* d_outside_h, const float* d_outside_s, const float* d_split_s,
+                              void* fwd_ws, size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, float* d_x_span,
+                              float* d_obj_span, const cliora_params* G, int ran_outside, void* stream, const RaggedBwd* rg) {
     // every refusal before the first launch
     if (!plan || !x_span || !inside_h || !inside_s || !outside_h || !outside_s || !fwd_ws || !bwd_ws || !G)
         return fail(CLIORA_EINVAL, "NULL argument");
@@ -1085,7 +1104,18 @@ extern "C" int cliora_chart_backward_split(cliora_plan* plan, const cliora_param
     ForkGuard fork_guard(st);
     fork_guard.arm(1, plan->side2, plan->ev_join[1]);     // the weight-gradient stream takes work at several points of the call
     return BwdCall{plan, P, G, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, d_inside_h, d_inside_s, d_outside_h, d_outside_s, d_split_s,
-                    (float*)fwd_ws, (float*)bwd_ws, d_x_span, d_obj_span, ran_outside, st}.run(fork_guard);
+                    (float*)fwd_ws, (float*)bwd_ws, d_x_span, d_obj_span, ran_outside, st, rg}.run(fork_guard);
+}
+
+extern "C" int cliora_chart_backward_split(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                                     const float* drop_mask, const float* inside_h, const float* inside_s,
+                                     const float* outside_h, const float* outside_s, const float* d_inside_h,
+                                     const float* d_inside_s, const float* d_outside_h, const float* d_outside_s, const float* d_split_s,
+                                     void* fwd_ws, size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, float* d_x_span,
+                                     float* d_obj_span, const cliora_params* G, int ran_outside, void* stream) {
+    return cliora_chart_backward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, d_inside_h, d_inside_s,
+                                     d_outside_h, d_outside_s, d_split_s, fwd_ws, fwd_ws_bytes, bwd_ws, bwd_ws_bytes, d_x_span, d_obj_span, G,
+                                     ran_outside, stream, nullptr);
 }
 
 extern "C" int cliora_chart_backward(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,

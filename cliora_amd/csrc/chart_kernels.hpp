@@ -459,16 +459,24 @@ static __global__ __launch_bounds__(256) void leaf_bwd_pre(int B, int L, int C, 
 // d root_vector = sum_b normbwd(vH[b, root]).  One workgroup of 16 waves: wave w takes sentences w, w+16, ... (a lane
 // owns columns lane, lane+64, ...; the row dot product is a wave reduction), the 16 partial vectors meet in LDS and are
 // added in wave order -- a fixed summation order, so the result is bitwise reproducible.
+// lengths != NULL (a padded chart of mixed lengths, ragged_kernels.hpp): the root of sentence b is ITS cell (n_b - 1, 0), which holds
+// copies of the seed's rows; n_b is clamped to [1, L].  Same sentences per wave, same order: with every n_b = L the same bits.
 constexpr int ROOT_WAVES = 16;
 static __global__ __launch_bounds__(ROOT_WAVES * 64) void root_bwd(int B, int C, int Dp, const float* __restrict__ VH, const float* __restrict__ H,
-                                                            const float* __restrict__ nrm, int normalize, float* __restrict__ groot) {
+                                                            const float* __restrict__ nrm, int normalize, float* __restrict__ groot,
+                                                            const int32_t* __restrict__ lengths, int L) {
     __shared__ float part[ROOT_WAVES][512];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float acc[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = 0.f;
     for (int b = wave; b < B; b += ROOT_WAVES) {
-        const size_t crow = (size_t)b * C + C - 1;
+        int root = C - 1;
+        if (lengths) {
+            const int lv = min(max(lengths[b], 1), L) - 1;      // the first cell of level lv
+            root = lv * L - lv * (lv - 1) / 2;
+        }
+        const size_t crow = (size_t)b * C + root;
         float v[8], h[8];
         float dot = 0.f;
 #pragma unroll

@@ -1,6 +1,7 @@
 // Sentences of DIFFERENT lengths that share one right-padded chart of length L (include/cliora_chart.h): the two kernels that turn
-// the padded chart's outside pass into each sentence's own (cliora_chart_forward_ragged).  The decode of each sentence's own triangle
-// (cliora_cky_spans_ragged) is cky_kernel with lengths (decode_kernels.hpp).
+// the padded chart's outside pass into each sentence's own (cliora_chart_forward_ragged), and the two that make the unchanged backward
+// chains compute each sentence's own gradient (cliora_chart_backward_ragged; root_bwd, chart_kernels.hpp, takes the per-sentence root
+// cell).  The decode of each sentence's own triangle (cliora_cky_spans_ragged) is cky_kernel with lengths (decode_kernels.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,6 +54,52 @@ static __global__ __launch_bounds__(256) void ragged_root_seed(int level, int of
         float* S = wave == 2 ? OS : nrmo;
         S[dst] = S[src];
     }
+}
+
+// ---------------------------------------------------------------------------------
+// The backward of a padded chart.  The chains of cliora_chart_backward compute each sentence's own gradient
+// when (1) the cotangents of the cells beyond its triangle are zero -- those cells are unspecified outputs -- (2) every invalid pair
+// carries a softmax weight of exactly 0, which the forward's mask has seen to, and (3) the sentence's root cell (n - 1, 0) is cut out
+// of the outside backward: its forward value is the seed, not its level's compose output, so what has accumulated in its vH belongs
+// to the root vector (root_bwd) and nothing of it may flow into the compose backward of its level.
+// ---------------------------------------------------------------------------------
+// The four chart cotangents (inside_h, inside_s, outside_h, outside_s) and the caller's buffers for their masked copies; a NULL
+// source stays NULL (its destination is not touched).
+struct RaggedCots { const float* src[4]; float* dst[4]; };
+
+// One wavefront per (sentence, cell) row: the row is copied inside the sentence's triangle and written as zero beyond it (a select,
+// never a product: whatever the source holds there, NaN included, does not get through).  Rows of the vector charts hold D floats
+// at the caller's stride D.  n < 1 zeroes every row of the sentence, n > L none (the forward has counted such a length in its status).
+static __global__ __launch_bounds__(256) void ragged_mask_cotangents(int B, int L, int C, int D, const int32_t* __restrict__ lengths,
+                                                                     RaggedCots rc) {
+    const int lane = threadIdx.x & 63;
+    const size_t i = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= (size_t)B * C) return;
+    const int b = (int)(i / C), cell = (int)(i - (size_t)b * C);
+    int level = 0, off = 0;                          // the level whose cells [off, off + L - level) hold `cell`
+    while (cell >= off + (L - level)) { off += L - level; ++level; }
+    const bool own = (cell - off) + level < lengths[b];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!rc.src[k]) continue;
+        if (k & 1) {
+            if (lane == 0) rc.dst[k][i] = own ? rc.src[k][i] : 0.f;
+        } else {
+            for (int c = lane; c < D; c += 64) rc.dst[k][i * D + c] = own ? rc.src[k][i * D + c] : 0.f;
+        }
+    }
+}
+
+// Outside backward of level `level` < L - 1, between the unit-norm backward and the compose backward: for every sentence whose own
+// root is cell (level, 0) = chart row off0, the cell's dGo row and its dStoto become zero, so that its pair rows get DA = DZ = 0 and
+// ds = 0 from the kernels as they are.  One workgroup (a wavefront) per sentence; sentences of other lengths return at once.
+static __global__ __launch_bounds__(64) void ragged_root_cut(int level, int off0, int C, int Dp, const int32_t* __restrict__ lengths,
+                                                             float* __restrict__ dGo, float* __restrict__ dStoto) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (lengths[b] - 1 != level) return;
+    const size_t row = (size_t)b * C + off0;
+    for (int c = 4 * lane; c < Dp; c += 256) st4(dGo + row * Dp + c, f4zero());
+    if (lane == 0) dStoto[row] = 0.f;
 }
 
 }  // namespace cliora

@@ -67,12 +67,15 @@ def _cont(g):
 class ChartWorkspaces(list):
     """The holder of a forward's workspace(s), made anew by every forward of a chart module, with the slot through which
     cliora_amd.structured hands the chart node a cotangent on the inside split scores: `split_cot` is a one-element list that the
-    node of that forward shares (ChartFunction keeps it in its ctx), so a cotangent left there can reach that forward's backward only."""
-    __slots__ = ('split_cot',)
+    node of that forward shares (ChartFunction keeps it in its ctx), so a cotangent left there can reach that forward's backward only.
+    `lengths`: the int32 device lengths of a padded training chart of mixed lengths (RaggedChartFunction), else None; the structured
+    losses read each sentence's own triangle through them."""
+    __slots__ = ('split_cot', 'lengths')
 
     def __init__(self):
         super().__init__()
         self.split_cot = [None]
+        self.lengths = None
 
 
 class ChartFunction(torch.autograd.Function):
@@ -136,6 +139,65 @@ class ChartFunction(torch.autograd.Function):
         return (None, None, None, d_x, d_obj, None) + tuple(g[n] for n in _lib.PARAM_FIELDS)
 
 
+def _check_lengths(plan, lengths, dev):
+    if lengths.dtype != torch.int32 or lengths.numel() != plan.B or lengths.device != dev:
+        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (plan.B, dev))
+
+
+class RaggedChartFunction(torch.autograd.Function):
+    """ChartFunction for a right-padded batch of mixed lengths, text-only.
+
+    forward  -> cliora_chart_forward_ragged_train   (the padded chart's schedule with the backward's state written)
+    backward -> cliora_chart_backward_ragged        (the split cotangent of a structured loss of the same forward included)
+    Inputs: plan, holder, run_outside, lengths (int32 device tensor (B,)), root_levels (the bit mask of {n - 1}), x_span, then the
+    parameter tensors in _lib.PARAM_FIELDS order.  Outputs: the four charts -- valid on each sentence's own triangle, unspecified
+    beyond it, where their cotangents are ignored -- and the status word (1,) int32 on the device, which the caller must read."""
+
+    @staticmethod
+    def forward(ctx, plan, holder, run_outside, lengths, root_levels, x_span, *params):
+        if not x_span.is_cuda:
+            raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
+        D, run_outside, dev = plan.D, int(run_outside), x_span.device
+        _check_lengths(plan, lengths, dev)
+        x_span, lengths = x_span.contiguous().float(), lengths.contiguous()
+        ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
+        with _lib.device_guard(x_span):
+            outs, ws, nbytes = chart_buffers(plan, dev, run_outside, D, 1, D, 1)
+            status = torch.empty(1, device=dev, dtype=torch.int32)
+            pst = _param_struct(ptens)
+            _lib.call('cliora_chart_forward_ragged_train', plan.handle, C.byref(pst), _ptr(x_span), None, None, *map(_ptr, outs), None,
+                      _ptr(ws), nbytes, run_outside, _ptr(lengths), int(root_levels), _ptr(status), _stream())
+        ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.root_levels = plan, run_outside & 1, ws, ptens, int(root_levels)
+        ctx.split_cot = getattr(holder, 'split_cot', None)
+        ctx.save_for_backward(x_span, lengths, *outs)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(status)
+        holder.clear()
+        holder.append(ws)
+        holder.lengths = lengths
+        return (*outs, status)
+
+    @staticmethod
+    def backward(ctx, d_ih, d_is, d_oh, d_os, _d_status):
+        plan, saved = ctx.plan, ctx.saved_tensors
+        x_span, lengths = saved[0], saved[1]
+        with _lib.device_guard(x_span):
+            d_x = torch.empty_like(x_span)
+            pst = _param_struct(ctx.ptens)
+            g = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
+            wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
+            gst = _param_struct(g)
+            d_split = ctx.split_cot[0] if ctx.split_cot is not None else None
+            if d_split is not None:
+                ctx.split_cot[0] = None                       # taken once
+            cots = [_cont(d) for d in (d_ih, d_is, d_oh, d_os)]
+            masked = [torch.empty_like(d) if d is not None else None for d in cots]      # the library masks the cotangents into these
+            _lib.call('cliora_chart_backward_ragged', plan.handle, C.byref(pst), _ptr(x_span), None, None, *map(_ptr, saved[-4:]),
+                      *map(_ptr, cots), _ptr(d_split), _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), None,
+                      C.byref(gst), ctx.run_outside, _ptr(lengths), ctx.root_levels, *map(_ptr, masked), _stream())
+        return (None, None, None, None, None, d_x) + tuple(g[n] for n in _lib.PARAM_FIELDS)
+
+
 def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_levels):
     """cliora_chart_forward_ragged (include/cliora_chart.h): both passes of a right-padded batch of mixed lengths, inference only, so no
     autograd node.  lengths: int32 device tensor (B,); root_levels: the bit mask of {n - 1}.  -> inside_h, inside_s, outside_h,
@@ -143,8 +205,7 @@ def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_
     if not x_span.is_cuda:
         raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
     D, dev, vl = plan.D, x_span.device, obj_span is not None
-    if lengths.dtype != torch.int32 or lengths.numel() != plan.B or lengths.device != dev:
-        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (plan.B, dev))
+    _check_lengths(plan, lengths, dev)
     x_span, obj_span = x_span.detach().contiguous().float(), _cont(obj_span.detach() if vl else None)
     lengths = lengths.contiguous()
     ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
@@ -228,6 +289,9 @@ class DioraBase(nn.Module):
         # cliora_amd.ragged sets (lengths on the device, root-level mask) around an eval forward over a right-padded batch of mixed
         # lengths: the chart then runs through cliora_chart_forward_ragged and leaves its status word in _ragged_status
         self.__dict__['_ragged'] = None
+        # cliora_amd.ragged sets the same pair around a TRAINING forward over such a batch (forward_ragged_train): the chart then is a
+        # RaggedChartFunction node, text-only DIORA only
+        self.__dict__['_ragged_train'] = None
         self.init_parameters()
         self.reset_parameters()
         self.reset()
@@ -311,6 +375,22 @@ class DioraBase(nn.Module):
         if self.compress:
             raise NotImplementedError('compress = True is not supported on a padded chart of mixed lengths')
 
+    def _check_ragged_train(self, L, hooks):
+        """A padded chart of mixed lengths with a backward: every refusal before any launch."""
+        if self.vision_language or self.plan_arch != 0:
+            raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP)')
+        if L > _lib.MAX_L:
+            raise _lib.ChartLibError('L = %d > %d: a padded chart of mixed lengths trains through at most %d words' % (L, _lib.MAX_L, _lib.MAX_L))
+        if hooks:
+            raise NotImplementedError('inside_hook / outside_hook overrides get no per-pair states from a padded chart of mixed lengths')
+        if self.compress:
+            raise NotImplementedError('compress = True is not supported on a padded chart of mixed lengths')
+
+    def _run_ragged_train(self, plan, holder, x_span, params, ragged):
+        """_run_chart through RaggedChartFunction; the status word is left in _ragged_status."""
+        *charts, self.__dict__['_ragged_status'] = RaggedChartFunction.apply(plan, holder, int(bool(self.outside)), *ragged, x_span, *params)
+        return (*charts, None, None)
+
     def _hook_overridden(self, name):
         return name in self.__dict__ or getattr(type(self), name) is not getattr(DioraBase, name)
 
@@ -370,10 +450,16 @@ class DioraBase(nn.Module):
         self._check_long(L, needs_grad, hooks)
         plan = _lib.get_plan(B, L, D, self.share, self.normalize, R, dev_index, arch=self.plan_arch)
         flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
-        ragged = self.__dict__.get('_ragged')
+        ragged, ragged_train = self.__dict__.get('_ragged'), self.__dict__.get('_ragged_train')
         if ragged is not None:
             self._check_ragged(needs_grad, hooks)
             charts = self._run_ragged(plan, holder, x_span, obj_embed_span, params, ragged)
+        elif ragged_train is not None and needs_grad:
+            self._check_ragged_train(L, hooks)
+            charts = self._run_ragged_train(plan, holder, x_span, params, ragged_train)
+        elif ragged_train is not None:
+            raise _lib.ChartLibError('a padded training chart of mixed lengths needs gradients enabled; cliora_amd.ragged.forward_ragged '
+                                     'runs the same batch for inference')
         else:
             charts = self._run_chart(plan, holder, flags, x_span, obj_embed_span, params)
         ch = Chart()

@@ -294,11 +294,19 @@ class Net(nn.Module):
                 v = fn(self.diora.vg_atten_score)
             ret[name] = v
             parts.append(v)
+        for name, v in self.structured_losses(entity_labels, tokens.shape[1], tokens.device):
+            ret[name] = v
+            parts.append(v)
+        ret.parts = parts
+        return ret
+
+    def structured_losses(self, entity_labels, L, device):
+        """The weighted structured terms of the chart self.diora holds (cliora_amd.structured), as (name, 0-d tensor) in the order they
+        join the total: bracket_nll and risk for a batch that carries entity_labels, entropy for a training step.  L: the chart's length."""
+        out = []
         if entity_labels is not None and self.bracket_loss_weight > 0:
             from .constrained import brackets_from_entity_labels
-            v = self.bracket_loss_weight * self.diora.bracket_nll(brackets_from_entity_labels(entity_labels))
-            ret['bracket_nll'] = v
-            parts.append(v)
+            out.append(('bracket_nll', self.bracket_loss_weight * self.diora.bracket_nll(brackets_from_entity_labels(entity_labels))))
         use_risk = entity_labels is not None and self.risk_loss_weight > 0
         use_entropy = self.entropy_loss_weight != 0 and self.training and torch.is_grad_enabled()
         if use_risk or use_entropy:                             # one node for both: one kernel launch each way
@@ -306,16 +314,13 @@ class Net(nn.Module):
             from .structured import span_costs
             cost = None
             if use_risk:
-                cost = span_costs(brackets_from_entity_labels(entity_labels, drop_crossing=False), L=tokens.shape[1], device=tokens.device)
+                cost = span_costs(brackets_from_entity_labels(entity_labels, drop_crossing=False), L=L, device=device)
             risk, entropy = self.diora.tree_objective(cost)
             if use_risk:
-                ret['risk'] = v = self.risk_loss_weight * risk.mean()
-                parts.append(v)
+                out.append(('risk', self.risk_loss_weight * risk.mean()))
             if use_entropy:
-                ret['entropy'] = v = self.entropy_loss_weight * entropy.mean()
-                parts.append(v)
-        ret.parts = parts
-        return ret
+                out.append(('entropy', self.entropy_loss_weight * entropy.mean()))
+        return out
 
 
 def select_diora(arch, obj_feats):
@@ -397,30 +402,64 @@ class Trainer(object):
             self._loss_pending = True
             loss_ev = self._loss_ev
         if train:
-            self.optimizer.zero_grad()
-            # this step owns its gradients from backward to the update, so the embedding table's gradient is assembled once, in the flat
-            # buffer, from every lookup's rows (heads.DeferredTableGrads) instead of one dense scatter per lookup + dense adds
-            defer = heads.DeferredTableGrads(self.optimizer.grads) if (self.fused and self.defer_table_grads) else None
-            heads._deferred = defer
-            heads._step_lanes = lanes = set() if self.fused else None
-            try:
-                total.backward()
-            finally:
-                heads._deferred = None
-                heads._step_lanes = None
-            for lane in (lanes or ()):               # leaf gradients that backward nodes left to the caller lane (heads._step_lane)
-                torch.cuda.current_stream(lane.device).wait_stream(lane)
-            if defer is not None:
-                defer.flush()
-            if self.reducer is not None:
-                self.reducer.all_reduce_mean()
-            if self.fused:
-                self.optimizer.step(gathered=self.reducer is not None and self.optimizer.grads is self.reducer)
-            else:
-                torch.nn.utils.clip_grad_norm_(self.params, 5.0)
-                self.optimizer.step()
+            self._backward_and_update(total)
         if loss_ev is not None:
             loss_ev.synchronize()
             self._loss_pending = False
             return {'total_loss': float(self._loss_host)}
         return {'total_loss': float(total.detach()) if sync else total.detach()}
+
+    def _backward_and_update(self, total):
+        """backward, all-reduce, clip 5.0 + Adam (trainer.py:483-501) from the step's scalar loss."""
+        self.optimizer.zero_grad()
+        # this step owns its gradients from backward to the update, so the embedding table's gradient is assembled once, in the flat
+        # buffer, from every lookup's rows (heads.DeferredTableGrads) instead of one dense scatter per lookup + dense adds
+        defer = heads.DeferredTableGrads(self.optimizer.grads) if (self.fused and self.defer_table_grads) else None
+        heads._deferred = defer
+        heads._step_lanes = lanes = set() if self.fused else None
+        try:
+            total.backward()
+        finally:
+            heads._deferred = None
+            heads._step_lanes = None
+        for lane in (lanes or ()):               # leaf gradients that backward nodes left to the caller lane (heads._step_lane)
+            torch.cuda.current_stream(lane.device).wait_stream(lane)
+        if defer is not None:
+            defer.flush()
+        if self.reducer is not None:
+            self.reducer.all_reduce_mean()
+        if self.fused:
+            self.optimizer.step(gathered=self.reducer is not None and self.optimizer.grads is self.reducer)
+        else:
+            torch.nn.utils.clip_grad_norm_(self.params, 5.0)
+            self.optimizer.step()
+
+    def step_ragged(self, sentences, neg_samples=None, entity_labels=None, max_batch=64, max_waste=None, pad_id=0):
+        """One optimizer step over sentences of any lengths in 1..64, text-only DIORA: the sentences are packed into right-padded
+        charts (cliora_amd.ragged.forward_ragged_train), each pack's loss is weighted by its share of the tokens -- the reconstruction
+        term of the step is therefore ONE mean over all tokens, what ``step`` gives for a batch of one length -- and one backward and
+        one update follow.  entity_labels: per sentence, as batch_map['entity_labels'], for the bracket / risk terms.  Returns the
+        loss as a Python float."""
+        from . import ragged
+        if 'reconstruct_softmax_loss' not in self.net.loss_func_names:
+            raise NotImplementedError('step_ragged trains the reconstruction loss of a text-only net')
+        net = self.net
+        net.train(True)
+        if neg_samples is None and self.negative_sampler is not None:
+            neg_samples = self.negative_sampler.sample(self.k_neg)
+        n_tokens = float(sum(len(s) for s in sentences))
+        total = None
+        with torch.enable_grad():
+            for idx, _, diora in ragged.forward_ragged_train(net, sentences, max_batch=max_batch, pad_id=pad_id,
+                                                             max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste):
+                group = [sentences[i] for i in idx]
+                labels = [entity_labels[i] for i in idx] if entity_labels is not None else None
+                part = ragged.reconstruction_loss_ragged(net, group, neg_samples, diora)
+                for _, v in net.structured_losses(labels, diora._plan.L, part.device):      # each sentence's own triangle (the holder's lengths)
+                    part = part + v
+                part = part * (sum(len(s) for s in group) / n_tokens)
+                total = part if total is None else total + part
+        if total is None:
+            raise ValueError('step_ragged: no sentence')
+        self._backward_and_update(total)
+        return {'total_loss': float(total.detach())}

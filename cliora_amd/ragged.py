@@ -12,8 +12,13 @@ it the sentence's own without touching a level kernel (``cliora_chart_forward_ra
 sibling) of a cell of the triangle leaves the triangle iff its sibling does and its score adds inside_s[sibling], so -1e30 written
 into inside_s beyond each triangle after the inside pass zeroes those pairs' softmax weights, and each sentence's root cell
 (n - 1, 0) receives the seed rows after its level.  ``forward_ragged`` runs both passes that way, for text-only and CLIORA nets;
-``evaluate.evaluate_ragged`` and ``phrases.embed_phrases_ragged`` are built on it.  Inference only: nothing here may be trained
-through.
+``evaluate.evaluate_ragged`` and ``phrases.embed_phrases_ragged`` are built on it.  Those entries are inference only.
+
+TRAINING text-only DIORA through the same padded chart: ``forward_ragged_train`` runs each pack as one
+autograd node (``diora.RaggedChartFunction``: cliora_chart_forward_ragged_train / cliora_chart_backward_ragged -- the cotangents are
+masked to each triangle and each sentence's root cell is cut out of the outside backward, so the unchanged backward chains compute
+each sentence's own gradient), ``reconstruction_loss_ragged`` is the reconstruction loss over the valid tokens, and
+``harness.Trainer.step_ragged`` one optimizer step over all packs.
 
     from cliora_amd.ragged import parse_ragged, encode_ragged, forward_ragged
     trees = parse_ragged(net, sentences)        # net: harness.Net; sentences: lists of token ids, any lengths 1..64
@@ -21,6 +26,7 @@ through.
     vecs = encode_ragged(net, sentences)        # (N, D) inside vectors of the sentences' roots, on the device
     trees = parse_ragged(vl_net, sentences, obj_feats=feats)     # a CLIORA net: region features (N, R, img_dim), one row per sentence
     forward_ragged(net, sentences, per_pack=lambda idx, lens, diora: ...)    # both passes; diora holds the pack's padded charts
+    for idx, lens, diora in forward_ragged_train(net, sentences): ...        # the same, one pack at a time, with autograd live
 """
 import ctypes as C
 
@@ -254,6 +260,69 @@ def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, 
 
     _run_packs(net, sentences, max_batch, max_waste, pad_id, each, obj_feats=obj_feats, outside=True)
     return packs
+
+
+def forward_ragged_train(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
+    """forward_ragged with autograd live, text-only DIORA, sentences of any lengths in 1..64: a generator that packs them (``pack``)
+    and, one pack at a time, pads, embeds and runs the pack as one right-padded chart through ``diora.RaggedChartFunction``, then
+    yields ``(indices, lengths, diora)`` -- `indices` the pack's positions in `sentences`, `lengths` their int32 lengths on the device,
+    `diora` the chart module holding the pack's charts in the autograd graph: valid on each sentence's own triangle; cells beyond it
+    are unspecified and their cotangents are ignored.  The status word is read after each forward (one synchronisation per pack) and
+    a rejected length raises.  The structured losses of the module (bracket_nll, tree_objective, ...) read each sentence's own
+    triangle.  Gradients must be enabled; the net's mode is the caller's."""
+    from .diora import DioraMLP as TextDiora
+    diora = net.diora
+    if type(diora).vision_language or not isinstance(diora, TextDiora):
+        raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP), got %s'
+                                  % type(diora).__name__)
+    if not torch.is_grad_enabled():
+        raise _lib.ChartLibError('forward_ragged_train needs gradients enabled; forward_ragged runs the same batch for inference')
+    lengths = [len(s) for s in sentences]
+    if not lengths:
+        return
+    if min(lengths) < 1:
+        raise ValueError('an empty sentence has no chart')
+    if max(lengths) > MAX_L:             # before any pack has run
+        raise _lib.ChartLibError('L > %d is not supported by the padded training chart (got a sentence of %d words)' % (MAX_L, max(lengths)))
+    dev = next(net.parameters()).device
+    for idx in pack(lengths, max_batch, max_waste):
+        tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
+        x_span, x_word = net.embed(tokens.to(dev))
+        lens = lens.to(dev)
+        diora.__dict__['_ragged_train'] = (lens, root_level_mask(lengths[i] for i in idx))
+        try:
+            diora(x_span, x_word)
+        finally:
+            diora.__dict__['_ragged_train'] = None
+        bad = int(diora._ragged_status.item())
+        if bad:
+            raise _lib.ChartLibError('cliora_chart_forward_ragged_train rejected %d sentence length(s)' % bad)
+        yield idx, lens, diora
+
+
+class _LeafRows(object):
+    """What a reconstruction loss reads of a chart module (outside_h), holding the valid leaf rows as sentences of one word."""
+    __slots__ = ('outside_h',)
+
+    def __init__(self, outside_h):
+        self.outside_h = outside_h
+
+
+def reconstruction_loss_ragged(net, pack_sentences, neg_samples, diora=None):
+    """The reconstruction loss (harness.ReconstructionSoftmaxLoss) of a padded chart over its VALID tokens: the leaf rows
+    outside_h[b, :n_b] and their tokens are gathered and presented to the loss as N_valid sentences of one word, so the mean is over
+    the sum of the lengths and no padded position contributes.  pack_sentences: the token lists of the chart's sentences, in its
+    order.  -> a 0-d tensor in the graph."""
+    diora = net.diora if diora is None else diora
+    oh = diora.chart.outside_h
+    lens = [len(s) for s in pack_sentences]
+    if len(lens) != oh.shape[0]:
+        raise ValueError('pack_sentences holds %d sentences, the chart %d' % (len(lens), oh.shape[0]))
+    rows = torch.from_numpy(np.repeat(np.arange(len(lens), dtype=np.int64), lens)).to(oh.device)
+    pos = torch.from_numpy(np.concatenate([np.arange(n, dtype=np.int64) for n in lens])).to(oh.device)
+    tokens = torch.from_numpy(np.concatenate([np.asarray(s, dtype=np.int64) for s in pack_sentences])).to(oh.device)
+    cells = oh[rows, pos].unsqueeze(1)                   # (N_valid, 1, D): the leaf cell of a one-word chart is its cell 0
+    return net.reconstruct_softmax_loss(tokens.view(-1, 1), neg_samples, _LeafRows(cells))
 
 
 def decode_entry(decode):

@@ -87,6 +87,8 @@ def bracket_grad(diora, brackets, weights=None, lengths=None):
     nws, B = len(parts), plan.B
     dev = parts[0][0].device
     M = _check_brackets(brackets, B * nws)
+    if lengths is None:
+        lengths = getattr(diora._wss, 'lengths', None)         # a padded training chart of mixed lengths: each sentence's own triangle
     if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
         raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
     if weights is not None and weights.numel() != B * nws:
@@ -252,6 +254,8 @@ def tree_expectation(diora, cost=None, w_cost=None, w_entropy=None, lengths=None
     plan, parts = diora._plan, workspace_slices(diora)
     nws, B = len(parts), plan.B
     dev = parts[0][0].device
+    if lengths is None:
+        lengths = getattr(diora._wss, 'lengths', None)         # a padded training chart of mixed lengths: each sentence's own triangle
     if cost is not None and (cost.dim() != 2 or tuple(cost.shape) != (B * nws, plan.C)):
         raise ValueError('cost must be (%d, %d): one value per cell of the chart' % (B * nws, plan.C))
     if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):

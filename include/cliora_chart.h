@@ -520,6 +520,33 @@ int cliora_chart_forward_ragged(cliora_plan* plan, const cliora_params* params, 
                                 float* inside_c, void* fwd_workspace, size_t fwd_workspace_bytes, int run_outside,
                                 const int32_t* lengths, uint64_t root_levels, int32_t* status, void* stream);
 
+/* TRAINING through such a padded chart, text-only DIORA.  cliora_chart_forward_ragged_train: the call above,
+ * same schedule, same status word, same charts, with the state the backward needs written -- run_outside WITHOUT
+ * CLIORA_FWD_NO_BACKWARD.  cliora_chart_backward_ragged: the arguments of cliora_chart_backward_split (d_split_s may be NULL), plus
+ * lengths and root_levels as the forward got them and four caller-allocated buffers m_* of the shapes of the four cotangents
+ * ((B,C,D), (B,C), (B,C,D), (B,C); one may be NULL where its cotangent is).  The cotangents of cells beyond a sentence's triangle are
+ * ignored, whatever they hold: the call first writes their masked copies into m_* and the chains read those.  Every invalid pair
+ * carries a softmax weight of exactly 0 from the forward, and each sentence's root cell (lengths[b] - 1, 0) is cut out of the outside
+ * backward of its level -- what accumulates in its vH goes to d root_h through the unit-norm backward -- so the unchanged chains of
+ * cliora_chart_backward compute, for every parameter and for d_x_span[b, :lengths[b]], the sum over the sentences of the gradients
+ * cliora_chart_backward computes for each alone at its exact length, to rounding; d_x_span[b, lengths[b]:] is exactly 0; d_split_s
+ * must be zero beyond each triangle (cliora_bracket_grad and cliora_tree_expectation with `lengths` write it so).  The backward never
+ * runs on the sentence-resident kernels; with every length equal to L its results are bitwise those of cliora_chart_backward_split on
+ * the launch path.  Both are refused with CLIORA_EINVAL and a message of their own, before any launch, for: TreeLSTM plans, CLIORA
+ * plans (R > 0), L > 64, CLIORA_FWD_PAIR_STATES, params->root_mat (compress), a drop_mask; the forward also for
+ * CLIORA_FWD_NO_BACKWARD (that is cliora_chart_forward_ragged). */
+int cliora_chart_forward_ragged_train(cliora_plan* plan, const cliora_params* params, const float* x_span, const float* obj_span,
+                                      const float* drop_mask, float* inside_h, float* inside_s, float* outside_h, float* outside_s,
+                                      float* inside_c, void* fwd_workspace, size_t fwd_workspace_bytes, int run_outside,
+                                      const int32_t* lengths, uint64_t root_levels, int32_t* status, void* stream);
+int cliora_chart_backward_ragged(cliora_plan* plan, const cliora_params* params, const float* x_span, const float* obj_span,
+                                 const float* drop_mask, const float* inside_h, const float* inside_s, const float* outside_h,
+                                 const float* outside_s, const float* d_inside_h, const float* d_inside_s, const float* d_outside_h,
+                                 const float* d_outside_s, const float* d_split_s, void* fwd_workspace, size_t fwd_workspace_bytes,
+                                 void* bwd_workspace, size_t bwd_workspace_bytes, float* d_x_span, float* d_obj_span,
+                                 const cliora_params* grads, int ran_outside, const int32_t* lengths, uint64_t root_levels,
+                                 float* m_inside_h, float* m_inside_s, float* m_outside_h, float* m_outside_s, void* stream);
+
 /* Grounding evaluation (cliora/scripts/parse.py:176-264, the host loop over every phrase and predicted span): ONE launch for a batch,
  * one workgroup per sentence.  All pointers are device memory.
  *   atten (B, L, R) fp32 at element strides (sb, sl, sr) -- DioraMLP.atten_score, a permuted diagonal of vg_atten_score, read in
