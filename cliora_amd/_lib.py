@@ -54,6 +54,8 @@ ABI = {
     'cliora_chart_forward_ragged': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
     'cliora_chart_forward_ragged_train': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
     'cliora_chart_backward_ragged': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp, u64] + [vp] * 4 + [vp]),
+    'cliora_chart_forward_ragged_train_vl': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
+    'cliora_chart_backward_ragged_vl': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp, u64] + [vp] * 4 + [vp]),
     'cliora_lstm_forward': (i32, [vp, pp] + [vp] * 7 + [vp, sz, i32, vp]),
     'cliora_lstm_backward': (i32, [vp, pp] + [vp] * 13 + [vp, sz, vp, sz, vp, pp, i32, vp]),
     'cliora_inside_pair_states': (i32, [vp, vp, i32, pvp, pvp, psz, psz]),
@@ -65,6 +67,7 @@ ABI = {
     'cliora_vl_scores_max_backward': (i32, [vp] * 4 + [vp, vp, vp, vp, vp, sz, vp]),
     'cliora_contrastive_workspace_bytes': (sz, [i32, i32]),
     'cliora_contrastive_loss': (i32, [i32, i32, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, sz, vp]),
+    'cliora_contrastive_loss_ragged': (i32, [i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, sz, vp]),
     'cliora_proj_workspace_bytes': (sz, [i32, i32, i32]),
     'cliora_proj_forward': (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
     'cliora_proj_backward': (i32, [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
@@ -75,6 +78,7 @@ ABI = {
     'cliora_rows_scatter_add_segments': (i32, [pvp, pvp, C.POINTER(i32), i32, i32, vp, i64, vp]),
     'cliora_vg_workspace_bytes': (sz, [i32, i32]),
     'cliora_vg_loss': (i32, [i32, i32, i32, vp, f32, vp, vp, vp, sz, vp]),
+    'cliora_vg_loss_ragged': (i32, [i32, i32, i32, vp, vp, f32, vp, vp, vp, sz, vp]),
     'cliora_clip_adam_workspace_bytes': (sz, []),
     'cliora_clip_adam': (i32, [vp, vp, vp, vp, sz, f32, f32, f32, f32, f32, i32, vp, sz, vp]),
     'cliora_cky_decode': (i32, [vp, vp, vp, vp]),

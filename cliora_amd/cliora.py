@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import ptr, stream
-from .diora import DioraBase, ComposeMLP, Bilinear, ChartFunction, _cont
+from .diora import DioraBase, ComposeMLP, Bilinear, ChartFunction, RaggedChartFunction, _cont
 
 DROPOUT_P = 0.1   # AttentionHead: nn.Dropout(0.1), cliora.py:32
 
@@ -268,13 +268,22 @@ class DioraMLP(DioraBase):
             raise ValueError('the CLIORA module needs obj_embed_span (use cliora_amd.diora.DioraMLP for text only)')
         return obj_embed_span.shape[1]
 
+    def _drop_mask(self, plan, dev):
+        if not self.training:
+            return None
+        mask = self.dropout_mask
+        if mask is None:   # same distribution as nn.Dropout(0.1) on the (.., R) probabilities
+            mask = F.dropout(torch.ones((plan.B, plan.C, plan.R), device=dev), DROPOUT_P, True)
+        return mask
+
     def _run_chart(self, plan, holder, flags, x_span, obj_embed_span, params):
-        mask = None
-        if self.training:
-            mask = self.dropout_mask
-            if mask is None:   # same distribution as nn.Dropout(0.1) on the (.., R) probabilities
-                mask = F.dropout(torch.ones((plan.B, plan.C, plan.R), device=x_span.device), DROPOUT_P, True)
-        return ChartFunction.apply(plan, holder, flags, x_span, obj_embed_span, mask, *params) + (None,)
+        return ChartFunction.apply(plan, holder, flags, x_span, obj_embed_span, self._drop_mask(plan, x_span.device), *params) + (None,)
+
+    def _run_ragged_train(self, plan, holder, x_span, obj_embed_span, params, ragged):
+        """A padded chart of mixed lengths with a backward: the mask's rows are those of the PADDED chart."""
+        *charts, self.__dict__['_ragged_status'], inside_c = RaggedChartFunction.apply(
+            plan, holder, int(bool(self.outside)), *ragged, x_span, obj_embed_span, self._drop_mask(plan, x_span.device), *params)
+        return (*charts, inside_c, None)
 
     def forward(self, x_span, x_word, obj_embed_span=None, obj_embed_word=None):
         super().forward(x_span, x_word, obj_embed_span, obj_embed_word)
@@ -284,7 +293,8 @@ class DioraMLP(DioraBase):
         # cliora.py:453-468
         if self.training and self.lazy_region_scores:
             # training: vg_atten does not read all_atten (cliora.py:459-461) and the contrastive loss only wants its region max
-            lane = self.word_lane if x_span.is_cuda else None
+            # (a padded chart of mixed lengths, _ragged_train: everything on the current stream)
+            lane = self.word_lane if x_span.is_cuda and self.__dict__.get('_ragged_train') is None else None
             if lane is not None:
                 # the word-region scorer on the caller lane: neither its forward nor its backward (0.2 ms at c3) is on the chart's path; the
                 # chart rows and the span region matrix are not read by it (detached: no gradient edge into the chart either)

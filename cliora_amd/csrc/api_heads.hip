@@ -33,23 +33,36 @@ static size_t tn_rect_slab_floats(int nrows, int Mi, int Nj) {
 extern "C" size_t cliora_vg_workspace_bytes(int B, int L) {
     return (al64((size_t)B * B) * 2 + al64((size_t)B) + al64((size_t)B * B * L)) * sizeof(float);
 }
-extern "C" int cliora_vg_loss(int B, int L, int R, const float* vg_atten, float alpha, float* loss, float* d_vg_atten, void* ws, size_t ws_bytes, void* stream) {
-    if (!vg_atten || !loss || !ws || B < 1 || L < 1 || R < 1) return fail(CLIORA_EINVAL, "bad argument");
-    if (ws_bytes < cliora_vg_workspace_bytes(B, L)) return fail(CLIORA_ENOMEM, "workspace too small");
+// lengths == NULL: cliora_vg_loss.  Else cliora_vg_loss_ragged, whose workspace starts with the status word (VG_STATUS_BYTES).
+constexpr size_t VG_STATUS_BYTES = 256;
+static int vg_loss_run(const char* who, int B, int L, int R, const float* vg_atten, const int32_t* lengths, float alpha, float* loss,
+                       float* d_vg_atten, void* ws, size_t ws_bytes, void* stream) {
+    const std::string w = std::string(who) + ": ";
+    if (!vg_atten || !loss || !ws || B < 1 || L < 1 || R < 1) return fail(CLIORA_EINVAL, lengths ? w + "bad argument" : "bad argument");
+    if (ws_bytes < cliora_vg_workspace_bytes(B, L) + (lengths ? VG_STATUS_BYTES : 0)) return fail(CLIORA_ENOMEM, lengths ? w + "workspace too small" : "workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    float* w = (float*)ws;
-    float* logits = w; float* dlog = w + al64((size_t)B * B); float* row_loss = dlog + al64((size_t)B * B);
+    int32_t* status = lengths ? (int32_t*)ws : nullptr;
+    float* w0 = (float*)((char*)ws + (lengths ? VG_STATUS_BYTES : 0));
+    float* logits = w0; float* dlog = w0 + al64((size_t)B * B); float* row_loss = dlog + al64((size_t)B * B);
     int32_t* arg = reinterpret_cast<int32_t*>(row_loss + al64((size_t)B));
-    hipLaunchKernelGGL(vg_logits_fwd, dim3((B * B + 3) / 4), dim3(256), 0, st, B, L, R, vg_atten, logits, arg);
+    hipLaunchKernelGGL(vg_logits_fwd, dim3((B * B + 3) / 4), dim3(256), 0, st, B, L, R, vg_atten, logits, arg, lengths);
     LAUNCHOK("vg_logits_fwd");
-    hipLaunchKernelGGL(vg_ce, dim3(1), dim3(1024), 0, st, B, alpha, logits, row_loss, dlog, loss);
+    hipLaunchKernelGGL(vg_ce, dim3(1), dim3(1024), 0, st, B, alpha, logits, row_loss, dlog, loss, lengths, L, status);
     LAUNCHOK("vg_ce");
     if (d_vg_atten) {
         const size_t n = (size_t)B * B * L * R;
-        hipLaunchKernelGGL(vg_scatter_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, L, R, dlog, arg, d_vg_atten);
+        hipLaunchKernelGGL(vg_scatter_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, B, L, R, dlog, arg, d_vg_atten, lengths);
         LAUNCHOK("vg_scatter_bwd");
     }
     return CLIORA_OK;
+}
+extern "C" int cliora_vg_loss(int B, int L, int R, const float* vg_atten, float alpha, float* loss, float* d_vg_atten, void* ws, size_t ws_bytes, void* stream) {
+    return vg_loss_run("cliora_vg_loss", B, L, R, vg_atten, nullptr, alpha, loss, d_vg_atten, ws, ws_bytes, stream);
+}
+extern "C" int cliora_vg_loss_ragged(int B, int L, int R, const float* vg_atten, const int32_t* lengths, float alpha, float* loss,
+                                     float* d_vg_atten, void* ws, size_t ws_bytes, void* stream) {
+    if (!lengths) return fail(CLIORA_EINVAL, "cliora_vg_loss_ragged: NULL lengths");
+    return vg_loss_run("cliora_vg_loss_ragged", B, L, R, vg_atten, lengths, alpha, loss, d_vg_atten, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------ y = gather(x, index) W^T + bias

@@ -1,5 +1,6 @@
 // C ABI, ragged unit: the forward (both passes) of mixed-length sentences that share one right-padded chart, for inference
-// (cliora_chart_forward_ragged) and for training (cliora_chart_forward_ragged_train, cliora_chart_backward_ragged).  See
+// (cliora_chart_forward_ragged) and for training (cliora_chart_forward_ragged_train, cliora_chart_backward_ragged; their _vl forms for
+// CLIORA plans).  See
 // include/cliora_chart.h for the contract and ragged_kernels.hpp for why the padded chart serves; the decode is in api_decode.hip.
 #include "api_common.hpp"
 
@@ -34,6 +35,18 @@ static int ragged_train_refusals(const char* who, const cliora_plan* plan, const
     return CLIORA_OK;
 }
 
+// The _vl pair (CLIORA plans): the same, with the region matrix required instead of refused.
+static int ragged_train_vl_refusals(const char* who, const cliora_plan* plan, const cliora_params* P, const float* obj_span, int flags) {
+    const std::string w = std::string(who) + ": ";
+    if (plan->p.arch != 0) return fail(CLIORA_EINVAL, w + "TreeLSTM plans are not supported");
+    if (plan->p.R <= 0) return fail(CLIORA_EINVAL, w + "text-only plans (R = 0) are not supported (they train through the entry without _vl)");
+    if (!obj_span) return fail(CLIORA_EINVAL, w + "a CLIORA plan (R > 0) needs obj_span");
+    if (plan->p.is_long()) return fail(CLIORA_EINVAL, w + "L > 64 is not supported (the backward and the root-level mask stop at 64 words)");
+    if (flags & CLIORA_FWD_PAIR_STATES) return fail(CLIORA_EINVAL, w + "CLIORA_FWD_PAIR_STATES is not supported");
+    if (P && P->root_mat) return fail(CLIORA_EINVAL, w + "compress (root_mat) is not supported");
+    return CLIORA_OK;
+}
+
 extern "C" int cliora_chart_forward_ragged_train(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
                                                  const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
                                                  float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
@@ -65,4 +78,36 @@ extern "C" int cliora_chart_backward_ragged(cliora_plan* plan, const cliora_para
                                      rg.cot[0] ? rg.masked[0] : nullptr, rg.cot[1] ? rg.masked[1] : nullptr, rg.cot[2] ? rg.masked[2] : nullptr,
                                      rg.cot[3] ? rg.masked[3] : nullptr, d_split_s, fwd_ws, fwd_ws_bytes, bwd_ws, bwd_ws_bytes, d_x_span,
                                      nullptr, G, ran_outside & 1, stream, &rg);
+}
+
+extern "C" int cliora_chart_forward_ragged_train_vl(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                                                    const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
+                                                    float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
+                                                    const int32_t* lengths, uint64_t root_levels, int32_t* status, void* stream) {
+    if (!plan || !P || !lengths || !status) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_train_vl: NULL argument");
+    OKR(ragged_train_vl_refusals("cliora_chart_forward_ragged_train_vl", plan, P, obj_span, run_outside));
+    if (run_outside & CLIORA_FWD_NO_BACKWARD)
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_train_vl: writes the backward's state, CLIORA_FWD_NO_BACKWARD is cliora_chart_forward_ragged's");
+    HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), (hipStream_t)stream));
+    const RaggedFwd rg{lengths, root_levels, status};
+    return cliora_chart_forward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws,
+                                    fwd_ws_bytes, run_outside, stream, &rg);
+}
+
+extern "C" int cliora_chart_backward_ragged_vl(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                                               const float* drop_mask, const float* inside_h, const float* inside_s, const float* outside_h,
+                                               const float* outside_s, const float* d_inside_h, const float* d_inside_s,
+                                               const float* d_outside_h, const float* d_outside_s, const float* d_split_s, void* fwd_ws,
+                                               size_t fwd_ws_bytes, void* bwd_ws, size_t bwd_ws_bytes, float* d_x_span, float* d_obj_span,
+                                               const cliora_params* G, int ran_outside, const int32_t* lengths, uint64_t root_levels,
+                                               float* m_inside_h, float* m_inside_s, float* m_outside_h, float* m_outside_s, void* stream) {
+    if (!plan || !lengths) return fail(CLIORA_EINVAL, "cliora_chart_backward_ragged_vl: NULL argument");
+    OKR(ragged_train_vl_refusals("cliora_chart_backward_ragged_vl", plan, P, obj_span, ran_outside));
+    RaggedBwd rg{lengths, root_levels, {d_inside_h, d_inside_s, d_outside_h, d_outside_s}, {m_inside_h, m_inside_s, m_outside_h, m_outside_s}};
+    for (int k = 0; k < 4; ++k)
+        if (rg.cot[k] && !rg.masked[k]) return fail(CLIORA_EINVAL, "cliora_chart_backward_ragged_vl: a cotangent is given without the buffer for its masked copy");
+    return cliora_chart_backward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s,
+                                     rg.cot[0] ? rg.masked[0] : nullptr, rg.cot[1] ? rg.masked[1] : nullptr, rg.cot[2] ? rg.masked[2] : nullptr,
+                                     rg.cot[3] ? rg.masked[3] : nullptr, d_split_s, fwd_ws, fwd_ws_bytes, bwd_ws, bwd_ws_bytes, d_x_span,
+                                     d_obj_span, G, ran_outside & 1, stream, &rg);
 }

@@ -245,7 +245,40 @@ extern "C" int cliora_contrastive_loss(int B, int C, const float* all_max, const
                            d_all_max, d_inside_s, d_outside_s);
         LAUNCHOK("contrastive_spans");
     }
-    hipLaunchKernelGGL(contrastive_finish, dim3(1), dim3(256), 0, st, B, C, nb, part, last, k, loss, d_inside_s);
+    hipLaunchKernelGGL(contrastive_finish, dim3(1), dim3(256), 0, st, B, C, nb, part, last, k, loss, d_inside_s, (const int32_t*)nullptr, 0,
+                       (int32_t*)nullptr);
+    LAUNCHOK("contrastive_finish");
+    return CLIORA_OK;
+}
+
+// The same loss over right-padded sentences of mixed lengths: every cell of the padded chart gets a workgroup, so the partial sums are
+// C of them (cliora_contrastive_workspace_bytes(B, 2 C)) behind the status word.
+constexpr size_t CONTRASTIVE_STATUS_BYTES = 256;
+extern "C" int cliora_contrastive_loss_ragged(int B, int C, const float* all_max, const float* inside_s, const float* outside_s,
+                                              const int32_t* lengths, float margin, float alpha, float* loss, float* d_all_max,
+                                              float* d_inside_s, float* d_outside_s, void* ws, size_t ws_bytes, void* stream) {
+    if (!all_max || !inside_s || !outside_s || !lengths || !loss || !d_all_max || !d_inside_s || !d_outside_s || !ws)
+        return fail(CLIORA_EINVAL, "cliora_contrastive_loss_ragged: NULL argument");
+    if (B < 1 || B > 128 || C < 1) return fail(CLIORA_EINVAL, "cliora_contrastive_loss_ragged: 1 <= B <= 128");
+    int L = 1;
+    while (L * (L + 1) / 2 < C) ++L;
+    if (L * (L + 1) / 2 != C) return fail(CLIORA_EINVAL, "cliora_contrastive_loss_ragged: C is not L (L + 1) / 2 of a padded chart");
+    if (ws_bytes < CONTRASTIVE_STATUS_BYTES + cliora_contrastive_workspace_bytes(B, 2 * C))
+        return fail(CLIORA_ENOMEM, "cliora_contrastive_loss_ragged: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* status = (int32_t*)ws;
+    float* part = (float*)((char*)ws + CONTRASTIVE_STATUS_BYTES);
+    float* last = part + ((C + 63) / 64) * 64;
+    HIPOK(hipMemsetAsync(d_all_max, 0, (size_t)B * B * C * sizeof(float), st));
+    HIPOK(hipMemsetAsync(d_inside_s, 0, (size_t)B * C * sizeof(float), st));
+    HIPOK(hipMemsetAsync(d_outside_s, 0, (size_t)B * C * sizeof(float), st));
+    const float k = alpha / (float)B;
+    const size_t lds = ((size_t)B * (B + 1) + 4 * B + 256 + B) * sizeof(float);
+    OKR(cliora_ensure_max_lds((const void*)contrastive_spans_ragged));
+    hipLaunchKernelGGL(contrastive_spans_ragged, dim3(C), dim3(256), lds, st, B, L, C, all_max, inside_s, outside_s, lengths, margin, k, part,
+                       last, d_all_max, d_inside_s, d_outside_s);
+    LAUNCHOK("contrastive_spans_ragged");
+    hipLaunchKernelGGL(contrastive_finish, dim3(1), dim3(256), 0, st, B, C, C, part, last, k, loss, d_inside_s, lengths, L, status);
     LAUNCHOK("contrastive_finish");
     return CLIORA_OK;
 }

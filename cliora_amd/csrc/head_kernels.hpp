@@ -75,15 +75,26 @@ struct StoreAxpyRowsE {
 // ---------------------------------------------------------------------------------------------------------------------------
 // VGLoss (trainer.py:139-171).  One wave per (sentence a, image c): logits[a][c] = sum_l max_r vg[a][c][l][r] / L and the region
 // that attains each maximum (smallest index on ties, as torch.max on the CPU).
+// lengths != NULL (cliora_vg_loss_ragged: right-padded sentences of mixed lengths): sentence a has n_a words,
+// the sum and its divisor stop there, and the words l >= n_a -- never read -- get the region -1, which no region equals, so their
+// gradient is an exact zero.  A length outside [1, L] counts as no word at all (vg_ce counts it and drops the sentence's row).  The
+// words are added in the same order: with every n_a = L the same bits.
 // ---------------------------------------------------------------------------------------------------------------------------
+__device__ inline int vg_words(const int32_t* __restrict__ lengths, int a, int L) {
+    if (!lengths) return L;
+    const int n = lengths[a];
+    return n >= 1 && n <= L ? n : 0;
+}
 static __global__ __launch_bounds__(256) void vg_logits_fwd(int B, int L, int R, const float* __restrict__ vg, float* __restrict__ logits,
-                                                            int32_t* __restrict__ arg) {
+                                                            int32_t* __restrict__ arg, const int32_t* __restrict__ lengths) {
     const int lane = threadIdx.x & 63;
     const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pair >= B * B) return;
     const float* src = vg + (size_t)pair * L * R;
+    const int n = vg_words(lengths, pair / B, L);
     float sum = 0.f;
-    for (int l = 0; l < L; ++l) {
+    for (int l = n + lane; l < L; l += 64) arg[(size_t)pair * L + l] = -1;
+    for (int l = 0; l < n; ++l) {
         float best = -INFINITY; int bi = 0x7fffffff;
         for (int r = lane; r < R; r += 64) { const float v = src[l * R + r]; if (v > best) { best = v; bi = r; } }
 #pragma unroll
@@ -94,15 +105,23 @@ static __global__ __launch_bounds__(256) void vg_logits_fwd(int B, int L, int R,
         sum += best;
         if (lane == 0) arg[(size_t)pair * L + l] = bi;
     }
-    if (lane == 0) logits[pair] = sum / (float)L;
+    if (lane == 0) logits[pair] = n ? sum / (float)n : 0.f;
 }
 // One workgroup: cross entropy of the (B, B) logits against the diagonal; row a on wave a % 16 (sixteen waves: a row is three dependent
 // passes with a wave reduction each, 20 us on four waves at B 64).  d_logits for an upstream cotangent of 1; the per-row losses are
 // added in row order by one lane.
+// lengths != NULL: a sentence whose length is outside [1, L] has no row -- its loss term and its d_logits row are zero -- and is
+// counted in status[0]; its image still stands as a negative in the other rows.
 static __global__ __launch_bounds__(1024) void vg_ce(int B, float alpha, const float* __restrict__ logits, float* __restrict__ row_loss,
-                                                     float* __restrict__ d_logits, float* __restrict__ loss) {
+                                                     float* __restrict__ d_logits, float* __restrict__ loss,
+                                                     const int32_t* __restrict__ lengths, int L, int32_t* __restrict__ status) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
     for (int a = wave; a < B; a += nwave) {
+        if (lengths && !vg_words(lengths, a, L)) {
+            for (int c = lane; c < B; c += 64) d_logits[a * B + c] = 0.f;
+            if (lane == 0) row_loss[a] = 0.f;
+            continue;
+        }
         float m = -INFINITY;
         for (int c = lane; c < B; c += 64) m = fmaxf(m, logits[a * B + c]);
         m = wave_max(m);
@@ -118,16 +137,23 @@ static __global__ __launch_bounds__(1024) void vg_ce(int B, float alpha, const f
         float t = 0.f;
         for (int a = 0; a < B; ++a) t += row_loss[a];
         loss[0] = alpha * t / (float)B;
+        if (lengths) {
+            int bad = 0;
+            for (int a = 0; a < B; ++a) bad += vg_words(lengths, a, L) ? 0 : 1;
+            status[0] = bad;
+        }
     }
 }
-static __global__ __launch_bounds__(256) void vg_scatter_bwd(size_t n, int L, int R, const float* __restrict__ d_logits, const int32_t* __restrict__ arg,
-                                                             float* __restrict__ d_vg) {
+// (lengths != NULL: the divisor is the sentence's n_a; the words beyond it carry the region -1 and get an exact zero, selected)
+static __global__ __launch_bounds__(256) void vg_scatter_bwd(size_t n, int B, int L, int R, const float* __restrict__ d_logits, const int32_t* __restrict__ arg,
+                                                             float* __restrict__ d_vg, const int32_t* __restrict__ lengths) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= n) return;
     const size_t pl = e / R;                  // (pair, l)
     const int r = (int)(e - pl * R);
     const size_t pair = pl / L;
-    d_vg[e] = (arg[pl] == r) ? d_logits[pair] / (float)L : 0.f;
+    const int na = vg_words(lengths, (int)(pair / B), L);
+    d_vg[e] = (arg[pl] == r) ? d_logits[pair] / (float)na : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -532,12 +532,122 @@ static __global__ __launch_bounds__(256) void contrastive_spans(int B, int Cq, c
     }
     if (tid == 0) part[b] = red[0];
 }
+// The same loss over right-padded sentences of mixed lengths (cliora_contrastive_loss_ragged), one workgroup per
+// cell of the PADDED chart of length L (Cq = L (L + 1) / 2), cell = (level, pos).  Sentence x of n_x words owns the cell iff
+// pos + level < n_x; the cell is then number level n_x - level (level - 1) / 2 + pos of x's own chart of C_x = n_x (n_x + 1) / 2 cells, and
+// enters x's loss iff that number is below C_x / 2 (trainer.py:126 at the sentence's own length).  For such an x:
+//   txt = sum_{y != x} hinge(s[x][y] - s[x][x]) / B  (every image);  img = sum_{a != x, a owns the cell} hinge(s[a][x] - s[x][x]) / B
+//   marg[x] = exp(in_s[x][cell] + out_s[x][cell] - in_s[x][root(x)]),  root(x) = the first cell of level n_x - 1
+// Everything is SELECTED by ownership, never multiplied by a mask: what the inputs hold beyond a triangle, NaN included, is not
+// read into any sum, and the gradients there stay the exact zeros of the entry's memset.  A length outside [1, L] owns no cell
+// (contrastive_finish counts it); its image still stands as a negative for the other texts.  The sums run in the order of
+// contrastive_spans: with every n_x = L, part / last / the gradients of the cells b < C / 2 are its bits and the other cells add zeros.
+struct CellOf { int level, pos; };
+__device__ inline CellOf cell_of(int cell, int L) {
+    int level = 0, off = 0;
+    while (cell >= off + (L - level)) { off += L - level; ++level; }
+    return CellOf{level, cell - off};
+}
+__device__ inline int ragged_len(const int32_t* __restrict__ lengths, int x, int L) {
+    const int n = lengths[x];
+    return n >= 1 && n <= L ? n : 0;
+}
+static __global__ __launch_bounds__(256) void contrastive_spans_ragged(int B, int L, int Cq, const float* __restrict__ M, const float* __restrict__ IS,
+                                                                       const float* __restrict__ OS, const int32_t* __restrict__ lengths,
+                                                                       float margin, float k, float* __restrict__ part, float* __restrict__ last,
+                                                                       float* __restrict__ dM, float* __restrict__ dIS, float* __restrict__ dOS) {
+    extern __shared__ float sm[];
+    float* S = sm;                       // [B][B+1]: s[a][c] of this cell, rows of the sentences that own it (others: never read)
+    float* diag = S + B * (B + 1);       // [B]
+    float* marg = diag + B;              // [B]
+    float* vl = marg + B;                // [B]
+    float* dd = vl + B;                  // [B]
+    float* red = dd + B;                 // [256]
+    int* own = reinterpret_cast<int*>(red + 256);      // [B] 0: beyond the triangle, 1: owned, 2: owned and in the sentence's first half
+    const int b = blockIdx.x, tid = threadIdx.x, ld = B + 1;
+    const CellOf cl = cell_of(b, L);
+    if (tid < B) {
+        const int n = ragged_len(lengths, tid, L);
+        int o = 0;
+        if (cl.pos + cl.level < n) o = (cl.level * n - cl.level * (cl.level - 1) / 2 + cl.pos < (n * (n + 1) / 2) / 2) ? 2 : 1;
+        own[tid] = o;
+    }
+    __syncthreads();
+    for (int e = tid; e < B * B; e += 256) {
+        const int a = e / B, c = e - a * B;
+        S[a * ld + c] = own[a] ? M[((size_t)a * B + c) * Cq + b] : 0.f;
+    }
+    __syncthreads();
+    if (tid < B) {
+        float mg = 0.f;
+        if (own[tid] == 2) {
+            const int lv = ragged_len(lengths, tid, L) - 1;
+            mg = expf(IS[(size_t)tid * Cq + b] + OS[(size_t)tid * Cq + b] - IS[(size_t)tid * Cq + lv * L - lv * (lv - 1) / 2]);
+        }
+        diag[tid] = S[tid * ld + tid];
+        marg[tid] = mg;
+    }
+    __syncthreads();
+    const float invB = 1.f / (float)B;
+    if (tid < B) {
+        const int x = tid;
+        float lt = 0.f, li = 0.f, g = 0.f;
+        if (own[x] == 2) {
+            for (int j = 0; j < B; ++j) {
+                if (j == x) continue;
+                lt += fmaxf(margin + S[x * ld + j] - diag[x], CONTRASTIVE_FLOOR);
+                if (own[j]) li += fmaxf(margin + S[j * ld + x] - diag[x], CONTRASTIVE_FLOOR);
+            }
+            for (int j = 0; j < B; ++j) {
+                if (j == x) continue;
+                if (margin + S[x * ld + j] - diag[x] >= CONTRASTIVE_FLOOR) g -= k * marg[x] * invB;
+                if (own[j] && margin + S[j * ld + x] - diag[x] >= CONTRASTIVE_FLOOR) g -= k * marg[x] * invB;
+            }
+        }
+        vl[x] = (lt + li) * invB;
+        dd[x] = g;
+    }
+    __syncthreads();
+    for (int e = tid; e < B * B; e += 256) {
+        const int a = e / B, c = e - a * B;
+        if (!own[a]) continue;                       // (a, :, cell) is beyond a's triangle: the memset's zero stays
+        float g;
+        if (a == c) g = dd[a];
+        else {
+            const float s = S[a * ld + c];
+            g = (own[a] == 2 && margin + s - diag[a] >= CONTRASTIVE_FLOOR ? k * marg[a] * invB : 0.f) +
+                (own[c] == 2 && margin + s - diag[c] >= CONTRASTIVE_FLOOR ? k * marg[c] * invB : 0.f);
+        }
+        dM[((size_t)a * B + c) * Cq + b] = g;
+    }
+    float p = 0.f;
+    if (tid < B) {
+        float mv = 0.f;
+        if (own[tid] == 2) {
+            mv = marg[tid] * vl[tid];
+            dIS[(size_t)tid * Cq + b] = k * mv;
+            dOS[(size_t)tid * Cq + b] = k * mv;
+        }
+        p = mv;
+        last[(size_t)b * B + tid] = mv;
+    }
+    red[tid] = p;
+    __syncthreads();
+    for (int s2 = 128; s2 > 0; s2 >>= 1) {
+        if (tid < s2) red[tid] += red[tid + s2];
+        __syncthreads();
+    }
+    if (tid == 0) part[b] = red[0];
+}
 // loss = k sum_b part[b];  d in_s[x][C-1] = -k sum_b last[b][x]   (fixed order: the same bits as one lane adding b = 0, 1, ...)
+// lengths != NULL (the padded chart above, nb = Cq): the marginal's subtracted score and its gradient sit at the sentence's own root
+// cell, the first of level n_x - 1; a length outside [1, L] gets nothing and is counted in status[0].
 // 256 threads: wave 0 prefetches the partial losses (lane l holds part[l], part[l + 64], ...) and lane 0 adds them in b order out of LDS;
 // waves 1..3 take the columns x < B, four loads in flight (the round-5 form was one dependent global load per addend on a single lane: 29 us
 // at C = 210).
 static __global__ __launch_bounds__(256) void contrastive_finish(int B, int Cq, int nb, const float* __restrict__ part, const float* __restrict__ last, float k,
-                                                                 float* __restrict__ loss, float* __restrict__ dIS) {
+                                                                 float* __restrict__ loss, float* __restrict__ dIS,
+                                                                 const int32_t* __restrict__ lengths, int L, int32_t* __restrict__ status) {
     __shared__ float sp[1024];
     const int tid = threadIdx.x;
     if (tid < 64) {
@@ -550,10 +660,21 @@ static __global__ __launch_bounds__(256) void contrastive_finish(int B, int Cq, 
             for (int b = 0; b < nbc; ++b) s += sp[b];
             for (int b = nbc; b < nb; ++b) s += part[b];
             loss[0] = k * s;
+            if (lengths) {
+                int bad = 0;
+                for (int x = 0; x < B; ++x) bad += ragged_len(lengths, x, L) ? 0 : 1;
+                status[0] = bad;
+            }
         }
         return;
     }
     for (int x = tid - 64; x < B; x += 192) {
+        int root = Cq - 1;
+        if (lengths) {
+            const int lv = ragged_len(lengths, x, L) - 1;
+            if (lv < 0) continue;
+            root = lv * L - lv * (lv - 1) / 2;
+        }
         float s = 0.f;
         int b = 0;
         for (; b + 4 <= nb; b += 4) {
@@ -561,7 +682,7 @@ static __global__ __launch_bounds__(256) void contrastive_finish(int B, int Cq, 
             s += v0; s += v1; s += v2; s += v3;
         }
         for (; b < nb; ++b) s += last[(size_t)b * B + x];
-        dIS[(size_t)x * Cq + Cq - 1] -= k * s;
+        dIS[(size_t)x * Cq + root] -= k * s;
     }
 }
 

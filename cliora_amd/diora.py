@@ -145,44 +145,51 @@ def _check_lengths(plan, lengths, dev):
 
 
 class RaggedChartFunction(torch.autograd.Function):
-    """ChartFunction for a right-padded batch of mixed lengths, text-only.
+    """ChartFunction for a right-padded batch of mixed lengths (DESIGN.md sections 22 and 23).
 
     forward  -> cliora_chart_forward_ragged_train   (the padded chart's schedule with the backward's state written)
     backward -> cliora_chart_backward_ragged        (the split cotangent of a structured loss of the same forward included)
-    Inputs: plan, holder, run_outside, lengths (int32 device tensor (B,)), root_levels (the bit mask of {n - 1}), x_span, then the
-    parameter tensors in _lib.PARAM_FIELDS order.  Outputs: the four charts -- valid on each sentence's own triangle, unspecified
-    beyond it, where their cotangents are ignored -- and the status word (1,) int32 on the device, which the caller must read."""
+    With image regions (obj_span given, a plan of R > 0) the `_vl` forms of the two entries: the (B, C, R) dropout mask is taken and
+    d obj_span returned.
+    Inputs: plan, holder, run_outside, lengths (int32 device tensor (B,)), root_levels (the bit mask of {n - 1}), x_span, obj_span,
+    drop_mask (both None for text-only DIORA), then the parameter tensors in _lib.PARAM_FIELDS order.  Outputs: the four charts --
+    valid on each sentence's own triangle, unspecified beyond it, where their cotangents are ignored -- the status word (1,) int32
+    on the device, which the caller must read, and inside_c (None without regions)."""
 
     @staticmethod
-    def forward(ctx, plan, holder, run_outside, lengths, root_levels, x_span, *params):
+    def forward(ctx, plan, holder, run_outside, lengths, root_levels, x_span, obj_span, drop_mask, *params):
         if not x_span.is_cuda:
             raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-        D, run_outside, dev = plan.D, int(run_outside), x_span.device
+        D, run_outside, dev, vl = plan.D, int(run_outside), x_span.device, obj_span is not None
         _check_lengths(plan, lengths, dev)
-        x_span, lengths = x_span.contiguous().float(), lengths.contiguous()
+        x_span, lengths, obj_span, drop_mask = x_span.contiguous().float(), lengths.contiguous(), _cont(obj_span), _cont(drop_mask)
         ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
         with _lib.device_guard(x_span):
-            outs, ws, nbytes = chart_buffers(plan, dev, run_outside, D, 1, D, 1)
+            outs, ws, nbytes = chart_buffers(plan, dev, run_outside, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
+            inside_c = outs.pop().zero_() if vl else None
             status = torch.empty(1, device=dev, dtype=torch.int32)
             pst = _param_struct(ptens)
-            _lib.call('cliora_chart_forward_ragged_train', plan.handle, C.byref(pst), _ptr(x_span), None, None, *map(_ptr, outs), None,
-                      _ptr(ws), nbytes, run_outside, _ptr(lengths), int(root_levels), _ptr(status), _stream())
+            _lib.call('cliora_chart_forward_ragged_train' + ('_vl' if vl else ''), plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span),
+                      _ptr(drop_mask), *map(_ptr, outs), _ptr(inside_c), _ptr(ws), nbytes, run_outside, _ptr(lengths), int(root_levels),
+                      _ptr(status), _stream())
         ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.root_levels = plan, run_outside & 1, ws, ptens, int(root_levels)
+        ctx.drop_mask, ctx.vl = drop_mask, vl
         ctx.split_cot = getattr(holder, 'split_cot', None)
-        ctx.save_for_backward(x_span, lengths, *outs)
+        ctx.save_for_backward(x_span, lengths, *((obj_span,) if vl else ()), *outs)
         ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(status)
+        ctx.mark_non_differentiable(status, *((inside_c,) if vl else ()))
         holder.clear()
         holder.append(ws)
         holder.lengths = lengths
-        return (*outs, status)
+        return (*outs, status, inside_c)
 
     @staticmethod
-    def backward(ctx, d_ih, d_is, d_oh, d_os, _d_status):
+    def backward(ctx, d_ih, d_is, d_oh, d_os, _d_status, _d_ic):
         plan, saved = ctx.plan, ctx.saved_tensors
-        x_span, lengths = saved[0], saved[1]
+        x_span, lengths, obj_span = saved[0], saved[1], (saved[2] if ctx.vl else None)
         with _lib.device_guard(x_span):
             d_x = torch.empty_like(x_span)
+            d_obj = torch.empty_like(obj_span) if ctx.vl else None
             pst = _param_struct(ctx.ptens)
             g = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
             wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
@@ -192,10 +199,11 @@ class RaggedChartFunction(torch.autograd.Function):
                 ctx.split_cot[0] = None                       # taken once
             cots = [_cont(d) for d in (d_ih, d_is, d_oh, d_os)]
             masked = [torch.empty_like(d) if d is not None else None for d in cots]      # the library masks the cotangents into these
-            _lib.call('cliora_chart_backward_ragged', plan.handle, C.byref(pst), _ptr(x_span), None, None, *map(_ptr, saved[-4:]),
-                      *map(_ptr, cots), _ptr(d_split), _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), None,
-                      C.byref(gst), ctx.run_outside, _ptr(lengths), ctx.root_levels, *map(_ptr, masked), _stream())
-        return (None, None, None, None, None, d_x) + tuple(g[n] for n in _lib.PARAM_FIELDS)
+            _lib.call('cliora_chart_backward_ragged' + ('_vl' if ctx.vl else ''), plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span),
+                      _ptr(ctx.drop_mask), *map(_ptr, saved[-4:]), *map(_ptr, cots), _ptr(d_split), _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb),
+                      plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst), ctx.run_outside, _ptr(lengths), ctx.root_levels,
+                      *map(_ptr, masked), _stream())
+        return (None, None, None, None, None, d_x, d_obj, None) + tuple(g[n] for n in _lib.PARAM_FIELDS)
 
 
 def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_levels):
@@ -290,7 +298,7 @@ class DioraBase(nn.Module):
         # lengths: the chart then runs through cliora_chart_forward_ragged and leaves its status word in _ragged_status
         self.__dict__['_ragged'] = None
         # cliora_amd.ragged sets the same pair around a TRAINING forward over such a batch (forward_ragged_train): the chart then is a
-        # RaggedChartFunction node, text-only DIORA only
+        # RaggedChartFunction node (text-only DIORA, or CLIORA with its regions)
         self.__dict__['_ragged_train'] = None
         self.init_parameters()
         self.reset_parameters()
@@ -377,8 +385,9 @@ class DioraBase(nn.Module):
 
     def _check_ragged_train(self, L, hooks):
         """A padded chart of mixed lengths with a backward: every refusal before any launch."""
-        if self.vision_language or self.plan_arch != 0:
-            raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP)')
+        if self.plan_arch != 0:
+            raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP) '
+                                      'or CLIORA (cliora_amd.cliora.DioraMLP), not the TreeLSTM')
         if L > _lib.MAX_L:
             raise _lib.ChartLibError('L = %d > %d: a padded chart of mixed lengths trains through at most %d words' % (L, _lib.MAX_L, _lib.MAX_L))
         if hooks:
@@ -386,9 +395,10 @@ class DioraBase(nn.Module):
         if self.compress:
             raise NotImplementedError('compress = True is not supported on a padded chart of mixed lengths')
 
-    def _run_ragged_train(self, plan, holder, x_span, params, ragged):
+    def _run_ragged_train(self, plan, holder, x_span, obj_embed_span, params, ragged):
         """_run_chart through RaggedChartFunction; the status word is left in _ragged_status."""
-        *charts, self.__dict__['_ragged_status'] = RaggedChartFunction.apply(plan, holder, int(bool(self.outside)), *ragged, x_span, *params)
+        *charts, self.__dict__['_ragged_status'], _ = RaggedChartFunction.apply(plan, holder, int(bool(self.outside)), *ragged, x_span, None,
+                                                                                None, *params)
         return (*charts, None, None)
 
     def _hook_overridden(self, name):
@@ -456,7 +466,7 @@ class DioraBase(nn.Module):
             charts = self._run_ragged(plan, holder, x_span, obj_embed_span, params, ragged)
         elif ragged_train is not None and needs_grad:
             self._check_ragged_train(L, hooks)
-            charts = self._run_ragged_train(plan, holder, x_span, params, ragged_train)
+            charts = self._run_ragged_train(plan, holder, x_span, obj_embed_span, params, ragged_train)
         elif ragged_train is not None:
             raise _lib.ChartLibError('a padded training chart of mixed lengths needs gradients enabled; cliora_amd.ragged.forward_ragged '
                                      'runs the same batch for inference')

@@ -122,26 +122,61 @@ class FusedContrastive(torch.autograd.Function):
     gradient in one launch (the backward scales the stored gradients by the incoming cotangent)."""
 
     @staticmethod
-    def forward(ctx, smax, ins, outs, margin, alpha):
+    def forward(ctx, smax, ins, outs, margin, alpha, lengths=None, status_out=None):
+        """lengths (int32 device tensor (B,)): cliora_contrastive_loss_ragged over the sentences' own triangles of a padded chart; its
+        status word (the count of lengths outside 1..L) is copied into status_out[0], a one-element list, still on the device."""
         from . import _lib
         B, _, Cc = smax.shape
         smax, ins, outs = smax.contiguous().float(), ins.contiguous().float(), outs.contiguous().float()
         dev = smax.device
         loss = torch.empty(1, device=dev)
         d_smax, d_ins, d_outs = torch.empty_like(smax), torch.empty_like(ins), torch.empty_like(outs)
-        nbytes = _lib.fn('cliora_contrastive_workspace_bytes')(B, Cc)
-        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         p = _lib.ptr
         with _lib.device_guard(smax):
-            _lib.call('cliora_contrastive_loss', B, Cc, p(smax), p(ins), p(outs), float(margin), float(alpha), p(loss), p(d_smax), p(d_ins),
-                      p(d_outs), p(ws), nbytes, _lib.stream())
+            if lengths is None:
+                nbytes = _lib.fn('cliora_contrastive_workspace_bytes')(B, Cc)
+                ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+                _lib.call('cliora_contrastive_loss', B, Cc, p(smax), p(ins), p(outs), float(margin), float(alpha), p(loss), p(d_smax), p(d_ins),
+                          p(d_outs), p(ws), nbytes, _lib.stream())
+            else:
+                lengths = check_lengths(lengths, B, dev)
+                nbytes = RAGGED_STATUS_BYTES + _lib.fn('cliora_contrastive_workspace_bytes')(B, 2 * Cc)
+                ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+                _lib.call('cliora_contrastive_loss_ragged', B, Cc, p(smax), p(ins), p(outs), p(lengths), float(margin), float(alpha), p(loss),
+                          p(d_smax), p(d_ins), p(d_outs), p(ws), nbytes, _lib.stream())
+                if status_out is not None:
+                    status_out[0] = ws[:4].view(torch.int32)
         ctx.save_for_backward(d_smax, d_ins, d_outs)
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         d_smax, d_ins, d_outs = ctx.saved_tensors
-        return d_smax * g, d_ins * g, d_outs * g, None, None
+        return d_smax * g, d_ins * g, d_outs * g, None, None, None, None
+
+
+RAGGED_STATUS_BYTES = heads.RAGGED_STATUS_BYTES
+
+
+def check_lengths(lengths, B, dev):
+    """The lengths of a padded chart's sentences as the loss entries take them: int32, (B,), on the scores' device."""
+    if lengths.dtype != torch.int32 or lengths.numel() != B or lengths.device != dev:
+        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (B, dev))
+    return lengths.contiguous()
+
+
+def triangle_masks(lengths, L):
+    """Of a padded chart of length L whose sentence x has lengths[x] words, in closed form from (n_x, level,
+    pos) and on the lengths' device: own (B, C) bool, the cells (level, pos) with pos + level < n_x; half (B, C) bool, the owned cells
+    whose number in the sentence's OWN chart, level n_x - level (level - 1) / 2 + pos, is below C_x // 2; root (B,) int64, the padded
+    chart's row of the cell (n_x - 1, 0)."""
+    level = torch.cat([torch.full((L - k,), k, dtype=torch.int64) for k in range(L)]).to(lengths.device)
+    pos = torch.cat([torch.arange(L - k, dtype=torch.int64) for k in range(L)]).to(lengths.device)
+    n = lengths.long().view(-1, 1)
+    own = pos + level < n
+    half = own & (level * n - level * (level - 1) // 2 + pos < (n * (n + 1) // 2) // 2)
+    lv = n.view(-1) - 1
+    return own, half, lv * L - lv * (lv - 1) // 2
 
 
 class ContrastiveLoss(nn.Module):
@@ -152,10 +187,19 @@ class ContrastiveLoss(nn.Module):
         super().__init__()
         self.margin, self.alpha, self.floor = margin, alpha_contr, 1e-8
 
-    def forward(self, diora):
+    def forward(self, diora, lengths=None):
+        """lengths (int32 (B,), on the scores' device): the sentences of a right-padded chart have these many words, and the loss is
+        DESIGN.md section 23's over their own triangles; `self.status` then holds the fused kernel's status word, on the device."""
         ins, outs = diora.inside_s.squeeze(-1), diora.outside_s.squeeze(-1)
         B, C = ins.shape
         smax = diora.all_atten_score.max(-1).values                      # B(text),B(image),C
+        if lengths is not None:
+            if self.fused and smax.is_cuda and B <= 128:
+                status = [None]
+                v = FusedContrastive.apply(smax, ins, outs, self.margin, self.alpha, lengths, status)
+                self.__dict__['status'] = status[0]
+                return v
+            return self.forward_ragged_torch(smax, ins, outs, lengths)
         if self.fused and smax.is_cuda and B <= 128:
             return FusedContrastive.apply(smax, ins, outs, self.margin, self.alpha)
         sc = smax.permute(2, 0, 1)                                       # C,B(text),B(image)
@@ -167,6 +211,22 @@ class ContrastiveLoss(nn.Module):
         marginal = torch.exp(ins + outs - ins[:, -1:])
         return (marginal * per_span)[:, :C // 2].sum(-1).mean() * self.alpha
 
+    def forward_ragged_torch(self, smax, ins, outs, lengths):
+        """The mixed-length loss in torch ops.  Whatever the inputs hold beyond a triangle is replaced by 0 BEFORE any arithmetic (a
+        mask applied after the exp would let a NaN there into the gradients), and every sum selects its terms."""
+        B, C = ins.shape
+        L = int(round(((8 * C + 1) ** 0.5 - 1) / 2))
+        own, half, root = triangle_masks(check_lengths(lengths, B, ins.device), L)
+        zero = smax.new_zeros(())
+        s = torch.where(own[:, None, :], smax, zero)                     # s[a, c, cell]: text a's cell against image c
+        ins, outs = torch.where(own, ins, zero), torch.where(own, outs, zero)
+        pos = torch.diagonal(s, 0, 0, 1).t()                             # B,C: s[x, x, cell]
+        off_diag = ~torch.eye(B, dtype=torch.bool, device=s.device)[:, :, None]
+        txt = torch.where(off_diag, (self.margin + s - pos[:, None, :]).clamp(min=self.floor), zero).sum(1) / B       # over the images y != x
+        img = torch.where(off_diag & own[:, None, :], (self.margin + s - pos[None, :, :]).clamp(min=self.floor), zero).sum(0) / B   # texts a != x owning the cell
+        marginal = torch.exp(torch.where(half, ins + outs - ins.gather(1, root.view(-1, 1)), zero))
+        return torch.where(half, marginal * (txt + img), zero).sum() / B * self.alpha
+
 
 class VGLoss(nn.Module):
     name = 'vg_loss'
@@ -175,8 +235,21 @@ class VGLoss(nn.Module):
         super().__init__()
         self.alpha = alpha_vg
 
-    def forward(self, vg_atten_score):
+    def forward(self, vg_atten_score, lengths=None):
+        """lengths (int32 (B,), on the scores' device): sentence a of the right-padded batch has lengths[a] words, and its logits are the
+        mean over those; `self.status` then holds the fused kernel's status word, on the device."""
         B, _, L, _ = vg_atten_score.shape
+        if lengths is not None:
+            lengths = check_lengths(lengths, B, vg_atten_score.device)
+            if _native(vg_atten_score):
+                status = [None]
+                v = heads.vg_loss(vg_atten_score, self.alpha, lengths, status)
+                self.__dict__['status'] = status[0]
+                return v
+            word = torch.arange(L, device=lengths.device) < lengths.view(-1, 1)            # B,L
+            v = torch.where(word[:, None, :, None], vg_atten_score, vg_atten_score.new_zeros(()))      # zeros before any arithmetic
+            logits = v.max(-1).values.sum(-1) / lengths.view(-1, 1)
+            return self.alpha * F.cross_entropy(logits, torch.arange(B, device=logits.device))
         if _native(vg_atten_score):
             return heads.vg_loss(vg_atten_score, self.alpha)
         logits = vg_atten_score.max(-1).values.sum(-1) / L
@@ -434,30 +507,38 @@ class Trainer(object):
             torch.nn.utils.clip_grad_norm_(self.params, 5.0)
             self.optimizer.step()
 
-    def step_ragged(self, sentences, neg_samples=None, entity_labels=None, max_batch=64, max_waste=None, pad_id=0):
-        """One optimizer step over sentences of any lengths in 1..64, text-only DIORA: the sentences are packed into right-padded
-        charts (cliora_amd.ragged.forward_ragged_train), each pack's loss is weighted by its share of the tokens -- the reconstruction
-        term of the step is therefore ONE mean over all tokens, what ``step`` gives for a batch of one length -- and one backward and
-        one update follow.  entity_labels: per sentence, as batch_map['entity_labels'], for the bracket / risk terms.  Returns the
-        loss as a Python float."""
+    def step_ragged(self, sentences, neg_samples=None, entity_labels=None, max_batch=64, max_waste=None, pad_id=0, obj_feats=None):
+        """One optimizer step over sentences of any lengths in 1..64: the sentences are packed into right-padded charts
+        (cliora_amd.ragged.forward_ragged_train), each pack's losses are weighted, and one backward and one update follow.  The
+        reconstruction term (and the structured terms with it) is weighted by the pack's share of the TOKENS -- over the step it is
+        ONE mean over all tokens, what ``step`` gives for a batch of one length.  obj_feats: (N, R, img_dim) region features, one row
+        per sentence, for a CLIORA net, which then trains whatever of vg_loss and contrastive_loss it carries too (DESIGN.md section
+        23), each weighted by the pack's share of the SENTENCES: each is a mean over the pack's sentences and compares sentences of
+        that pack only.  entity_labels: per sentence, as batch_map['entity_labels'], for the bracket / risk terms.  Returns the loss
+        as a Python float."""
         from . import ragged
         if 'reconstruct_softmax_loss' not in self.net.loss_func_names:
-            raise NotImplementedError('step_ragged trains the reconstruction loss of a text-only net')
+            raise NotImplementedError('step_ragged trains the reconstruction loss of a net (with the vision-language losses it carries)')
         net = self.net
         net.train(True)
         if neg_samples is None and self.negative_sampler is not None:
             neg_samples = self.negative_sampler.sample(self.k_neg)
-        n_tokens = float(sum(len(s) for s in sentences))
+        n_tokens, n_sentences = float(sum(len(s) for s in sentences)), float(len(sentences))
         total = None
         with torch.enable_grad():
-            for idx, _, diora in ragged.forward_ragged_train(net, sentences, max_batch=max_batch, pad_id=pad_id,
-                                                             max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste):
+            for idx, lens, diora in ragged.forward_ragged_train(net, sentences, max_batch=max_batch, pad_id=pad_id, obj_feats=obj_feats,
+                                                                max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste):
                 group = [sentences[i] for i in idx]
                 labels = [entity_labels[i] for i in idx] if entity_labels is not None else None
                 part = ragged.reconstruction_loss_ragged(net, group, neg_samples, diora)
                 for _, v in net.structured_losses(labels, diora._plan.L, part.device):      # each sentence's own triangle (the holder's lengths)
                     part = part + v
                 part = part * (sum(len(s) for s in group) / n_tokens)
+                for name in net.loss_func_names:
+                    if 'contrastive' in name:
+                        part = part + getattr(net, name)(diora, lens) * (len(idx) / n_sentences)
+                    elif 'reconstruct' not in name:
+                        part = part + getattr(net, name)(diora.vg_atten_score, lens) * (len(idx) / n_sentences)
                 total = part if total is None else total + part
         if total is None:
             raise ValueError('step_ragged: no sentence')

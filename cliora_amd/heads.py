@@ -237,27 +237,40 @@ def recon_loss(emb, mat, outside_h, tokens, neg):
     return ReconLoss.apply(_pad16(emb), _pad16(mat), outside_h, tokens, neg)
 
 
+RAGGED_STATUS_BYTES = 256      # the mixed-length loss entries keep their status word at the start of the workspace (include/cliora_chart.h)
+
+
 class VGLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, vg, alpha):
+    def forward(ctx, vg, alpha, lengths=None, status_out=None):
         vg = vg.contiguous().float()
         B, _, L, R = vg.shape
         with device_guard(vg):
             loss = torch.empty(1, device=vg.device)
             d_vg = torch.empty_like(vg) if ctx.needs_input_grad[0] else None
-            nb = _lib.fn('cliora_vg_workspace_bytes')(B, L)
+            nb = _lib.fn('cliora_vg_workspace_bytes')(B, L) + (RAGGED_STATUS_BYTES if lengths is not None else 0)
             ws = torch.empty(nb, device=vg.device, dtype=torch.uint8)
-            _lib.call('cliora_vg_loss', B, L, R, ptr(vg), float(alpha), ptr(loss), ptr(d_vg), ptr(ws), nb, stream())
+            if lengths is None:
+                _lib.call('cliora_vg_loss', B, L, R, ptr(vg), float(alpha), ptr(loss), ptr(d_vg), ptr(ws), nb, stream())
+            else:      # right-padded sentences of lengths[a] words; the status word stays on the device
+                _lib.call('cliora_vg_loss_ragged', B, L, R, ptr(vg), ptr(lengths.contiguous()), float(alpha), ptr(loss), ptr(d_vg), ptr(ws), nb,
+                          stream())
+                if status_out is not None:
+                    status_out[0] = ws[:4].view(torch.int32)
         ctx.d_vg = d_vg
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        return (ctx.d_vg * g if ctx.d_vg is not None else None), None
+        return (ctx.d_vg * g if ctx.d_vg is not None else None), None, None, None
 
 
-def vg_loss(vg_atten, alpha):
-    return VGLossFn.apply(vg_atten, alpha)
+def vg_loss(vg_atten, alpha, lengths=None, status_out=None):
+    """lengths: int32 device tensor (B,) -> cliora_vg_loss_ragged, whose status word (the count of lengths outside 1..L) is left in
+    status_out[0], a one-element list, on the device."""
+    if lengths is None:
+        return VGLossFn.apply(vg_atten, alpha)
+    return VGLossFn.apply(vg_atten, alpha, lengths, status_out)
 
 
 class FusedClipAdam(object):

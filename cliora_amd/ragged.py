@@ -14,11 +14,13 @@ into inside_s beyond each triangle after the inside pass zeroes those pairs' sof
 (n - 1, 0) receives the seed rows after its level.  ``forward_ragged`` runs both passes that way, for text-only and CLIORA nets;
 ``evaluate.evaluate_ragged`` and ``phrases.embed_phrases_ragged`` are built on it.  Those entries are inference only.
 
-TRAINING text-only DIORA through the same padded chart: ``forward_ragged_train`` runs each pack as one
-autograd node (``diora.RaggedChartFunction``: cliora_chart_forward_ragged_train / cliora_chart_backward_ragged -- the cotangents are
-masked to each triangle and each sentence's root cell is cut out of the outside backward, so the unchanged backward chains compute
-each sentence's own gradient), ``reconstruction_loss_ragged`` is the reconstruction loss over the valid tokens, and
-``harness.Trainer.step_ragged`` one optimizer step over all packs.
+TRAINING through the same padded chart: ``forward_ragged_train`` runs each pack as one autograd node
+(``diora.RaggedChartFunction``: cliora_chart_forward_ragged_train / cliora_chart_backward_ragged -- the cotangents are masked to
+each triangle and each sentence's root cell is cut out of the outside backward, so the unchanged backward chains compute each
+sentence's own gradient), ``reconstruction_loss_ragged`` is the reconstruction loss over the valid tokens, and
+``harness.Trainer.step_ragged`` one optimizer step over all packs.  A CLIORA net trains the same way when given the region
+features of every sentence (``obj_feats=``): the ``_vl`` forms of the two entries, and the VG and contrastive losses over each
+sentence's own words and triangle (``harness.VGLoss`` / ``ContrastiveLoss`` with ``lengths``).
 
     from cliora_amd.ragged import parse_ragged, encode_ragged, forward_ragged
     trees = parse_ragged(net, sentences)        # net: harness.Net; sentences: lists of token ids, any lengths 1..64
@@ -27,6 +29,7 @@ each sentence's own gradient), ``reconstruction_loss_ragged`` is the reconstruct
     trees = parse_ragged(vl_net, sentences, obj_feats=feats)     # a CLIORA net: region features (N, R, img_dim), one row per sentence
     forward_ragged(net, sentences, per_pack=lambda idx, lens, diora: ...)    # both passes; diora holds the pack's padded charts
     for idx, lens, diora in forward_ragged_train(net, sentences): ...        # the same, one pack at a time, with autograd live
+    for idx, lens, diora in forward_ragged_train(vl_net, sentences, obj_feats=feats): ...      # a CLIORA net with its images
 """
 import ctypes as C
 
@@ -262,19 +265,25 @@ def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, 
     return packs
 
 
-def forward_ragged_train(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
-    """forward_ragged with autograd live, text-only DIORA, sentences of any lengths in 1..64: a generator that packs them (``pack``)
-    and, one pack at a time, pads, embeds and runs the pack as one right-padded chart through ``diora.RaggedChartFunction``, then
-    yields ``(indices, lengths, diora)`` -- `indices` the pack's positions in `sentences`, `lengths` their int32 lengths on the device,
+def forward_ragged_train(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None):
+    """forward_ragged with autograd live, sentences of any lengths in 1..64: a generator that packs them (``pack``) and, one pack at a
+    time, pads, embeds and runs the pack as one right-padded chart through ``diora.RaggedChartFunction``, then yields
+    ``(indices, lengths, diora)`` -- `indices` the pack's positions in `sentences`, `lengths` their int32 lengths on the device,
     `diora` the chart module holding the pack's charts in the autograd graph: valid on each sentence's own triangle; cells beyond it
-    are unspecified and their cotangents are ignored.  The status word is read after each forward (one synchronisation per pack) and
-    a rejected length raises.  The structured losses of the module (bracket_nll, tree_objective, ...) read each sentence's own
-    triangle.  Gradients must be enabled; the net's mode is the caller's."""
+    are unspecified and their cotangents are ignored.  Text-only DIORA, or a CLIORA net with obj_feats (N, R, img_dim), one row of
+    region features per sentence: each pack then encodes its images, and the module also holds vg_atten_score and all_atten_score of
+    the pack, to be read through the length-aware losses (harness.VGLoss / ContrastiveLoss with `lengths`).  The status word is read
+    after each forward (one synchronisation per pack) and a rejected length raises.  The structured losses of the module
+    (bracket_nll, tree_objective, ...) read each sentence's own triangle.  Gradients must be enabled; the net's mode is the caller's."""
+    from .cliora import DioraMLP as VLDiora
     from .diora import DioraMLP as TextDiora
     diora = net.diora
-    if type(diora).vision_language or not isinstance(diora, TextDiora):
-        raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP), got %s'
-                                  % type(diora).__name__)
+    vl = isinstance(diora, VLDiora) and obj_feats is not None
+    if not vl and (type(diora).vision_language or not isinstance(diora, TextDiora)):
+        raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP), got %s%s'
+                                  % (type(diora).__name__, ' without obj_feats' if isinstance(diora, VLDiora) else ''))
+    if not vl and obj_feats is not None:
+        raise ValueError('obj_feats given to a text-only net')
     if not torch.is_grad_enabled():
         raise _lib.ChartLibError('forward_ragged_train needs gradients enabled; forward_ragged runs the same batch for inference')
     lengths = [len(s) for s in sentences]
@@ -284,19 +293,24 @@ def forward_ragged_train(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WAS
         raise ValueError('an empty sentence has no chart')
     if max(lengths) > MAX_L:             # before any pack has run
         raise _lib.ChartLibError('L > %d is not supported by the padded training chart (got a sentence of %d words)' % (MAX_L, max(lengths)))
+    if vl and len(obj_feats) != len(sentences):
+        raise ValueError('obj_feats holds %d sentences, not %d' % (len(obj_feats), len(sentences)))
     dev = next(net.parameters()).device
     for idx in pack(lengths, max_batch, max_waste):
         tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
         x_span, x_word = net.embed(tokens.to(dev))
+        o_span = o_word = None
+        if vl:
+            o_span, o_word = net.img_encoder(obj_feats[torch.as_tensor(idx, dtype=torch.int64)].to(dev))
         lens = lens.to(dev)
         diora.__dict__['_ragged_train'] = (lens, root_level_mask(lengths[i] for i in idx))
         try:
-            diora(x_span, x_word)
+            diora(x_span, x_word, o_span, o_word) if vl else diora(x_span, x_word)
         finally:
             diora.__dict__['_ragged_train'] = None
         bad = int(diora._ragged_status.item())
         if bad:
-            raise _lib.ChartLibError('cliora_chart_forward_ragged_train rejected %d sentence length(s)' % bad)
+            raise _lib.ChartLibError('cliora_chart_forward_ragged_train%s rejected %d sentence length(s)' % ('_vl' if vl else '', bad))
         yield idx, lens, diora
 
 

@@ -234,6 +234,20 @@ int cliora_contrastive_loss(int B, int C, const float* all_max, const float* ins
                             float alpha, float* loss, float* d_all_max, float* d_inside_s, float* d_outside_s, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* The same loss over B right-padded sentences of lengths[b] words in a chart of length L, C = L (L + 1) / 2.
+ * Sentence x owns the cells (level, pos) with pos + level < lengths[x]; such a cell is number level n - level (level - 1) / 2 + pos of
+ * its own chart of C_x = n (n + 1) / 2 cells, and half(x) is the cells whose number is below C_x / 2 (none for one word).  For x and a
+ * cell of half(x):  txt = (1/B) sum_{y != x} max(margin + s[x][y] - s[x][x], 1e-8) over every image;  img = (1/B) sum over the texts
+ * a != x THAT OWN THE CELL of max(margin + s[a][x] - s[x][x], 1e-8) -- the divisor stays B;  marg = exp(in_s + out_s - in_s[x][root(x)])
+ * with root(x) the cell (lengths[x] - 1, 0);  loss = alpha / B * sum_x sum_{half(x)} marg (txt + img).  Nothing beyond a triangle is
+ * read into a sum (selected, not multiplied by a mask: NaN there does not leak) and every gradient there is exactly 0.  Fixed
+ * summation order; with every length = L the results are bitwise cliora_contrastive_loss's.  B <= 128.
+ * workspace: 256 + cliora_contrastive_workspace_bytes(B, 2 * C) bytes; its first int32 is the STATUS WORD: the number of lengths outside
+ * [1, L].  Such a sentence owns no cell -- nothing is written for it -- and its image still stands as a negative for the others. */
+int cliora_contrastive_loss_ragged(int B, int C, const float* all_max, const float* inside_s, const float* outside_s,
+                                   const int32_t* lengths, float margin, float alpha, float* loss, float* d_all_max, float* d_inside_s,
+                                   float* d_outside_s, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the callers either side of the chart, as kernels of this library ----
  *
  * Projection of (optionally looked-up) rows: y (nrows, D) = gather(x, index) w^T + bias.
@@ -281,6 +295,14 @@ int cliora_recon_backward(const int64_t* tokens, const int64_t* neg, int B, int 
 size_t cliora_vg_workspace_bytes(int B, int L);
 int cliora_vg_loss(int B, int L, int R, const float* vg_atten, float alpha, float* loss, float* d_vg_atten, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* The same loss over right-padded sentences of lengths[a] words:  logits[a][c] = sum_{l < lengths[a]} max_r vg_atten[a][c][l][r] /
+ * lengths[a].  d_vg_atten[a][:][l][:] is exactly 0 for l >= lengths[a], and nothing there is read.  Same summation order: with every
+ * length = L the results are bitwise cliora_vg_loss's.  workspace: 256 + cliora_vg_workspace_bytes(B, L) bytes; its first int32 is
+ * the STATUS WORD: the number of lengths outside [1, L].  Such a sentence has no row in the cross entropy (the mean's divisor stays
+ * B) and a zero gradient; its image still stands as a negative for the others. */
+int cliora_vg_loss_ragged(int B, int L, int R, const float* vg_atten, const int32_t* lengths, float alpha, float* loss,
+                          float* d_vg_atten, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Trainer.gradient_update (cliora/net/trainer.py:450-455): torch.nn.utils.clip_grad_norm_(params, max_norm) followed by one
  * torch.optim.Adam step (no weight decay, no amsgrad), over ONE flat fp32 buffer holding every parameter (and one holding every
@@ -546,6 +568,26 @@ int cliora_chart_backward_ragged(cliora_plan* plan, const cliora_params* params,
                                  void* bwd_workspace, size_t bwd_workspace_bytes, float* d_x_span, float* d_obj_span,
                                  const cliora_params* grads, int ran_outside, const int32_t* lengths, uint64_t root_levels,
                                  float* m_inside_h, float* m_inside_s, float* m_outside_h, float* m_outside_s, void* stream);
+
+/* The same pair for CLIORA plans (R > 0): same arguments, with obj_span (B, R, D) REQUIRED, the (B, C, R)
+ * drop_mask of cliora_chart_forward taken (NULL: no dropout) and d_obj_span (B, R, D) written (NULL: skipped).  The attention over
+ * a sentence's own regions touches the inside cells only and has no term across cells, so nothing is added to the schedule: the
+ * attention backward runs over every cell of a level, and a cell beyond a triangle carries vH = 0 and finite attention state (an
+ * all-masked cell has uniform weights), so its contribution to d_obj_span and to the chains is an exact zero.  The backward never
+ * runs on the sentence-resident kernels; with every length equal to L the results are bitwise those of cliora_chart_backward_split.
+ * Refused with CLIORA_EINVAL and a message of their own, before any launch: TreeLSTM plans, text-only plans (R = 0), a NULL obj_span,
+ * L > 64, CLIORA_FWD_PAIR_STATES, params->root_mat (compress); the forward also CLIORA_FWD_NO_BACKWARD. */
+int cliora_chart_forward_ragged_train_vl(cliora_plan* plan, const cliora_params* params, const float* x_span, const float* obj_span,
+                                         const float* drop_mask, float* inside_h, float* inside_s, float* outside_h, float* outside_s,
+                                         float* inside_c, void* fwd_workspace, size_t fwd_workspace_bytes, int run_outside,
+                                         const int32_t* lengths, uint64_t root_levels, int32_t* status, void* stream);
+int cliora_chart_backward_ragged_vl(cliora_plan* plan, const cliora_params* params, const float* x_span, const float* obj_span,
+                                    const float* drop_mask, const float* inside_h, const float* inside_s, const float* outside_h,
+                                    const float* outside_s, const float* d_inside_h, const float* d_inside_s, const float* d_outside_h,
+                                    const float* d_outside_s, const float* d_split_s, void* fwd_workspace, size_t fwd_workspace_bytes,
+                                    void* bwd_workspace, size_t bwd_workspace_bytes, float* d_x_span, float* d_obj_span,
+                                    const cliora_params* grads, int ran_outside, const int32_t* lengths, uint64_t root_levels,
+                                    float* m_inside_h, float* m_inside_s, float* m_outside_h, float* m_outside_s, void* stream);
 
 /* Grounding evaluation (cliora/scripts/parse.py:176-264, the host loop over every phrase and predicted span): ONE launch for a batch,
  * one workgroup per sentence.  All pointers are device memory.
