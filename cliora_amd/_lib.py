@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CLIORA_CHART_LIB') or os.path.join(HERE, 'libcliora_chart.so')   # override: kernel experiments only
 
 NORM = {'none': 0, 'unit': 1}
-MAX_L = 64               # csrc/plan.hpp CLIORA_MAX_L: the longest sentence of anything with a backward, of TreeLSTM / compress plans, of the ragged both-pass entries
+MAX_L = 64               # csrc/plan.hpp CLIORA_MAX_L: the longest sentence of anything with a backward, of TreeLSTM / compress plans, of the ragged entries that take the root-level mask as one word
 MAX_L_FWD = 128          # csrc/plan.hpp CLIORA_MAX_L_FWD: the longest sentence of a forward-only ("long") DioraMLP / CLIORA plan
 FWD_NO_BACKWARD = 2      # include/cliora_chart.h: flag bits of cliora_chart_forward's run_outside word
 FWD_PAIR_STATES = 4
@@ -52,6 +52,7 @@ ABI = {
     'cliora_chart_backward': (i32, [vp, pp] + [vp] * 11 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_backward_split': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_forward_ragged': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
+    'cliora_chart_forward_ragged_wide': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, vp, vp, vp]),
     'cliora_chart_forward_ragged_train': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),
     'cliora_chart_backward_ragged': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp, u64] + [vp] * 4 + [vp]),
     'cliora_chart_forward_ragged_train_vl': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),

@@ -498,7 +498,7 @@ struct FwdCall {
         const PassOps out = pass_ops(true);
         for (int level = L - 2; level >= 0 && run_outside; --level) {
             OKR(level_step(out, level, nullptr));
-            if (!((rg->root_levels >> level) & 1)) continue;
+            if (!rg->root_level(level)) continue;
             hipLaunchKernelGGL(ragged_root_seed, dim3(B), dim3(4 * 64), 0, st, level, p.level_offset[level], C, p.Dp, rg->lengths, OH, OS,
                                ws + f.nrmo, ws + f.po);
             LAUNCHOK("ragged_root_seed");
@@ -536,8 +536,8 @@ struct FwdCall {
     }
 };
 
-// The body of cliora_chart_forward.  rg == nullptr: that entry, launch for launch.  rg != nullptr: cliora_chart_forward_ragged
-// (api_ragged.hip, which has checked its own refusals) -- FwdSchedule::Ragged.
+// The body of cliora_chart_forward.  rg == nullptr: that entry, launch for launch.  rg != nullptr: a ragged forward entry
+// (api_ragged.hip, which has checked its own refusals) -- FwdSchedule::Ragged; on a long plan only cliora_chart_forward_ragged_wide's.
 int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
                              const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
                              float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
@@ -563,7 +563,7 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
         if (run_outside & CLIORA_FWD_PAIR_STATES)
             return fail(CLIORA_EINVAL, "L > 64: CLIORA_FWD_PAIR_STATES is not supported (a long plan sizes no per-pair rows)");
         if (compress) return fail(CLIORA_EINVAL, "L > 64: compress (root_mat) is not supported");
-        if (rg) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: L > 64 is not supported (the root-level mask holds 64 levels)");
+        if (rg && !rg->wide) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: L > 64 is not supported (the root-level mask holds 64 levels)");
         if (g_cliora_resident == 1 && !vl && p.Dp <= 64)
             return fail(CLIORA_EINVAL, "L > 64: the sentence-resident kernels are not supported (cliora_set_resident / CLIORA_RESIDENT forces them on)");
     }

@@ -1,7 +1,7 @@
 // C ABI, ragged unit: the forward (both passes) of mixed-length sentences that share one right-padded chart, for inference
-// (cliora_chart_forward_ragged) and for training (cliora_chart_forward_ragged_train, cliora_chart_backward_ragged; their _vl forms for
-// CLIORA plans).  See
-// include/cliora_chart.h for the contract and ragged_kernels.hpp for why the padded chart serves; the decode is in api_decode.hip.
+// (cliora_chart_forward_ragged at L <= 64, cliora_chart_forward_ragged_wide at L <= 128) and for training
+// (cliora_chart_forward_ragged_train, cliora_chart_backward_ragged; their _vl forms for CLIORA plans).  See include/cliora_chart.h for
+// the contract and ragged_kernels.hpp for why the padded chart serves; the decode is in api_decode.hip.
 #include "api_common.hpp"
 
 extern "C" int cliora_chart_forward_ragged(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
@@ -17,7 +17,36 @@ extern "C" int cliora_chart_forward_ragged(cliora_plan* plan, const cliora_param
     if (P->root_mat) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: compress (root_mat) is not supported");
     if (drop_mask) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: inference only, drop_mask must be NULL");
     HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), (hipStream_t)stream));
-    const RaggedFwd rg{lengths, root_levels, status};
+    const RaggedFwd rg{lengths, {root_levels, 0}, status, false};
+    return cliora_chart_forward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws,
+                                    fwd_ws_bytes, run_outside, stream, &rg);
+}
+
+// The same call with the root-level mask as two words in host memory: every DioraMLP / CLIORA plan of L <= 128, long plans included
+// (DESIGN.md section 24).  Every refusal below comes before any HIP call.
+extern "C" int cliora_chart_forward_ragged_wide(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                                                const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
+                                                float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
+                                                const int32_t* lengths, const uint64_t* root_levels, int32_t* status, void* stream) {
+    if (!plan || !P || !lengths || !root_levels || !status) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: NULL argument");
+    if (plan->p.arch != 0) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: TreeLSTM plans are not supported");
+    if (!(run_outside & CLIORA_FWD_NO_BACKWARD))
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: inference only, pass CLIORA_FWD_NO_BACKWARD (a padded chart has no backward)");
+    if (run_outside & CLIORA_FWD_PAIR_STATES)
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: CLIORA_FWD_PAIR_STATES is not supported");
+    if (P->root_mat) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: compress (root_mat) is not supported");
+    if (drop_mask) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: inference only, drop_mask must be NULL");
+    const int L = plan->p.L;              // 1 .. 128 (plan creation)
+    const uint64_t w0 = root_levels[0], w1 = root_levels[1];
+    const uint64_t above0 = L >= 64 ? 0 : w0 >> L, above1 = L <= 64 ? w1 : (L >= 128 ? 0 : w1 >> (L - 64));
+    if (above0 || above1)
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: root_levels has a bit set at or above L = " + std::to_string(L) +
+                                       " (bit t stands for a sentence of t + 1 words)");
+    if (plan->p.is_long() && g_cliora_resident == 1 && plan->p.R <= 0 && plan->p.Dp <= 64)
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_wide: L > 64: the sentence-resident kernels are not supported "
+                                   "(cliora_set_resident / CLIORA_RESIDENT forces them on)");
+    HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), (hipStream_t)stream));
+    const RaggedFwd rg{lengths, {w0, w1}, status, true};
     return cliora_chart_forward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws,
                                     fwd_ws_bytes, run_outside, stream, &rg);
 }
@@ -56,7 +85,7 @@ extern "C" int cliora_chart_forward_ragged_train(cliora_plan* plan, const cliora
     if (run_outside & CLIORA_FWD_NO_BACKWARD)
         return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_train: writes the backward's state, CLIORA_FWD_NO_BACKWARD is cliora_chart_forward_ragged's");
     HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), (hipStream_t)stream));
-    const RaggedFwd rg{lengths, root_levels, status};
+    const RaggedFwd rg{lengths, {root_levels, 0}, status, false};
     return cliora_chart_forward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws,
                                     fwd_ws_bytes, run_outside, stream, &rg);
 }
@@ -89,7 +118,7 @@ extern "C" int cliora_chart_forward_ragged_train_vl(cliora_plan* plan, const cli
     if (run_outside & CLIORA_FWD_NO_BACKWARD)
         return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged_train_vl: writes the backward's state, CLIORA_FWD_NO_BACKWARD is cliora_chart_forward_ragged's");
     HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), (hipStream_t)stream));
-    const RaggedFwd rg{lengths, root_levels, status};
+    const RaggedFwd rg{lengths, {root_levels, 0}, status, false};
     return cliora_chart_forward_run(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws,
                                     fwd_ws_bytes, run_outside, stream, &rg);
 }

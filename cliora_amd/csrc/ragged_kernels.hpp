@@ -22,7 +22,7 @@ namespace cliora {
 // That root has none: its rows are overwritten with the seed's -- cell C - 1 holds unit(root vector), outside_s = 0, its norm and
 // its W1R_out projection for every sentence -- once the level kernels have written level n_b - 1 (ragged_root_seed).
 // ---------------------------------------------------------------------------------
-constexpr float RAGGED_MASKED = -1e30f;          // sums of such scores over 64 levels stay far inside fp32's range
+constexpr float RAGGED_MASKED = -1e30f;          // sums of such scores over 128 levels (about -1.3e32) stay far inside fp32's range
 
 // One thread per (sentence, cell).  A length outside [1, L] is counted once in *status (zeroed by the caller); the cells of such a
 // sentence are unspecified (n < 1 masks all of them, n > L none: nothing is read or written out of bounds either way).

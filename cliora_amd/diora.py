@@ -206,10 +206,19 @@ class RaggedChartFunction(torch.autograd.Function):
         return (None, None, None, None, None, d_x, d_obj, None) + tuple(g[n] for n in _lib.PARAM_FIELDS)
 
 
+def split_root_levels(mask):
+    """A root-level mask of up to 128 bits as cliora_chart_forward_ragged_wide takes it: two 64-bit words in host memory, bit t & 63 of
+    word t >> 6 for level t."""
+    mask = int(mask)
+    return (C.c_uint64 * 2)(mask & 0xFFFFFFFFFFFFFFFF, (mask >> 64) & 0xFFFFFFFFFFFFFFFF)
+
+
 def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_levels):
     """cliora_chart_forward_ragged (include/cliora_chart.h): both passes of a right-padded batch of mixed lengths, inference only, so no
-    autograd node.  lengths: int32 device tensor (B,); root_levels: the bit mask of {n - 1}.  -> inside_h, inside_s, outside_h,
-    outside_s, inside_c (None for a text-only plan), status (1,) int32 on the device, which the caller must read."""
+    autograd node.  lengths: int32 device tensor (B,); root_levels: the bit mask of {n - 1}, a Python int.  A long plan (L > 64) runs
+    through cliora_chart_forward_ragged_wide, which takes the mask as two 64-bit words; a short plan through the entry it always ran
+    through.  -> inside_h, inside_s, outside_h, outside_s, inside_c (None for a text-only plan), status (1,) int32 on the device,
+    which the caller must read."""
     if not x_span.is_cuda:
         raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
     D, dev, vl = plan.D, x_span.device, obj_span is not None
@@ -217,13 +226,19 @@ def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_
     x_span, obj_span = x_span.detach().contiguous().float(), _cont(obj_span.detach() if vl else None)
     lengths = lengths.contiguous()
     ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
+    wide = plan.L > _lib.MAX_L
+    entry, mask = 'cliora_chart_forward_ragged', int(root_levels)
+    if wide:
+        if mask < 0 or mask >> _lib.MAX_L_FWD:
+            raise ValueError('root_levels holds a bit at or above %d' % _lib.MAX_L_FWD)
+        entry, mask = 'cliora_chart_forward_ragged_wide', split_root_levels(mask)
     with _lib.device_guard(x_span):
         outs, ws, nbytes = chart_buffers(plan, dev, 0, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
         inside_c = outs.pop().zero_() if vl else None
         status = torch.empty(1, device=dev, dtype=torch.int32)
         pst = _param_struct(ptens)
-        _lib.call('cliora_chart_forward_ragged', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), None, *map(_ptr, outs),
-                  _ptr(inside_c), _ptr(ws), nbytes, int(bool(outside)) | _lib.FWD_NO_BACKWARD, _ptr(lengths), int(root_levels),
+        _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), None, *map(_ptr, outs),
+                  _ptr(inside_c), _ptr(ws), nbytes, int(bool(outside)) | _lib.FWD_NO_BACKWARD, _ptr(lengths), mask,
                   _ptr(status), _stream())
     holder.clear()
     holder.append(ws)
@@ -295,7 +310,7 @@ class DioraBase(nn.Module):
         self.index = None
         self.charts = None
         # cliora_amd.ragged sets (lengths on the device, root-level mask) around an eval forward over a right-padded batch of mixed
-        # lengths: the chart then runs through cliora_chart_forward_ragged and leaves its status word in _ragged_status
+        # lengths: the chart then runs through cliora_chart_forward_ragged (L > 64: _wide) and leaves its status word in _ragged_status
         self.__dict__['_ragged'] = None
         # cliora_amd.ragged sets the same pair around a TRAINING forward over such a batch (forward_ragged_train): the chart then is a
         # RaggedChartFunction node (text-only DIORA, or CLIORA with its regions)
@@ -360,7 +375,8 @@ class DioraBase(nn.Module):
                              _wss=None, _plan=None, _ragged_status=None)
 
     def _check_long(self, L, needs_grad, hooks):
-        """64 < L <= 128 runs on a forward-only plan (include/cliora_chart.h): every refusal before any launch."""
+        """64 < L <= 128 runs on a forward-only plan (include/cliora_chart.h): every refusal before any launch.  A padded chart of mixed
+        lengths (_ragged) is taken at these lengths too (cliora_chart_forward_ragged_wide)."""
         if L <= _lib.MAX_L:
             return
         if needs_grad or self.training:
@@ -371,9 +387,6 @@ class DioraBase(nn.Module):
                                      'per-pair rows)' % (L, _lib.MAX_L))
         if self.compress:
             raise _lib.ChartLibError('L = %d > %d: compress = True is not supported' % (L, _lib.MAX_L))
-        if self.__dict__.get('_ragged') is not None:
-            raise _lib.ChartLibError('L > %d is not supported by the both-pass padded chart (its root-level mask holds %d levels): run '
-                                     'longer sentences through the uniform-length entry points' % (_lib.MAX_L, _lib.MAX_L))
 
     def _check_ragged(self, needs_grad, hooks):
         if needs_grad or self.training:

@@ -324,7 +324,7 @@ def evaluate(net, batches, idx2word, out_path=None, postprocess=False, decode='v
 
 
 def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, max_batch=64, max_waste=None, pad_id=0,
-                    return_details=False, decode='viterbi'):
+                    return_details=False, decode='viterbi', max_len=64, max_long_batch=8):
     """``evaluate`` for examples of any lengths, given in any order: the sentences are packed into right-padded charts
     (cliora_amd.ragged), each pack costs one forward with the outside pass (cliora_chart_forward_ragged), one cliora_cky_spans_ragged,
     one cliora_ground_eval_ragged and one device-to-host copy, and the results come back in the caller's order.
@@ -336,7 +336,8 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
     the eval losses per uniform-length batch (the reconstruction loss reads every leaf of the batch and shares its negatives, the
     contrastive and VG losses compare the sentences of a batch with each other), and their ops take no per-sentence lengths.  return_details: also a list with, per
     example, None (skipped) or a dict of spans (n-1, 2), sent (3,), hit / ccr / word / box per phrase and span_xyxy (n-1, 4).
-    decode: 'viterbi' or 'mbr', as ``evaluate``."""
+    decode: 'viterbi' or 'mbr', as ``evaluate``.  max_len: the longest sentence taken, 64 or up to 128 (an unfiltered test set); a
+    pack topped by a sentence of more than 64 words then holds at most `max_long_batch` sentences (``ragged.forward_ragged``)."""
     from . import ragged
     entry = ragged.decode_entry(decode)
     diora = net.diora
@@ -376,7 +377,8 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
                 lines[keep[j]] = batch_records(one, tree, [list(ex[b]['sentence'])], [ex[b]['example_id']], idx2word, vl, postprocess)[0]
 
     ragged.forward_ragged(net, sents, obj_feats=feats, per_pack=per_pack, max_batch=max_batch,
-                          max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste, pad_id=pad_id)
+                          max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste, pad_id=pad_id, max_len=max_len,
+                          max_long_batch=max_long_batch)
     ev = Evaluator()
     for det in details:                 # in the caller's order: the sentence F1s are averaged in it
         if det is not None:

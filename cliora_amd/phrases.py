@@ -211,7 +211,8 @@ def embed_phrases(net, batches, mode, normalize=False, min_size=2, postprocess=F
 
 
 def embed_phrases_ragged(net, sentences, mode, example_ids=None, entity_labels=None, trees=None, obj_feats=None, normalize=False,
-                         min_size=2, postprocess=False, idx2word=None, max_batch=64, max_waste=None, pad_id=0):
+                         min_size=2, postprocess=False, idx2word=None, max_batch=64, max_waste=None, pad_id=0, max_len=64,
+                         max_long_batch=8):
     """``embed_phrases`` for sentences of any lengths, given in any order: packed into right-padded charts and run with the outside
     pass made each sentence's own (cliora_amd.ragged.forward_ragged); cliora_phrase_gather addresses a cell by (sentence, pos, size)
     within the padded chart's L, so it reads the padded charts as they are.  -> PhraseSet whose rows follow the caller's order of
@@ -220,7 +221,8 @@ def embed_phrases_ragged(net, sentences, mode, example_ids=None, entity_labels=N
     sentences: lists of token ids; example_ids: one per sentence (default: its index); entity_labels (mode 'entities') / trees
     (mode 'given'): one entry per sentence, as batch_map['entity_labels'][b] / batch_map['trees'][b]; obj_feats: (N, R, img_dim) for a
     CLIORA net.  'all-spans' means the cells of each sentence's own triangle.  Sentences of length <= 2 are skipped, as both scripts
-    skip such batches.  Every row must lie inside its sentence (checked on the host)."""
+    skip such batches.  Every row must lie inside its sentence (checked on the host).  max_len: the longest sentence taken, 64 or up to
+    128; a pack topped by a sentence of more than 64 words then holds at most `max_long_batch` sentences (``ragged.forward_ragged``)."""
     from . import ragged
     if mode not in MODES:
         raise ValueError('mode %r: one of %s' % (mode, ', '.join(MODES)))
@@ -276,7 +278,8 @@ def embed_phrases_ragged(net, sentences, mode, example_ids=None, entity_labels=N
             parts[i] = ([(i,) + rows[r][1:] for r in rr], out[torch.as_tensor(rr, dtype=torch.int64, device=dev)])
 
     ragged.forward_ragged(net, sents, obj_feats=feats, per_pack=per_pack, max_batch=max_batch,
-                          max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste, pad_id=pad_id)
+                          max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste, pad_id=pad_id, max_len=max_len,
+                          max_long_batch=max_long_batch)
     pset = PhraseSet(dim=diora.size, device=dev)
     order = sorted(parts)
     if order:

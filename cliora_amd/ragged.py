@@ -12,7 +12,10 @@ it the sentence's own without touching a level kernel (``cliora_chart_forward_ra
 sibling) of a cell of the triangle leaves the triangle iff its sibling does and its score adds inside_s[sibling], so -1e30 written
 into inside_s beyond each triangle after the inside pass zeroes those pairs' softmax weights, and each sentence's root cell
 (n - 1, 0) receives the seed rows after its level.  ``forward_ragged`` runs both passes that way, for text-only and CLIORA nets;
-``evaluate.evaluate_ragged`` and ``phrases.embed_phrases_ragged`` are built on it.  Those entries are inference only.
+``evaluate.evaluate_ragged`` and ``phrases.embed_phrases_ragged`` are built on it.  Those entries are inference only.  They take
+sentences of up to 64 words unless ``max_len`` is raised, to 128 at the most: a pack topped by a sentence of
+more than 64 words runs on a forward-only plan through ``cliora_chart_forward_ragged_wide``, whose root-level mask is two words, and
+holds at most ``max_long_batch`` sentences (such a plan's workspace is large: 1 300.8 MiB at B 8 / L 128 / D 400).
 
 TRAINING through the same padded chart: ``forward_ragged_train`` runs each pack as one autograd node
 (``diora.RaggedChartFunction``: cliora_chart_forward_ragged_train / cliora_chart_backward_ragged -- the cotangents are masked to
@@ -28,6 +31,7 @@ sentence's own words and triangle (``harness.VGLoss`` / ``ContrastiveLoss`` with
     vecs = encode_ragged(net, sentences)        # (N, D) inside vectors of the sentences' roots, on the device
     trees = parse_ragged(vl_net, sentences, obj_feats=feats)     # a CLIORA net: region features (N, R, img_dim), one row per sentence
     forward_ragged(net, sentences, per_pack=lambda idx, lens, diora: ...)    # both passes; diora holds the pack's padded charts
+    forward_ragged(net, sentences, per_pack=..., max_len=128)                # ... of sentences of 1..128 words
     for idx, lens, diora in forward_ragged_train(net, sentences): ...        # the same, one pack at a time, with autograd live
     for idx, lens, diora in forward_ragged_train(vl_net, sentences, obj_feats=feats): ...      # a CLIORA net with its images
 """
@@ -40,8 +44,11 @@ from . import _lib
 from ._lib import ptr_or_null as _p, stream as _stream
 from .diora import span_buffer
 
-MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L -- the both-pass padded chart (64 root levels in one mask word) and the default of max_len
-MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_len may be raised to for the inside-only entries (parse_ragged, encode_ragged)
+MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L -- the default of max_len, the training charts, one word of the root-level mask
+MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_len may be raised to, for the inside-only and the both-pass entries
+# Sentences in a pack topped by one of more than 64 words, for the both-pass entries: the batch the figures of a long plan's forward
+# workspace are quoted for (1 300.8 MiB at B 8 / L 128 / D 400, 1 418 MiB with 36 regions); it grows with B.
+DEFAULT_MAX_LONG_BATCH = 8
 # Padded work a pack may carry beyond its sentences' own work, as a fraction of the latter.  Measured choice (tools/ragged_bench.py,
 # profiles/ragged_bench.json): the best of the sweep on 64 mixed sentences (5.3x the bucketed path), within
 # 2 % of the best on 1 000.
@@ -67,26 +74,30 @@ def pad_batch(sentences, pad_id=0):
     return torch.from_numpy(tokens), torch.tensor(lengths, dtype=torch.int32)
 
 
-def pack(lengths, max_batch=64, max_waste=DEFAULT_MAX_WASTE):
+def pack(lengths, max_batch=64, max_waste=DEFAULT_MAX_WASTE, max_long_batch=None):
     """Cut the sentences into batches that each share one padded chart: -> list of index lists.
 
     The indices are sorted by length (longest first, ties by index) and cut greedily: a batch takes the next sentence while it holds
     fewer than `max_batch` and its padded work, len(batch) * work(longest), stays within (1 + max_waste) times the sum of its
     sentences' own work().  max_waste = 0 buckets by exact work (sentences of length 1 cost nothing and ride along with each other
-    only), float('inf') fills every batch.  Pure and deterministic."""
+    only), float('inf') fills every batch.  max_long_batch: a batch whose longest sentence has more than 64 words (it runs on a
+    forward-only plan, whose workspace is large) takes at most that many sentences; None: no such cap.  Pure and deterministic."""
     if max_batch < 1:
         raise ValueError('max_batch must be at least 1')
+    if max_long_batch is not None and max_long_batch < 1:
+        raise ValueError('max_long_batch must be at least 1')
     if not max_waste >= 0:
         raise ValueError('max_waste must be >= 0')
     order = sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i))
-    packs, cur, exact, top = [], [], 0, 0
+    packs, cur, exact, top, cap = [], [], 0, 0, max_batch
     for i in order:
         w = work(lengths[i])
-        if cur and (len(cur) >= max_batch or (len(cur) + 1) * top > (1.0 + max_waste) * (exact + w)):
+        if cur and (len(cur) >= cap or (len(cur) + 1) * top > (1.0 + max_waste) * (exact + w)):
             packs.append(cur)
             cur, exact = [], 0
         if not cur:
             top = w
+            cap = min(max_batch, max_long_batch) if max_long_batch is not None and int(lengths[i]) > MAX_L else max_batch
         cur.append(i)
         exact += w
     if cur:
@@ -171,11 +182,16 @@ def root_rows(diora, lengths):
     return out[:, :D]
 
 
-def root_level_mask(lengths):
-    """Bit t set iff some sentence has n - 1 == t: the outside levels after which cliora_chart_forward_ragged seeds a root."""
+def root_level_mask(lengths, max_len=MAX_L):
+    """Bit t set iff some sentence has n - 1 == t: the outside levels after which cliora_chart_forward_ragged seeds a root.  A
+    Python int of up to max_len bits (64, or 128 for cliora_chart_forward_ragged_wide, which takes it as two words:
+    ``diora.ragged_chart`` splits it); a length outside 1..max_len sets no bit."""
+    max_len = int(max_len)
+    if not 1 <= max_len <= MAX_L_INSIDE:
+        raise ValueError('max_len must be in 1..%d' % MAX_L_INSIDE)
     m = 0
     for n in lengths:
-        if 1 <= int(n) <= MAX_L:
+        if 1 <= int(n) <= max_len:
             m |= 1 << (int(n) - 1)
     return m
 
@@ -198,10 +214,11 @@ def _check_module(net, obj_feats):
     return False
 
 
-def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats=None, outside=False, max_len=MAX_L):
+def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats=None, outside=False, max_len=MAX_L, max_long_batch=None):
     """pack -> per pack: pad, embed (and encode the regions), chart forward, `per_pack(indices, lengths_on_device)`.  outside False:
-    the inside pass alone through the module's ordinary forward; True: both passes through cliora_chart_forward_ragged.  max_len: the
-    longest sentence taken (64, or up to 128 for the inside pass alone); a longer one is refused before any pack has run."""
+    the inside pass alone through the module's ordinary forward; True: both passes through cliora_chart_forward_ragged (a pack of
+    L > 64: cliora_chart_forward_ragged_wide).  max_len: the longest sentence taken (64, or up to 128); a longer one is refused before
+    any pack has run.  max_long_batch: ``pack``'s."""
     diora = net.diora
     vl = _check_module(net, obj_feats)
     lengths = [len(s) for s in sentences]
@@ -212,10 +229,10 @@ def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats
     if vl and len(obj_feats) != len(sentences):
         raise ValueError('obj_feats holds %d sentences, not %d' % (len(obj_feats), len(sentences)))
     dev = next(net.parameters()).device
-    if not 1 <= int(max_len) <= (MAX_L if outside else MAX_L_INSIDE):
-        raise ValueError('max_len must be in 1..%d' % (MAX_L if outside else MAX_L_INSIDE))
+    if not 1 <= int(max_len) <= MAX_L_INSIDE:
+        raise ValueError('max_len must be in 1..%d' % MAX_L_INSIDE)
     if max(lengths) > max_len:       # before any pack has run
-        if outside:
+        if outside and max_len == MAX_L:
             raise _lib.ChartLibError('L > %d is not supported by the both-pass padded chart (its root-level mask holds %d levels; got a '
                                      'sentence of %d words): run longer sentences through the uniform-length entry points'
                                      % (MAX_L, MAX_L, max(lengths)))
@@ -227,7 +244,7 @@ def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats
     diora.outside = bool(outside)
     try:
         with torch.no_grad():
-            for idx in pack(lengths, max_batch, max_waste):
+            for idx in pack(lengths, max_batch, max_waste, max_long_batch):
                 tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
                 x_span, x_word = net.embed(tokens.to(dev))
                 o_span = o_word = None
@@ -235,7 +252,7 @@ def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats
                     o_span, o_word = net.img_encoder(obj_feats[torch.as_tensor(idx, dtype=torch.int64)].to(dev))
                 lens = lens.to(dev)
                 if outside:
-                    diora.__dict__['_ragged'] = (lens, root_level_mask(lengths[i] for i in idx))
+                    diora.__dict__['_ragged'] = (lens, root_level_mask((lengths[i] for i in idx), max_len))
                 try:
                     diora(x_span, x_word, o_span, o_word)
                 finally:
@@ -246,8 +263,11 @@ def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats
         net.train(was_training)
 
 
-def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0):
-    """Both passes over sentences of any lengths in 1..64: packs them (``pack``), runs each pack as one right-padded chart through
+def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, max_len=MAX_L,
+                   max_long_batch=DEFAULT_MAX_LONG_BATCH):
+    """Both passes over sentences of any lengths in 1..max_len (64; up to 128 when asked for: a pack whose longest sentence has more
+    than 64 words runs on a forward-only plan through cliora_chart_forward_ragged_wide and, with max_len > 64, holds at most
+    `max_long_batch` sentences): packs them (``pack``), runs each pack as one right-padded chart through
     cliora_chart_forward_ragged in eval mode under no_grad, and calls ``per_pack(indices, lengths, diora)`` after each -- `indices`
     the pack's positions in `sentences`, `lengths` their int32 lengths on the device, `diora` the chart module holding the pack's
     state: the four charts, valid on each sentence's own triangle (cells beyond it are unspecified), and for a CLIORA net
@@ -261,7 +281,8 @@ def forward_ragged(net, sentences, obj_feats=None, per_pack=None, max_batch=64, 
         if per_pack is not None:
             per_pack(idx, lens, net.diora)
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, each, obj_feats=obj_feats, outside=True)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, each, obj_feats=obj_feats, outside=True, max_len=max_len,
+               max_long_batch=max_long_batch if int(max_len) > MAX_L else None)
     return packs
 
 
@@ -357,13 +378,15 @@ def decode_spans_ragged(diora, lengths, decode='viterbi', out=None):
     return post.spans, post.status, entry
 
 
-def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L, decode='viterbi'):
+def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L, decode='viterbi',
+                 max_long_batch=None):
     """Best binary tree of every sentence (nested tuples of word positions as ``DioraBase.cky()``; 0 for a single word), in the
     caller's order.  net: a harness.Net; sentences: sequences of token ids of any lengths in 1..max_len (64; up to 128 when asked for:
     a pack whose longest sentence has more than 64 words runs on a forward-only plan); obj_feats: the region features
     (N, R, img_dim) of a CLIORA net, one row per sentence.  Runs in eval mode under no_grad with the outside pass off (both restored
     afterwards; the module's chart is left as the last pack's, outside_h unwritten).  One device-to-host copy per pack.
-    decode: 'viterbi' (the reference's tree) or 'mbr' (the tree with the most expected correct brackets, cliora_amd.posterior)."""
+    decode: 'viterbi' (the reference's tree) or 'mbr' (the tree with the most expected correct brackets, cliora_amd.posterior).
+    max_long_batch: ``pack``'s cap on a pack topped by a sentence of more than 64 words (None: none)."""
     diora = net.diora
     trees = [None] * len(sentences)
     decode_entry(decode)                             # a bad name is refused before any pack has run
@@ -378,7 +401,7 @@ def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_
         for b, i in enumerate(idx):
             trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len, max_long_batch=max_long_batch)
     return trees
 
 
@@ -473,9 +496,9 @@ def parse_ragged_constrained(net, sentences, required, forbidden=None, max_batch
     return out
 
 
-def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L):
+def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None, max_len=MAX_L, max_long_batch=None):
     """(N, D) fp32 on the device: row i = inside_h of sentence i's root cell (its own length's root, not the padded chart's), the
-    vector DIORA users read off the root.  Same plumbing as parse_ragged, max_len included."""
+    vector DIORA users read off the root.  Same plumbing as parse_ragged, max_len and max_long_batch included."""
     diora = net.diora
     dev = next(net.parameters()).device
     out = torch.empty((len(sentences), diora.size), dtype=torch.float32, device=dev)
@@ -483,5 +506,5 @@ def encode_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad
     def gather(idx, lens):
         out[torch.tensor(idx, dtype=torch.int64, device=dev)] = root_rows(diora, lens)
 
-    _run_packs(net, sentences, max_batch, max_waste, pad_id, gather, obj_feats=obj_feats, max_len=max_len)
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, gather, obj_feats=obj_feats, max_len=max_len, max_long_batch=max_long_batch)
     return out

@@ -90,8 +90,8 @@ typedef struct cliora_params {
  * refused with CLIORA_EINVAL and a message that says why, before any launch:
  *   cliora_chart_forward without CLIORA_FWD_NO_BACKWARD, with CLIORA_FWD_PAIR_STATES, or with params->root_mat (compress);
  *   cliora_chart_forward while cliora_set_resident(1) / CLIORA_RESIDENT=1 forces the sentence-resident kernels on a plan they would
- *   otherwise take (text-only, D <= 64); cliora_chart_backward; cliora_chart_forward_ragged (its root-level mask holds 64 levels);
- *   cliora_plan_create_ex with arch = 1.  cliora_cky_decode, cliora_cky_spans, cliora_cky_spans_ragged, cliora_ground_eval(_ragged),
+ *   otherwise take (text-only, D <= 64); cliora_chart_backward; cliora_chart_forward_ragged (its root-level mask holds 64 levels:
+ *   cliora_chart_forward_ragged_wide runs a long plan) and the four ragged training entries; cliora_plan_create_ex with arch = 1.  cliora_cky_decode, cliora_cky_spans, cliora_cky_spans_ragged, cliora_ground_eval(_ragged),
  *   cliora_phrase_gather and the cliora_vl_scores_* forward entries take L <= 128.  L > 128 is refused at plan creation. */
 int cliora_plan_create(int B, int L, int D, int share, int normalize, int R, cliora_plan** out);
 /* arch: 0 = DioraMLP (as above), 1 = DioraTreeLSTM (text-only: R = 0) */
@@ -541,6 +541,20 @@ int cliora_chart_forward_ragged(cliora_plan* plan, const cliora_params* params, 
                                 const float* drop_mask, float* inside_h, float* inside_s, float* outside_h, float* outside_s,
                                 float* inside_c, void* fwd_workspace, size_t fwd_workspace_bytes, int run_outside,
                                 const int32_t* lengths, uint64_t root_levels, int32_t* status, void* stream);
+/* The call above for every DioraMLP / CLIORA plan of L <= 128, LONG plans (64 < L <= 128) included: the same
+ * arguments, the same schedule and the same contract, except that root_levels points at TWO words in host memory (read during the
+ * call): bit t & 63 of word t >> 6 is set iff some sentence has lengths[b] - 1 == t.  On a long plan the level launches are the long
+ * plan's (two splits per lane in the score + softmax kernels); the mask and seed kernels are the same.  On a plan of L <= 64 the
+ * launches, and so the bits of every output, are those of cliora_chart_forward_ragged given word 0.  With every length equal to L the
+ * charts are bitwise those of cliora_chart_forward on the sequential schedule at any L.
+ * Refused with CLIORA_EINVAL and a message that starts with the entry's name, each before any HIP call: a NULL plan, params, lengths,
+ * root_levels or status; a TreeLSTM plan; run_outside without CLIORA_FWD_NO_BACKWARD or with CLIORA_FWD_PAIR_STATES; params->root_mat
+ * (compress); a drop_mask; a bit of root_levels set at or above L (bit L - 1, the chart's own root, is legal and ignored); on a long
+ * plan, cliora_set_resident(1) / CLIORA_RESIDENT=1 forcing the sentence-resident kernels on a plan they would otherwise take. */
+int cliora_chart_forward_ragged_wide(cliora_plan* plan, const cliora_params* params, const float* x_span, const float* obj_span,
+                                     const float* drop_mask, float* inside_h, float* inside_s, float* outside_h, float* outside_s,
+                                     float* inside_c, void* fwd_workspace, size_t fwd_workspace_bytes, int run_outside,
+                                     const int32_t* lengths, const uint64_t* root_levels, int32_t* status, void* stream);
 
 /* TRAINING through such a padded chart, text-only DIORA.  cliora_chart_forward_ragged_train: the call above,
  * same schedule, same status word, same charts, with the state the backward needs written -- run_outside WITHOUT
