@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import ptr, stream
-from .diora import DioraBase, ComposeMLP, Bilinear, ChartFunction, RaggedChartFunction, _cont
+from .diora import DioraBase, ComposeMLP, Bilinear, _cont
 
 DROPOUT_P = 0.1   # AttentionHead: nn.Dropout(0.1), cliora.py:32
 
@@ -276,14 +276,8 @@ class DioraMLP(DioraBase):
             mask = F.dropout(torch.ones((plan.B, plan.C, plan.R), device=dev), DROPOUT_P, True)
         return mask
 
-    def _run_chart(self, plan, holder, flags, x_span, obj_embed_span, params):
-        return ChartFunction.apply(plan, holder, flags, x_span, obj_embed_span, self._drop_mask(plan, x_span.device), *params) + (None,)
-
-    def _run_ragged_train(self, plan, holder, x_span, obj_embed_span, params, ragged):
-        """A padded chart of mixed lengths with a backward: the mask's rows are those of the PADDED chart."""
-        *charts, self.__dict__['_ragged_status'], inside_c = RaggedChartFunction.apply(
-            plan, holder, int(bool(self.outside)), *ragged, x_span, obj_embed_span, self._drop_mask(plan, x_span.device), *params)
-        return (*charts, inside_c, None)
+    def _chart_inputs(self, plan, x_span, obj_embed_span):
+        return obj_embed_span, self._drop_mask(plan, x_span.device)
 
     def forward(self, x_span, x_word, obj_embed_span=None, obj_embed_word=None):
         super().forward(x_span, x_word, obj_embed_span, obj_embed_word)

@@ -85,18 +85,19 @@ int cliora_ensure_max_lds(const void* fn);
 // uploads the plan's index tables on first use (current device) and checks that later calls run on that device
 int cliora_plan_ready(cliora_plan* plan, hipStream_t st);
 
-// The ragged forward entries' extra arguments (api_ragged.hip), handed to the forward's body (api_mlp.hip: FwdSchedule::Ragged,
-// forward_ragged).  root_levels: bit t & 63 of word t >> 6 is set iff some sentence has n - 1 == t; the entries that take the mask as
-// one word by value fill word 1 with 0.  wide: cliora_chart_forward_ragged_wide, the one entry a long plan (64 < L <= 128) is run by.
+// The ragged forward entries' extra arguments (api_ragged.hip: ragged_forward), handed to the forward's body (api_mlp.hip:
+// FwdSchedule::Ragged, forward_ragged).  root_levels: bit t & 63 of word t >> 6 is set iff some sentence has n - 1 == t; the entries
+// that take the mask as one word by value fill word 1 with 0.  A long plan (64 < L <= 128) gets here through
+// cliora_chart_forward_ragged_wide alone: every other entry has refused it under its own name (api_ragged.hip: ragged_refusals).
 struct RaggedFwd {
-    const int32_t* lengths; uint64_t root_levels[2]; int32_t* status; bool wide;
+    const int32_t* lengths; uint64_t root_levels[2]; int32_t* status;
     bool root_level(int t) const { return (root_levels[t >> 6] >> (t & 63)) & 1; }
 };
 int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span, const float* drop_mask,
                              float* inside_h, float* inside_s, float* outside_h, float* outside_s, float* inside_c, void* fwd_ws,
                              size_t fwd_ws_bytes, int run_outside, void* stream, const RaggedFwd* rg);
 
-// cliora_chart_backward_ragged's extra arguments (api_ragged.hip), handed to the backward's body (api_mlp.hip: BwdCall): the caller's
+// The ragged backward entries' extra arguments (api_ragged.hip: ragged_backward), handed to the backward's body (api_mlp.hip: BwdCall): the caller's
 // four chart cotangents (inside_h, inside_s, outside_h, outside_s; NULL = zero) and the buffers their masked copies go to
 struct RaggedBwd { const int32_t* lengths; uint64_t root_levels; const float* cot[4]; float* masked[4]; };
 int cliora_chart_backward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span, const float* drop_mask,

@@ -537,7 +537,7 @@ struct FwdCall {
 };
 
 // The body of cliora_chart_forward.  rg == nullptr: that entry, launch for launch.  rg != nullptr: a ragged forward entry
-// (api_ragged.hip, which has checked its own refusals) -- FwdSchedule::Ragged; on a long plan only cliora_chart_forward_ragged_wide's.
+// (api_ragged.hip, which has checked its own refusals, a long plan's among them) -- FwdSchedule::Ragged.
 int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
                              const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
                              float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
@@ -563,7 +563,6 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
         if (run_outside & CLIORA_FWD_PAIR_STATES)
             return fail(CLIORA_EINVAL, "L > 64: CLIORA_FWD_PAIR_STATES is not supported (a long plan sizes no per-pair rows)");
         if (compress) return fail(CLIORA_EINVAL, "L > 64: compress (root_mat) is not supported");
-        if (rg && !rg->wide) return fail(CLIORA_EINVAL, "cliora_chart_forward_ragged: L > 64 is not supported (the root-level mask holds 64 levels)");
         if (g_cliora_resident == 1 && !vl && p.Dp <= 64)
             return fail(CLIORA_EINVAL, "L > 64: the sentence-resident kernels are not supported (cliora_set_resident / CLIORA_RESIDENT forces them on)");
     }

@@ -64,6 +64,16 @@ def _cont(g):
     return g.contiguous().float() if g is not None else None
 
 
+def host_copy(*tensors):
+    """The int32 / fp32 tensors of one device as numpy arrays of their own dtypes and shapes, after ONE device-to-host copy: they
+    travel concatenated, as 32-bit words."""
+    host = torch.cat([t.reshape(-1).view(torch.int32) for t in tensors]).cpu().numpy()
+    ends = [0]
+    for t in tensors:
+        ends.append(ends[-1] + t.numel())
+    return [host[a:b].view(str(t.dtype)[len('torch.'):]).reshape(t.shape) for t, a, b in zip(tensors, ends, ends[1:])]
+
+
 class ChartWorkspaces(list):
     """The holder of a forward's workspace(s), made anew by every forward of a chart module, with the slot through which
     cliora_amd.structured hands the chart node a cotangent on the inside split scores: `split_cot` is a one-element list that the
@@ -76,6 +86,66 @@ class ChartWorkspaces(list):
         super().__init__()
         self.split_cot = [None]
         self.lengths = None
+
+
+def check_lengths(lengths, B, dev):
+    """The lengths of a padded chart's sentences as the C entries take them: int32, (B,), on the chart's device."""
+    if lengths.dtype != torch.int32 or lengths.numel() != B or lengths.device != dev:
+        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (B, dev))
+    return lengths.contiguous()
+
+
+def _chart_forward(entry, plan, flags, x_span, obj_span, drop_mask, params, lengths=None, root_levels=None):
+    """The call of a chart forward entry, for every route: the inputs made contiguous fp32, the parameters detached, the outputs and
+    the workspace allocated (chart_buffers), inside_c zeroed for a plan with regions, then `entry` under the tensors' device.  With
+    `lengths` (a padded chart of mixed lengths) the entry also gets them, `root_levels` as the entry takes it and a fresh status
+    word.  -> (x_span, lengths, obj_span, drop_mask, ptens, the four charts, inside_c or None, workspace, status or None)."""
+    if not x_span.is_cuda:
+        raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
+    D, dev, vl, status, tail = plan.D, x_span.device, obj_span is not None, None, ()
+    if lengths is not None:
+        lengths = check_lengths(lengths, plan.B, dev)
+    x_span, obj_span, drop_mask = x_span.contiguous().float(), _cont(obj_span), _cont(drop_mask)
+    ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
+    with _lib.device_guard(x_span):
+        outs, ws, nbytes = chart_buffers(plan, dev, flags, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
+        inside_c = outs.pop().zero_() if vl else None
+        if lengths is not None:
+            status = torch.empty(1, device=dev, dtype=torch.int32)
+            tail = (_ptr(lengths), root_levels, _ptr(status))
+        pst = _param_struct(ptens)
+        _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask), *map(_ptr, outs), _ptr(inside_c),
+                  _ptr(ws), nbytes, flags, *tail, _stream())
+    return x_span, lengths, obj_span, drop_mask, ptens, outs, inside_c, ws, status
+
+
+def _chart_backward(ctx, x_span, obj_span, charts, cots, lengths=None):
+    """The call of a chart backward entry for the node `ctx`: the gradient outputs and the workspace allocated, the split cotangent of
+    a structured loss of the same forward taken (once), then cliora_chart_backward -- cliora_chart_backward_split when there is a split
+    cotangent -- or, with `lengths`, cliora_chart_backward_ragged[_vl], which masks the cotangents into buffers of their own.
+    -> (d_x, d_obj or None, the parameters' gradients in _lib.PARAM_FIELDS order)."""
+    plan = ctx.plan
+    with _lib.device_guard(x_span):
+        d_x = torch.empty_like(x_span)
+        d_obj = torch.empty_like(obj_span) if ctx.vl else None
+        pst = _param_struct(ctx.ptens)
+        g = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
+        wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
+        gst = _param_struct(g)
+        d_split = ctx.split_cot[0] if ctx.split_cot is not None else None
+        if d_split is not None:
+            ctx.split_cot[0] = None                       # a bracket loss of this forward left it: taken once
+        cots = [_cont(d) for d in cots]
+        if lengths is None:
+            entry, split, tail = 'cliora_chart_backward' + ('_split' if d_split is not None else ''), d_split is not None, ()
+        else:
+            masked = [torch.empty_like(d) if d is not None else None for d in cots]      # the library masks the cotangents into these
+            entry, split = 'cliora_chart_backward_ragged' + ('_vl' if ctx.vl else ''), True
+            tail = (_ptr(lengths), ctx.root_levels, *map(_ptr, masked))
+        _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask), *map(_ptr, charts),
+                  *map(_ptr, cots), *((_ptr(d_split),) if split else ()), _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x),
+                  _ptr(d_obj), C.byref(gst), ctx.run_outside, *tail, _stream())
+    return d_x, d_obj, tuple(g[n] for n in _lib.PARAM_FIELDS)
 
 
 class ChartFunction(torch.autograd.Function):
@@ -92,17 +162,9 @@ class ChartFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, holder, run_outside, x_span, obj_span, drop_mask, *params):
-        if not x_span.is_cuda:
-            raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-        D, run_outside, vl = plan.D, int(run_outside), obj_span is not None
-        x_span, obj_span, drop_mask = x_span.contiguous().float(), _cont(obj_span), _cont(drop_mask)
-        ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
-        with _lib.device_guard(x_span):
-            outs, ws, nbytes = chart_buffers(plan, x_span.device, run_outside, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
-            inside_c = outs.pop().zero_() if vl else None
-            pst = _param_struct(ptens)
-            _lib.call('cliora_chart_forward', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask),
-                      *map(_ptr, outs), _ptr(inside_c), _ptr(ws), nbytes, run_outside, _stream())
+        run_outside, vl = int(run_outside), obj_span is not None
+        x_span, _, obj_span, drop_mask, ptens, outs, inside_c, ws, _ = _chart_forward('cliora_chart_forward', plan, run_outside, x_span,
+                                                                                     obj_span, drop_mask, params)
         ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.drop_mask, ctx.vl = plan, run_outside & 1, ws, ptens, drop_mask, vl
         ctx.split_cot = getattr(holder, 'split_cot', None)      # cliora_amd.structured leaves d_split there (a plain list: no such input)
         ctx.save_for_backward(x_span, *((obj_span,) if vl else ()), *outs)
@@ -115,33 +177,9 @@ class ChartFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_ih, d_is, d_oh, d_os, _d_ic):
-        plan, saved = ctx.plan, ctx.saved_tensors
-        x_span, obj_span = saved[0], (saved[1] if ctx.vl else None)
-        with _lib.device_guard(x_span):
-            d_x = torch.empty_like(x_span)
-            d_obj = torch.empty_like(obj_span) if ctx.vl else None
-            pst = _param_struct(ctx.ptens)
-            g = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
-            wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
-            gst = _param_struct(g)
-            d_split = ctx.split_cot[0] if ctx.split_cot is not None else None
-            if d_split is None:
-                _lib.call('cliora_chart_backward', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask),
-                          *map(_ptr, saved[-4:]), *[_ptr(_cont(d)) for d in (d_ih, d_is, d_oh, d_os)],
-                          _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst),
-                          ctx.run_outside, _stream())
-            else:                                         # a bracket loss of this forward left a cotangent on the split scores: taken once
-                ctx.split_cot[0] = None
-                _lib.call('cliora_chart_backward_split', plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(ctx.drop_mask),
-                          *map(_ptr, saved[-4:]), *[_ptr(_cont(d)) for d in (d_ih, d_is, d_oh, d_os)], _ptr(d_split),
-                          _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb), plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst),
-                          ctx.run_outside, _stream())
-        return (None, None, None, d_x, d_obj, None) + tuple(g[n] for n in _lib.PARAM_FIELDS)
-
-
-def _check_lengths(plan, lengths, dev):
-    if lengths.dtype != torch.int32 or lengths.numel() != plan.B or lengths.device != dev:
-        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (plan.B, dev))
+        saved = ctx.saved_tensors
+        d_x, d_obj, grads = _chart_backward(ctx, saved[0], saved[1] if ctx.vl else None, saved[-4:], (d_ih, d_is, d_oh, d_os))
+        return (None, None, None, d_x, d_obj, None) + grads
 
 
 class RaggedChartFunction(torch.autograd.Function):
@@ -158,20 +196,10 @@ class RaggedChartFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, holder, run_outside, lengths, root_levels, x_span, obj_span, drop_mask, *params):
-        if not x_span.is_cuda:
-            raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-        D, run_outside, dev, vl = plan.D, int(run_outside), x_span.device, obj_span is not None
-        _check_lengths(plan, lengths, dev)
-        x_span, lengths, obj_span, drop_mask = x_span.contiguous().float(), lengths.contiguous(), _cont(obj_span), _cont(drop_mask)
-        ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
-        with _lib.device_guard(x_span):
-            outs, ws, nbytes = chart_buffers(plan, dev, run_outside, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
-            inside_c = outs.pop().zero_() if vl else None
-            status = torch.empty(1, device=dev, dtype=torch.int32)
-            pst = _param_struct(ptens)
-            _lib.call('cliora_chart_forward_ragged_train' + ('_vl' if vl else ''), plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span),
-                      _ptr(drop_mask), *map(_ptr, outs), _ptr(inside_c), _ptr(ws), nbytes, run_outside, _ptr(lengths), int(root_levels),
-                      _ptr(status), _stream())
+        run_outside, vl = int(run_outside), obj_span is not None
+        x_span, lengths, obj_span, drop_mask, ptens, outs, inside_c, ws, status = _chart_forward(
+            'cliora_chart_forward_ragged_train' + ('_vl' if vl else ''), plan, run_outside, x_span, obj_span, drop_mask, params, lengths,
+            int(root_levels))
         ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.root_levels = plan, run_outside & 1, ws, ptens, int(root_levels)
         ctx.drop_mask, ctx.vl = drop_mask, vl
         ctx.split_cot = getattr(holder, 'split_cot', None)
@@ -185,25 +213,9 @@ class RaggedChartFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_ih, d_is, d_oh, d_os, _d_status, _d_ic):
-        plan, saved = ctx.plan, ctx.saved_tensors
-        x_span, lengths, obj_span = saved[0], saved[1], (saved[2] if ctx.vl else None)
-        with _lib.device_guard(x_span):
-            d_x = torch.empty_like(x_span)
-            d_obj = torch.empty_like(obj_span) if ctx.vl else None
-            pst = _param_struct(ctx.ptens)
-            g = {n: (_grad_out(t) if t is not None else None) for n, t in ctx.ptens.items()}
-            wsb = torch.empty(plan.bwd_bytes, device=x_span.device, dtype=torch.uint8)
-            gst = _param_struct(g)
-            d_split = ctx.split_cot[0] if ctx.split_cot is not None else None
-            if d_split is not None:
-                ctx.split_cot[0] = None                       # taken once
-            cots = [_cont(d) for d in (d_ih, d_is, d_oh, d_os)]
-            masked = [torch.empty_like(d) if d is not None else None for d in cots]      # the library masks the cotangents into these
-            _lib.call('cliora_chart_backward_ragged' + ('_vl' if ctx.vl else ''), plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span),
-                      _ptr(ctx.drop_mask), *map(_ptr, saved[-4:]), *map(_ptr, cots), _ptr(d_split), _ptr(ctx.ws), plan.fwd_bytes, _ptr(wsb),
-                      plan.bwd_bytes, _ptr(d_x), _ptr(d_obj), C.byref(gst), ctx.run_outside, _ptr(lengths), ctx.root_levels,
-                      *map(_ptr, masked), _stream())
-        return (None, None, None, None, None, d_x, d_obj, None) + tuple(g[n] for n in _lib.PARAM_FIELDS)
+        saved = ctx.saved_tensors
+        d_x, d_obj, grads = _chart_backward(ctx, saved[0], saved[2] if ctx.vl else None, saved[-4:], (d_ih, d_is, d_oh, d_os), saved[1])
+        return (None, None, None, None, None, d_x, d_obj, None) + grads
 
 
 def split_root_levels(mask):
@@ -219,27 +231,14 @@ def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_
     through cliora_chart_forward_ragged_wide, which takes the mask as two 64-bit words; a short plan through the entry it always ran
     through.  -> inside_h, inside_s, outside_h, outside_s, inside_c (None for a text-only plan), status (1,) int32 on the device,
     which the caller must read."""
-    if not x_span.is_cuda:
-        raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
-    D, dev, vl = plan.D, x_span.device, obj_span is not None
-    _check_lengths(plan, lengths, dev)
-    x_span, obj_span = x_span.detach().contiguous().float(), _cont(obj_span.detach() if vl else None)
-    lengths = lengths.contiguous()
-    ptens = {n: (p.detach().contiguous() if p is not None else None) for n, p in zip(_lib.PARAM_FIELDS, params)}
-    wide = plan.L > _lib.MAX_L
     entry, mask = 'cliora_chart_forward_ragged', int(root_levels)
-    if wide:
+    if plan.L > _lib.MAX_L:
         if mask < 0 or mask >> _lib.MAX_L_FWD:
             raise ValueError('root_levels holds a bit at or above %d' % _lib.MAX_L_FWD)
         entry, mask = 'cliora_chart_forward_ragged_wide', split_root_levels(mask)
-    with _lib.device_guard(x_span):
-        outs, ws, nbytes = chart_buffers(plan, dev, 0, *((D, 1, D, 1, D) if vl else (D, 1, D, 1)))
-        inside_c = outs.pop().zero_() if vl else None
-        status = torch.empty(1, device=dev, dtype=torch.int32)
-        pst = _param_struct(ptens)
-        _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), None, *map(_ptr, outs),
-                  _ptr(inside_c), _ptr(ws), nbytes, int(bool(outside)) | _lib.FWD_NO_BACKWARD, _ptr(lengths), mask,
-                  _ptr(status), _stream())
+    _, _, _, _, _, outs, inside_c, ws, status = _chart_forward(entry, plan, int(bool(outside)) | _lib.FWD_NO_BACKWARD, x_span.detach(),
+                                                               obj_span.detach() if obj_span is not None else None, None, params, lengths,
+                                                               mask)
     holder.clear()
     holder.append(ws)
     return (*outs, inside_c, status)
@@ -388,13 +387,17 @@ class DioraBase(nn.Module):
         if self.compress:
             raise _lib.ChartLibError('L = %d > %d: compress = True is not supported' % (L, _lib.MAX_L))
 
-    def _check_ragged(self, needs_grad, hooks):
-        if needs_grad or self.training:
-            raise _lib.ChartLibError('a padded chart of mixed lengths is inference only: call it in eval mode under torch.no_grad()')
+    def _check_padded(self, hooks):
+        """What no padded chart of mixed lengths takes, for inference or with a backward."""
         if hooks:
             raise NotImplementedError('inside_hook / outside_hook overrides get no per-pair states from a padded chart of mixed lengths')
         if self.compress:
             raise NotImplementedError('compress = True is not supported on a padded chart of mixed lengths')
+
+    def _check_ragged(self, needs_grad, hooks):
+        if needs_grad or self.training:
+            raise _lib.ChartLibError('a padded chart of mixed lengths is inference only: call it in eval mode under torch.no_grad()')
+        self._check_padded(hooks)
 
     def _check_ragged_train(self, L, hooks):
         """A padded chart of mixed lengths with a backward: every refusal before any launch."""
@@ -403,16 +406,14 @@ class DioraBase(nn.Module):
                                       'or CLIORA (cliora_amd.cliora.DioraMLP), not the TreeLSTM')
         if L > _lib.MAX_L:
             raise _lib.ChartLibError('L = %d > %d: a padded chart of mixed lengths trains through at most %d words' % (L, _lib.MAX_L, _lib.MAX_L))
-        if hooks:
-            raise NotImplementedError('inside_hook / outside_hook overrides get no per-pair states from a padded chart of mixed lengths')
-        if self.compress:
-            raise NotImplementedError('compress = True is not supported on a padded chart of mixed lengths')
+        self._check_padded(hooks)
 
     def _run_ragged_train(self, plan, holder, x_span, obj_embed_span, params, ragged):
-        """_run_chart through RaggedChartFunction; the status word is left in _ragged_status."""
-        *charts, self.__dict__['_ragged_status'], _ = RaggedChartFunction.apply(plan, holder, int(bool(self.outside)), *ragged, x_span, None,
-                                                                                None, *params)
-        return (*charts, None, None)
+        """_run_chart through RaggedChartFunction (with regions, DESIGN.md section 23: the mask's rows are those of the PADDED chart);
+        the status word is left in _ragged_status."""
+        *charts, self.__dict__['_ragged_status'], inside_c = RaggedChartFunction.apply(
+            plan, holder, int(bool(self.outside)), *ragged, x_span, *self._chart_inputs(plan, x_span, obj_embed_span), *params)
+        return (*charts, inside_c, None)
 
     def _hook_overridden(self, name):
         return name in self.__dict__ or getattr(type(self), name) is not getattr(DioraBase, name)
@@ -445,14 +446,19 @@ class DioraBase(nn.Module):
             raise NotImplementedError('text-only DIORA module; use cliora_amd.cliora.DioraMLP with image regions')
         return 0
 
+    def _chart_inputs(self, plan, x_span, obj_embed_span):
+        """(obj_span, drop_mask) of this module's kind of chart call, on every route: none here (_regions has refused the regions)."""
+        return None, None
+
     def _run_chart(self, plan, holder, flags, x_span, obj_embed_span, params):
         """The one call that runs the chart -> (inside_h, inside_s, outside_h, outside_s, inside_c, outside_c); a cell state None is
         identically zero (Chart creates it when first read)."""
-        return ChartFunction.apply(plan, holder, flags, x_span, None, None, *params) + (None,)
+        return ChartFunction.apply(plan, holder, flags, x_span, *self._chart_inputs(plan, x_span, obj_embed_span), *params) + (None,)
 
     def _run_ragged(self, plan, holder, x_span, obj_embed_span, params, ragged):
         """_run_chart through cliora_chart_forward_ragged (cliora_amd.ragged); the status word is left in _ragged_status."""
-        *charts, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, obj_embed_span, params, *ragged)
+        obj_span, _ = self._chart_inputs(plan, x_span, obj_embed_span)      # eval mode (_check_ragged): no dropout mask
+        *charts, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, obj_span, params, *ragged)
         return (*charts, None)
 
     def forward(self, x_span, x_word=None, obj_embed_span=None, obj_embed_word=None):
@@ -630,11 +636,7 @@ class DioraBase(nn.Module):
         """Per sentence the list of its (tree, score), best first: min(k, Catalan(L - 1)) nested tuples of word positions as cky()
         returns them, each with the sum of its potentials (<= 0; exp(score - log_z) is the tree's posterior mass)."""
         kb = self.kbest_spans_device(k)
-        nsp = kb.spans.numel()
-        host = torch.cat([kb.spans.reshape(-1), kb.scores.view(torch.int32).reshape(-1), kb.count]).cpu().numpy()    # one copy
-        spans = host[:nsp].reshape(kb.spans.shape)
-        scores = host[nsp:nsp + kb.scores.numel()].view('float32').reshape(kb.scores.shape)
-        count = host[nsp + kb.scores.numel():]
+        spans, scores, count = host_copy(kb.spans, kb.scores, kb.count)
         return [list(zip(self.trees_from_spans(spans[b, :count[b]]), scores[b, :count[b]].tolist())) for b in range(len(count))]
 
     def sample_spans_device(self, S, seed, lengths=None, ids=None, first_sample=0, beta=1.0):
@@ -648,10 +650,7 @@ class DioraBase(nn.Module):
         """Per sentence the list of its S sampled (tree, log_prob): nested tuples of word positions as cky() returns them, each with
         the log of its probability under the distribution it was drawn from.  One device-to-host copy."""
         ts = self.sample_spans_device(S, seed, beta=beta)
-        nsp = ts.spans.numel()
-        host = torch.cat([ts.spans.reshape(-1), ts.log_prob.view(torch.int32).reshape(-1)]).cpu().numpy()    # one copy
-        spans = host[:nsp].reshape(ts.spans.shape)
-        log_prob = host[nsp:].view('float32').reshape(ts.log_prob.shape)
+        spans, log_prob = host_copy(ts.spans, ts.log_prob)
         return [list(zip(self.trees_from_spans(spans[b]), log_prob[b].tolist())) for b in range(spans.shape[0])]
 
     def cky_constrained(self, required, forbidden=None):
@@ -670,11 +669,9 @@ class DioraBase(nn.Module):
         floats <= 0, -inf where no tree qualifies.  One device-to-host copy."""
         from . import constrained
         cp = constrained.constrained_parse(self, constrained.pack_brackets(required, forbidden))
-        host = torch.cat([cp.log_prob.view(torch.int32), cp.status]).cpu().numpy()
-        nb = cp.log_prob.numel()
-        constrained.refuse_rejected(int(host[nb:].sum()))
-        return host[:nb].view('float32').tolist()
-
+        log_prob, status = host_copy(cp.log_prob, cp.status)
+        constrained.refuse_rejected(int(status.sum()))
+        return log_prob.tolist()
 
     def bracket_nll(self, required, forbidden=None, reduction='mean'):
         """The loss -log_prob of the brackets, in the autograd graph of the last forward (cliora_amd.structured.bracket_nll; DESIGN.md

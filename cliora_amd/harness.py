@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import heads
-from .diora import DioraMLP as TextDiora
+from .diora import DioraMLP as TextDiora, check_lengths      # check_lengths: also imported from here (harness.check_lengths)
 from .cliora import DioraMLP as VLDiora
 
 NATIVE_HEADS = True        # False: the torch formulas everywhere (A/B and tests)
@@ -156,13 +156,6 @@ class FusedContrastive(torch.autograd.Function):
 
 
 RAGGED_STATUS_BYTES = heads.RAGGED_STATUS_BYTES
-
-
-def check_lengths(lengths, B, dev):
-    """The lengths of a padded chart's sentences as the loss entries take them: int32, (B,), on the scores' device."""
-    if lengths.dtype != torch.int32 or lengths.numel() != B or lengths.device != dev:
-        raise ValueError('lengths must be an int32 tensor of %d sentences on %s' % (B, dev))
-    return lengths.contiguous()
 
 
 def triangle_masks(lengths, L):

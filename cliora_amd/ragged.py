@@ -42,7 +42,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr_or_null as _p, stream as _stream
-from .diora import span_buffer
+from .diora import host_copy, span_buffer
 
 MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L -- the default of max_len, the training charts, one word of the root-level mask
 MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_len may be raised to, for the inside-only and the both-pass entries
@@ -196,22 +196,71 @@ def root_level_mask(lengths, max_len=MAX_L):
     return m
 
 
-def _check_module(net, obj_feats):
+def _check_batch(net, sentences, obj_feats, max_len, kind):
+    """What every entry here checks before any pack runs: which module this is and whether it may have regions, the sentences, the
+    length limit.  kind: 'inside' (the inside pass alone), 'both' (both passes, inference) or 'train' (forward_ragged_train), which
+    picks the messages.  -> (the net has regions, the sentences' lengths)."""
     from .cliora import DioraMLP as VLDiora
     from .diora import DioraMLP as TextDiora
-    diora = net.diora
-    if isinstance(diora, VLDiora):
-        if obj_feats is None:
+    diora, train = net.diora, kind == 'train'
+    vl = isinstance(diora, VLDiora)
+    if (vl and obj_feats is None) or not (vl or isinstance(diora, TextDiora)):
+        if train:
+            raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP), got %s%s'
+                                      % (type(diora).__name__, ' without obj_feats' if vl else ''))
+        if vl:
             raise NotImplementedError(
                 'the vision-language module scores regions against inside_h + outside_h of every cell: pass the region features of '
                 'every sentence (obj_feats=) to run it on a padded chart')
-        return True
-    if not isinstance(diora, TextDiora):
         raise NotImplementedError('ragged batches need cliora_amd.diora.DioraMLP or cliora_amd.cliora.DioraMLP, got %s'
                                   % type(diora).__name__)
-    if obj_feats is not None:
+    if not vl and obj_feats is not None:
         raise ValueError('obj_feats given to a text-only net')
-    return False
+    if train and not torch.is_grad_enabled():
+        raise _lib.ChartLibError('forward_ragged_train needs gradients enabled; forward_ragged runs the same batch for inference')
+    lengths = [len(s) for s in sentences]
+    if not lengths:
+        return vl, lengths
+    if min(lengths) < 1:
+        raise ValueError('an empty sentence has no chart')
+    if vl and len(obj_feats) != len(sentences):
+        raise ValueError('obj_feats holds %d sentences, not %d' % (len(obj_feats), len(sentences)))
+    if not 1 <= int(max_len) <= MAX_L_INSIDE:
+        raise ValueError('max_len must be in 1..%d' % MAX_L_INSIDE)
+    if max(lengths) > max_len:
+        if train:
+            raise _lib.ChartLibError('L > %d is not supported by the padded training chart (got a sentence of %d words)' % (MAX_L, max(lengths)))
+        if kind == 'both' and max_len == MAX_L:
+            raise _lib.ChartLibError('L > %d is not supported by the both-pass padded chart (its root-level mask holds %d levels; got a '
+                                     'sentence of %d words): run longer sentences through the uniform-length entry points'
+                                     % (MAX_L, MAX_L, max(lengths)))
+        raise _lib.ChartLibError('L > %d is not supported (got a sentence of %d words)%s' % (
+            max_len, max(lengths), ': pass max_len=%d for sentences of up to %d words' % (MAX_L_INSIDE, MAX_L_INSIDE)
+            if max_len < MAX_L_INSIDE and max(lengths) <= MAX_L_INSIDE else ''))
+    return vl, lengths
+
+
+def _forward_packs(net, sentences, lengths, packs, pad_id, obj_feats, slot, max_len=MAX_L):
+    """The one loop over the packs, a generator: per pack pad, embed, encode the pack's regions (obj_feats, else None) and run the
+    chart module's forward -- with (lengths on the device, root-level mask) in the module's slot `slot` ('_ragged', '_ragged_train')
+    around it, cleared whatever happens; slot None: the module's ordinary forward -- then yield (indices, lengths on the device)."""
+    diora = net.diora
+    dev = next(net.parameters()).device
+    for idx in packs:
+        tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
+        x_span, x_word = net.embed(tokens.to(dev))
+        o_span = o_word = None
+        if obj_feats is not None:
+            o_span, o_word = net.img_encoder(obj_feats[torch.as_tensor(idx, dtype=torch.int64)].to(dev))
+        lens = lens.to(dev)
+        if slot is not None:
+            diora.__dict__[slot] = (lens, root_level_mask((lengths[i] for i in idx), max_len))
+        try:
+            diora(x_span, x_word, o_span, o_word)
+        finally:
+            if slot is not None:
+                diora.__dict__[slot] = None
+        yield idx, lens
 
 
 def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats=None, outside=False, max_len=MAX_L, max_long_batch=None):
@@ -220,43 +269,16 @@ def _run_packs(net, sentences, max_batch, max_waste, pad_id, per_pack, obj_feats
     L > 64: cliora_chart_forward_ragged_wide).  max_len: the longest sentence taken (64, or up to 128); a longer one is refused before
     any pack has run.  max_long_batch: ``pack``'s."""
     diora = net.diora
-    vl = _check_module(net, obj_feats)
-    lengths = [len(s) for s in sentences]
+    _, lengths = _check_batch(net, sentences, obj_feats, max_len, 'both' if outside else 'inside')
     if not lengths:
         return
-    if min(lengths) < 1:
-        raise ValueError('an empty sentence has no chart')
-    if vl and len(obj_feats) != len(sentences):
-        raise ValueError('obj_feats holds %d sentences, not %d' % (len(obj_feats), len(sentences)))
-    dev = next(net.parameters()).device
-    if not 1 <= int(max_len) <= MAX_L_INSIDE:
-        raise ValueError('max_len must be in 1..%d' % MAX_L_INSIDE)
-    if max(lengths) > max_len:       # before any pack has run
-        if outside and max_len == MAX_L:
-            raise _lib.ChartLibError('L > %d is not supported by the both-pass padded chart (its root-level mask holds %d levels; got a '
-                                     'sentence of %d words): run longer sentences through the uniform-length entry points'
-                                     % (MAX_L, MAX_L, max(lengths)))
-        raise _lib.ChartLibError('L > %d is not supported (got a sentence of %d words)%s' % (
-            max_len, max(lengths), ': pass max_len=%d for sentences of up to %d words' % (MAX_L_INSIDE, MAX_L_INSIDE)
-            if max_len < MAX_L_INSIDE and max(lengths) <= MAX_L_INSIDE else ''))
     was_training, had_outside = net.training, diora.outside
     net.eval()
     diora.outside = bool(outside)
     try:
         with torch.no_grad():
-            for idx in pack(lengths, max_batch, max_waste, max_long_batch):
-                tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
-                x_span, x_word = net.embed(tokens.to(dev))
-                o_span = o_word = None
-                if vl:
-                    o_span, o_word = net.img_encoder(obj_feats[torch.as_tensor(idx, dtype=torch.int64)].to(dev))
-                lens = lens.to(dev)
-                if outside:
-                    diora.__dict__['_ragged'] = (lens, root_level_mask((lengths[i] for i in idx), max_len))
-                try:
-                    diora(x_span, x_word, o_span, o_word)
-                finally:
-                    diora.__dict__['_ragged'] = None
+            for idx, lens in _forward_packs(net, sentences, lengths, pack(lengths, max_batch, max_waste, max_long_batch), pad_id, obj_feats,
+                                            '_ragged' if outside else None, max_len):
                 per_pack(idx, lens)
     finally:
         diora.outside = had_outside
@@ -296,39 +318,9 @@ def forward_ragged_train(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WAS
     the pack, to be read through the length-aware losses (harness.VGLoss / ContrastiveLoss with `lengths`).  The status word is read
     after each forward (one synchronisation per pack) and a rejected length raises.  The structured losses of the module
     (bracket_nll, tree_objective, ...) read each sentence's own triangle.  Gradients must be enabled; the net's mode is the caller's."""
-    from .cliora import DioraMLP as VLDiora
-    from .diora import DioraMLP as TextDiora
     diora = net.diora
-    vl = isinstance(diora, VLDiora) and obj_feats is not None
-    if not vl and (type(diora).vision_language or not isinstance(diora, TextDiora)):
-        raise NotImplementedError('training through a padded chart of mixed lengths is text-only DIORA (cliora_amd.diora.DioraMLP), got %s%s'
-                                  % (type(diora).__name__, ' without obj_feats' if isinstance(diora, VLDiora) else ''))
-    if not vl and obj_feats is not None:
-        raise ValueError('obj_feats given to a text-only net')
-    if not torch.is_grad_enabled():
-        raise _lib.ChartLibError('forward_ragged_train needs gradients enabled; forward_ragged runs the same batch for inference')
-    lengths = [len(s) for s in sentences]
-    if not lengths:
-        return
-    if min(lengths) < 1:
-        raise ValueError('an empty sentence has no chart')
-    if max(lengths) > MAX_L:             # before any pack has run
-        raise _lib.ChartLibError('L > %d is not supported by the padded training chart (got a sentence of %d words)' % (MAX_L, max(lengths)))
-    if vl and len(obj_feats) != len(sentences):
-        raise ValueError('obj_feats holds %d sentences, not %d' % (len(obj_feats), len(sentences)))
-    dev = next(net.parameters()).device
-    for idx in pack(lengths, max_batch, max_waste):
-        tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
-        x_span, x_word = net.embed(tokens.to(dev))
-        o_span = o_word = None
-        if vl:
-            o_span, o_word = net.img_encoder(obj_feats[torch.as_tensor(idx, dtype=torch.int64)].to(dev))
-        lens = lens.to(dev)
-        diora.__dict__['_ragged_train'] = (lens, root_level_mask(lengths[i] for i in idx))
-        try:
-            diora(x_span, x_word, o_span, o_word) if vl else diora(x_span, x_word)
-        finally:
-            diora.__dict__['_ragged_train'] = None
+    vl, lengths = _check_batch(net, sentences, obj_feats, MAX_L, 'train')
+    for idx, lens in _forward_packs(net, sentences, lengths, pack(lengths, max_batch, max_waste), pad_id, obj_feats, '_ragged_train'):
         bad = int(diora._ragged_status.item())
         if bad:
             raise _lib.ChartLibError('cliora_chart_forward_ragged_train%s rejected %d sentence length(s)' % ('_vl' if vl else '', bad))
@@ -393,11 +385,9 @@ def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_
 
     def decode_pack(idx, lens):
         spans, status, entry = decode_spans_ragged(diora, lens, decode)
-        nsp = spans.numel()
-        host = torch.cat([spans.reshape(-1), status]).cpu().numpy()         # the pack's one device-to-host copy
-        if host[nsp:].any():
-            raise _lib.ChartLibError('%s rejected %d sentence length(s)' % (entry, int(host[nsp:].sum())))
-        rows = host[:nsp].reshape(spans.shape)
+        rows, status = host_copy(spans, status)                             # the pack's one device-to-host copy
+        if status.any():
+            raise _lib.ChartLibError('%s rejected %d sentence length(s)' % (entry, int(status.sum())))
         for b, i in enumerate(idx):
             trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
 
@@ -419,13 +409,9 @@ def parse_ragged_kbest(net, sentences, k, max_batch=64, max_waste=DEFAULT_MAX_WA
 
     def decode_pack(idx, lens):
         kb = kbest.kbest_spans(diora, k, lens)
-        nsp, nsc = kb.spans.numel(), kb.scores.numel()
-        host = torch.cat([kb.spans.reshape(-1), kb.scores.view(torch.int32).reshape(-1), kb.count, kb.status]).cpu().numpy()
-        if host[nsp + nsc + kb.count.numel():].any():
-            raise _lib.ChartLibError('cliora_kbest_spans rejected %d sentence length(s)' % int(host[nsp + nsc + kb.count.numel():].sum()))
-        rows = host[:nsp].reshape(kb.spans.shape)
-        scores = host[nsp:nsp + nsc].view(np.float32).reshape(kb.scores.shape)
-        count = host[nsp + nsc:nsp + nsc + kb.count.numel()]
+        rows, scores, count, status = host_copy(kb.spans, kb.scores, kb.count, kb.status)
+        if status.any():
+            raise _lib.ChartLibError('cliora_kbest_spans rejected %d sentence length(s)' % int(status.sum()))
         for b, i in enumerate(idx):
             trees = diora.trees_from_spans(rows[b, :count[b], :len(sentences[i]) - 1])
             out[i] = list(zip(trees, scores[b, :count[b]].tolist()))
@@ -452,12 +438,9 @@ def parse_ragged_samples(net, sentences, S, seed, beta=1.0, max_batch=64, max_wa
 
     def decode_pack(idx, lens):
         ts = sample.sample_spans(diora, S, seed, lens, ids=torch.tensor(idx, dtype=torch.int32), beta=beta)
-        nsp, nlp = ts.spans.numel(), ts.log_prob.numel()
-        host = torch.cat([ts.spans.reshape(-1), ts.log_prob.view(torch.int32).reshape(-1), ts.status]).cpu().numpy()
-        if host[nsp + nlp:].any():
-            raise _lib.ChartLibError('cliora_sample_trees rejected %d sentence length(s)' % int(host[nsp + nlp:].sum()))
-        rows = host[:nsp].reshape(ts.spans.shape)
-        log_prob = host[nsp:nsp + nlp].view(np.float32).reshape(ts.log_prob.shape)
+        rows, log_prob, status = host_copy(ts.spans, ts.log_prob, ts.status)
+        if status.any():
+            raise _lib.ChartLibError('cliora_sample_trees rejected %d sentence length(s)' % int(status.sum()))
         for b, i in enumerate(idx):
             trees = diora.trees_from_spans(rows[b, :, :len(sentences[i]) - 1])
             out[i] = list(zip(trees, log_prob[b].tolist()))
