@@ -16,9 +16,12 @@
 #include "posterior_kernels.hpp"
 #include "sample_kernels.hpp"
 
-// The one launch of a decode kernel: a workgroup of `waves` wavefronts per sentence, lds_of(L, C) bytes of dynamic LDS (a function or
-// a closure), the arguments every decode kernel starts with, then the kernel's own.  f(Bool<LONG>, go) calls go(name, the kernel's instance, its own arguments...).
+// The one launch of a decode kernel: a workgroup of `waves` wavefronts per sentence, lds_of(L, C).total bytes of dynamic LDS (the
+// layout description the kernel carves from: lds<CkyLds>, or a closure), the arguments every decode kernel starts with, then the kernel's own.  f(Bool<LONG>, go) calls go(name, the kernel's instance, its own arguments...).
 // who: the entry's name in the "called before forward" message.  status: zeroed first when given.
+template <class Lds>
+static Lds lds(int L, int C) { return Lds{L, C}; }
+
 template <class LdsOf, class F>
 static int launch_decode(cliora_plan* plan, void* fwd_ws, const char* who, int waves, LdsOf&& lds_of, const int32_t* lengths,
                          int32_t* split, int32_t* spans, int32_t* status, void* stream, F&& f) {
@@ -28,7 +31,7 @@ static int launch_decode(cliora_plan* plan, void* fwd_ws, const char* who, int w
     if (status) HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
     const Plan& p = plan->p;
     if (p.L <= 1) spans = nullptr;                   // one word: no constituent, and no row to write
-    const size_t lds = lds_of(p.L, p.C);
+    const size_t lds = lds_of(p.L, p.C).total;
     return with_long(p.is_long(), [&](auto LONG) {
         return f(LONG, [&](const char* name, auto* kernel, auto... own) {
             if (lds > 64 * 1024) OKR(cliora_ensure_max_lds((const void*)kernel));
@@ -42,7 +45,7 @@ static int launch_decode(cliora_plan* plan, void* fwd_ws, const char* who, int w
 
 static int launch_cky(cliora_plan* plan, void* fwd_ws, const char* who, const int32_t* lengths, int32_t* split_out, int32_t* spans_out,
                       int32_t* status, void* stream) {
-    return launch_decode(plan, fwd_ws, who, CKY_WAVES, cky_lds, lengths, split_out, spans_out, status, stream, [&](auto LONG, auto&& go) {
+    return launch_decode(plan, fwd_ws, who, CKY_WAVES, lds<CkyLds>, lengths, split_out, spans_out, status, stream, [&](auto LONG, auto&& go) {
         const Plan& p = plan->p;
         return go("cky_kernel", cky_kernel<decltype(LONG)::value>, p.d_tables + p.dev.pair_a_in, p.d_tables + p.dev.pair_b_in);
     });
@@ -77,17 +80,18 @@ extern "C" int cliora_span_posteriors(cliora_plan* plan, void* fwd_ws, const int
     (void)scratch;
     if (!plan || !fwd_ws || !marginals || !log_z) return fail(CLIORA_EINVAL, "cliora_span_posteriors: NULL argument");
     if (lengths && !status) return fail(CLIORA_EINVAL, "cliora_span_posteriors: lengths given without status");
-    return launch_decode(plan, fwd_ws, "span_posteriors", POST_WAVES, span_posteriors_lds, lengths, mbr_split, mbr_spans, status, stream,
+    return launch_decode(plan, fwd_ws, "span_posteriors", POST_WAVES, lds<PostLds>, lengths, mbr_split, mbr_spans, status, stream,
                          [&](auto LONG, auto&& go) {
                              return go("span_posteriors_kernel", span_posteriors_kernel<decltype(LONG)::value>, marginals, log_z);
                          });
 }
 
-// The tables of a plan's B sentences when they do not fit the LDS (kbest_kernels.hpp: kbest_in_lds), else 0.
+// The tables of a plan's B sentences when they do not fit the LDS (kbest_kernels.hpp: KbestLds.in_lds), else 0.
 extern "C" size_t cliora_kbest_scratch_bytes(const cliora_plan* plan, int K) {
     if (!plan || K < 1 || K > KBEST_MAX_K) return 0;
     const Plan& p = plan->p;
-    return kbest_in_lds(p.L, p.C, K) ? 0 : (size_t)p.B * kbest_table_bytes(p.C, K);
+    const KbestLds lay{p.L, p.C, K};
+    return lay.in_lds ? 0 : (size_t)p.B * lay.table_bytes;
 }
 
 extern "C" int cliora_kbest_spans(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, int K, int32_t* spans_out, float* scores_out,
@@ -97,8 +101,8 @@ extern "C" int cliora_kbest_spans(cliora_plan* plan, void* fwd_ws, const int32_t
         return fail(CLIORA_EINVAL, "cliora_kbest_spans: NULL argument");
     if (lengths && !status) return fail(CLIORA_EINVAL, "cliora_kbest_spans: lengths given without status");
     if (!scratch && cliora_kbest_scratch_bytes(plan, K)) return fail(CLIORA_EINVAL, "cliora_kbest_spans: NULL scratch");
-    const bool in_lds = kbest_in_lds(plan->p.L, plan->p.C, K);
-    return launch_decode(plan, fwd_ws, "kbest_spans", KBEST_WAVES, [K](int L, int C) { return kbest_lds(L, C, K); }, lengths, nullptr,
+    const bool in_lds = KbestLds{plan->p.L, plan->p.C, K}.in_lds;
+    return launch_decode(plan, fwd_ws, "kbest_spans", KBEST_WAVES, [K](int L, int C) { return KbestLds{L, C, K}; }, lengths, nullptr,
                          spans_out, status, stream, [&](auto LONG, auto&& go) {
                              constexpr bool LNG = decltype(LONG)::value;
                              return in_lds ? go("kbest_kernel", kbest_kernel<LNG, true>, K, scores_out, count_out, (float*)nullptr)
@@ -115,7 +119,7 @@ extern "C" int cliora_sample_trees(cliora_plan* plan, void* fwd_ws, const int32_
     if (!plan || !fwd_ws || !log_prob_out || !log_z_out || (!spans_out && plan->p.L > 1))
         return fail(CLIORA_EINVAL, "cliora_sample_trees: NULL argument");
     if (lengths && !status) return fail(CLIORA_EINVAL, "cliora_sample_trees: lengths given without status");
-    return launch_decode(plan, fwd_ws, "sample_trees", POST_WAVES, sample_trees_lds, lengths, nullptr, spans_out, status, stream,
+    return launch_decode(plan, fwd_ws, "sample_trees", POST_WAVES, lds<SampleLds>, lengths, nullptr, spans_out, status, stream,
                          [&](auto LONG, auto&& go) {
                              return go("sample_trees_kernel", sample_trees_kernel<decltype(LONG)::value>, ids, S, seed, first_sample, beta,
                                        log_prob_out, log_z_out);
@@ -131,7 +135,7 @@ extern "C" int cliora_constrained_parse(cliora_plan* plan, void* fwd_ws, const i
         return fail(CLIORA_EINVAL, "cliora_constrained_parse: NULL argument");
     if (!spans_out && plan->p.L > 1) return fail(CLIORA_EINVAL, "cliora_constrained_parse: NULL spans_out");
     if (!brackets && M > 0) return fail(CLIORA_EINVAL, "cliora_constrained_parse: NULL brackets");
-    return launch_decode(plan, fwd_ws, "constrained_parse", POST_WAVES, [M](int L, int C) { return constrained_lds(L, C, M); }, lengths,
+    return launch_decode(plan, fwd_ws, "constrained_parse", POST_WAVES, [M](int L, int C) { return ConLds{L, C, M}; }, lengths,
                          nullptr, spans_out, status, stream, [&](auto LONG, auto&& go) {
                              return go("constrained_kernel", constrained_kernel<decltype(LONG)::value>, brackets, M, score_out, log_z_out,
                                        log_zc_out, log_prob_out, feasible_out, marginals);
@@ -156,7 +160,7 @@ extern "C" int cliora_bracket_grad(cliora_plan* plan, void* fwd_ws, const int32_
     if (!plan || !fwd_ws || !d_split || !log_prob_out || !feasible_out || !status) return fail(CLIORA_EINVAL, "cliora_bracket_grad: NULL argument");
     if (!brackets && M > 0) return fail(CLIORA_EINVAL, "cliora_bracket_grad: NULL brackets");
     if (plan->p.is_long()) return fail(CLIORA_EINVAL, "cliora_bracket_grad: L > 64 is forward only (the backward stops at 64 words, so nothing could take the gradient)");
-    return launch_decode(plan, fwd_ws, "bracket_grad", POST_WAVES, [M](int L, int C) { return bracket_grad_lds(L, C, M); }, lengths, nullptr,
+    return launch_decode(plan, fwd_ws, "bracket_grad", POST_WAVES, [M](int L, int C) { return BracketGradLds{L, C, M}; }, lengths, nullptr,
                          nullptr, status, stream, [&](auto, auto&& go) {
                              return go("bracket_grad_kernel", bracket_grad_kernel, brackets, M, weights, d_split, log_prob_out, feasible_out);
                          });
@@ -170,7 +174,7 @@ extern "C" int cliora_tree_expectation(cliora_plan* plan, void* fwd_ws, const in
     if (!plan || !fwd_ws || !d_split || !risk_out || !entropy_out || !log_z_out || !status)
         return fail(CLIORA_EINVAL, "cliora_tree_expectation: NULL argument");
     if (plan->p.is_long()) return fail(CLIORA_EINVAL, "cliora_tree_expectation: L > 64 is forward only (the backward stops at 64 words, so nothing could take the gradient)");
-    return launch_decode(plan, fwd_ws, "tree_expectation", POST_WAVES, tree_expectation_lds, lengths, nullptr, nullptr, status, stream,
+    return launch_decode(plan, fwd_ws, "tree_expectation", POST_WAVES, lds<ExpectationLds>, lengths, nullptr, nullptr, status, stream,
                          [&](auto, auto&& go) {
                              return go("tree_expectation_kernel", tree_expectation_kernel, cost, w_cost, w_entropy, d_split, risk_out,
                                        entropy_out, log_z_out);

@@ -11,19 +11,20 @@
 //            s <= j < e, and per word i, he[i] = the smallest end of one with s < i <= e: [i, j] crosses a required bracket iff
 //            gs[j] > i or he[i] < j -- n M tests for the two tables and one test per cell, against C M for brute force (at L 128 and
 //            M 256: 33 k tests, not 2.1 M).  Then a byte per cell: bit 0 allowed, bit 1 required (its mu is 1).
-//   best     cky_kernel's recurrence: val[leaf] = 1.0f, candidate (val_l + val_r) + (s_k - smax) in fp32 in that order, first maximum
+//   best     cky_kernel's recurrence, by its step (best_split): val[leaf] = 1.0f, candidate (val_l + val_r) + (s_k - smax), first maximum
 //            wins, a disallowed cell (a forbidden leaf too) holds -inf; score = val[root] - (float)n; emit_spans' walk.
 //   inside   post_inside's recurrence in fp64 over the allowed cells (al), and in the SAME level loop the unconstrained one (au, in
 //            the table the outside pass takes afterwards) -- it shares the row load, the row maximum and the level's barrier, where a
-//            second pass would pay n - 1 more barriers; both are post_inside's operations in its order, so log_z is that of
-//            cliora_span_posteriors bit for bit, and without a disallowed cell the two tables are one and au is not computed at all.
-//   outside  span_posteriors_kernel's recurrence over the allowed cells; mu_c = exp(al + be - log_z_c), 0 on a disallowed cell.
-// A cell without a finite term skips the reduction (con_wave_lse), so -inf stays -inf and no NaN is formed.
+//            second pass would pay n - 1 more barriers; both call what post_inside calls (split_terms, inside_lse), so log_z is that
+//            of cliora_span_posteriors bit for bit, and without a disallowed cell the two tables are one and au is not computed at all.
+//   outside  span_posteriors_kernel's pass, post_outside, with MASKED set: over the allowed cells; mu_c = exp(al + be - log_z_c), 0 on
+//            a disallowed cell.  Without brackets it runs the operations of the unmasked instance: the same marginals bit for bit.
+// A cell without a finite term skips the reduction (con_wave_lse, posterior_kernels.hpp), so -inf stays -inf and no NaN is formed.
 // Geometry of posterior_kernels.hpp: one workgroup of POST_WAVES wavefronts per sentence, a wavefront per cell, a lane per split or
 // use (a second one at lane + 64 when LONG), one barrier per level.  No atomics but the status count; two calls give equal bits.
 //
-// LDS: 16 C bytes of tables -- val and bsp (8 C) first, then al and au / be in their place --, the level bases (L ints), the walk
-// stack (3 (L + 1) ints), gs and he (2 L ints), the rows (3 M ints), a vote slot per wavefront and the mask (C bytes): 17 C + 24 L +
+// LDS (ConLds = PostLds + MaskLds): 16 C bytes of tables -- val and bsp (8 C) first, then al and au / be in their place --, the level
+// bases (L ints), the walk stack (3 (L + 1) ints), gs and he (2 L ints), the rows (3 M ints), a vote slot per wavefront and the mask (C bytes): 17 C + 24 L +
 // 12 M + 44 bytes, 143 KiB at L 128 and M 256, inside the CU's 160 KiB.  All of it is dynamic: the kernel holds no static LDS (the
 // launch raises the dynamic limit to the whole CU's, which a static byte would overrun), so the workgroup's votes are con_block_any.
 #pragma once
@@ -35,15 +36,6 @@
 namespace cliora {
 
 constexpr int CON_MAX_M = 256;                       // bracket rows per sentence
-constexpr int CON_ALLOWED = 1, CON_REQUIRED = 2;     // bits of a cell's mask byte
-
-// post_wave_lse for terms that may all be -inf: the wave skips the reduction then (the ballot is the same in every lane).
-template <bool LONG>
-__device__ __forceinline__ post_t con_wave_lse(post_t t0, post_t t1) {
-    const post_t ninf = -INFINITY;
-    if (!__ballot(t0 > ninf || (LONG && t1 > ninf))) return ninf;
-    return post_wave_lse<LONG>(t0, t1);
-}
 
 // Whether `p` holds in any thread of the workgroup: a ballot per wavefront, a slot each, one barrier.  A second vote may reuse the
 // slots once another barrier lies between.
@@ -57,15 +49,28 @@ __device__ __forceinline__ bool con_block_any(bool p, int32_t* slots, int wave, 
     return any != 0;
 }
 
-// The mask of one sentence of n words (0 when its length is bad, with `bad` set): its M rows (start, end, kind) staged in brk and
-// validated, gs / he from the required ones, then a byte per cell of the triangle (the header above).  Called by every thread of the
-// workgroup.  -> -1: a bad length or a bad row (nothing but brk is written), 0: no cell is disallowed, 1: some cell is.  The fills the
-// caller made before the call are ordered before what it stores after it (the first vote's barrier).
-__device__ __forceinline__ int con_build_mask(int L, int C, int n, bool bad, const int32_t* __restrict__ rows, int M, int32_t* brk,
-                                              int32_t* gs, int32_t* he, int32_t* vote, unsigned char* mask) {
+// The mask tail of a kernel's dynamic LDS, from byte gs on: gs and he (L ints each), the rows (3 M ints), a vote slot per wavefront
+// and the mask (C bytes, rounded up to a word).  One sub-layout, shared by constrained_kernel and bracket_grad_kernel.
+struct MaskLds {
+    int L, C, M;
+    size_t gs, he = gs + (size_t)L * sizeof(int32_t), brk = he + (size_t)L * sizeof(int32_t), vote = brk + (size_t)3 * M * sizeof(int32_t);
+    size_t mask = vote + POST_WAVES * sizeof(int32_t), end = mask + (((size_t)C + 3) & ~(size_t)3);
+};
+
+// The mask of sentence t (n = 0 when its length is bad, with `bad` set): its M rows (start, end, kind) staged and validated, gs / he
+// from the required ones, then a byte per cell of the triangle (the header above), in the mask tail `ml` of `smem`.  Called by every
+// thread of the workgroup.  -> -1: a bad length or a bad row (nothing but the rows is written), 0: no cell is
+// disallowed, 1: some cell is.  The fills the caller made before the call are ordered before what it stores after it (the first
+// vote's barrier).
+__device__ __forceinline__ int con_build_mask(const Tri& t, bool bad, const int32_t* __restrict__ rows, int M, unsigned char* smem,
+                                              const MaskLds& ml) {
+    int32_t* gs = reinterpret_cast<int32_t*>(smem + ml.gs);
+    int32_t* he = reinterpret_cast<int32_t*>(smem + ml.he);
+    int32_t* brk = reinterpret_cast<int32_t*>(smem + ml.brk);
+    int32_t* vote = reinterpret_cast<int32_t*>(smem + ml.vote);
+    unsigned char* mask = smem + ml.mask;
     constexpr int NT = POST_WAVES * 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, L = t.L, n = t.n;
     for (int r = threadIdx.x; r < M; r += NT) {
         const int32_t* row = rows + (size_t)r * 3;
         int s = row[0], e = row[1], k = row[2];
@@ -92,57 +97,51 @@ __device__ __forceinline__ int con_build_mask(int L, int C, int n, bool bad, con
     for (int level = 0; level < n; ++level)
         for (int pos = threadIdx.x; pos < n - level; pos += NT) {
             const bool ok = gs[pos + level] <= pos && he[pos] >= pos + level;
-            mask[coff(level) + pos] = ok ? CON_ALLOWED : 0;
+            mask[t.cell(level, pos)] = ok ? CON_ALLOWED : 0;
             dis |= !ok;
         }
     __syncthreads();
     for (int r = threadIdx.x; r < M; r += NT)
-        if (brk[3 * r + 2] == 0) { mask[chart_cell(L, C, brk[3 * r + 1] - brk[3 * r], brk[3 * r])] = 0; dis = true; }
+        if (brk[3 * r + 2] == 0) { mask[t.cell(brk[3 * r + 1] - brk[3 * r], brk[3 * r])] = 0; dis = true; }
     __syncthreads();
     for (int r = threadIdx.x; r < M; r += NT)
         if (brk[3 * r + 2] == 1) {
-            const int cell = chart_cell(L, C, brk[3 * r + 1] - brk[3 * r], brk[3 * r]);
+            const int cell = t.cell(brk[3 * r + 1] - brk[3 * r], brk[3 * r]);
             if (mask[cell]) mask[cell] = CON_ALLOWED | CON_REQUIRED;        // every writer of a cell stores this value
         }
     return con_block_any(dis, vote, wave, lane) ? 1 : 0;
 }
 
-// The inside tables of sentence b's n words, levels up: al over the allowed cells and, where `constrained`, au over every cell --
-// post_inside's operations in its order, in one level loop.  The leaves are the caller's (before a barrier).  Called by every thread of
-// the workgroup; one barrier per level, the last one before it returns.  lvl: the plan's level bases, in LDS.
+// The inside tables of sentence t, levels up: al over the allowed cells and, where `constrained`, au over every cell -- each cell
+// by inside_lse on split_terms, as post_inside, in one level loop.  The leaves are the caller's (before a barrier).  Called by every
+// thread of the workgroup; one barrier per level, the last one before it returns.  t.lvl: the plan's level bases, in LDS.
 template <bool LONG>
-__device__ __forceinline__ void con_inside(post_t* al, post_t* au, const unsigned char* mask, bool constrained, const int32_t* lvl, int L,
-                                           int C, int B, int b, int n, const float* __restrict__ Sp) {
-    const post_t ninf = -INFINITY;
+__device__ __forceinline__ void con_inside(post_t* al, post_t* au, const unsigned char* mask, bool constrained, const Tri& t) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
-    auto row_of = [&](int level, int pos) { return (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level; };
-    for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const bool an = lane < level, an1 = LONG && lane + 64 < level;
-            float s, s1;
-            const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
-            const post_t r0 = (post_t)s - (post_t)smax, r1 = (post_t)s1 - (post_t)smax;
-            const int l0 = coff(lane) + pos, q0 = an ? coff(level - lane - 1) + pos + lane + 1 : 0;
-            const int l1 = an1 ? coff(lane + 64) + pos : 0, q1 = an1 ? coff(level - lane - 65) + pos + lane + 65 : 0;
-            post_t a = ninf;
-            if (mask[off + pos] & CON_ALLOWED) {
-                const post_t t0 = an ? al[l0] + al[q0] + r0 : ninf;
-                const post_t t1 = an1 ? al[l1] + al[q1] + r1 : ninf;
-                a = con_wave_lse<LONG>(t0, t1);
-            }
+    for (int level = 1; level < t.n; ++level) {
+        for (int pos = wave; pos < t.n - level; pos += POST_WAVES) {
+            const int cell = t.cell(level, pos);
+            const SplitTerms x = split_terms<LONG>(t, level, pos, lane);
+            post_t a = -INFINITY;
+            if (mask[cell] & CON_ALLOWED) a = inside_lse<LONG, true>(x.t0(al), x.t1(al));
             if (constrained) {
-                const post_t t0 = an ? au[l0] + au[q0] + r0 : ninf;
-                const post_t t1 = an1 ? au[l1] + au[q1] + r1 : ninf;
-                const post_t u = post_wave_lse<LONG>(t0, t1);
-                if (lane == 0) au[off + pos] = u;
+                const post_t u = inside_lse<LONG>(x.t0(au), x.t1(au));
+                if (lane == 0) au[cell] = u;
             }
-            if (lane == 0) al[off + pos] = a;
+            if (lane == 0) al[cell] = a;
         }
         __syncthreads();
     }
 }
+
+// Dynamic LDS of constrained_kernel for a chart of length L and M rows per sentence: 16 C bytes of tables -- val and bsp (8 C) first,
+// then al and au / be in their place --, the level bases, the walk stack, the mask tail.
+struct ConLds {
+    int L, C, M;
+    PostLds p{L, C};
+    MaskLds m{L, C, M, p.total};
+    size_t total = m.end;
+};
 
 // lengths (B) or NULL (every sentence has L words).  brackets (B, M, 3) rows (start, end, kind): kind 1 required, 0 forbidden, start
 // -1 unused; NULL when M = 0.  spans (B, L-1, 2) (NULL when L = 1): the best qualifying tree in emit_spans' order, (-1, -1) beyond;
@@ -160,31 +159,24 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void constrained_kernel(int
                                                                              float* __restrict__ log_zc, float* __restrict__ log_prob,
                                                                              int32_t* __restrict__ feasible, float* marg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char con_smem[];
-    post_t* al = reinterpret_cast<post_t*>(con_smem);
-    post_t* be = al + C;
-    int32_t* lvl = reinterpret_cast<int32_t*>(be + C);
-    int32_t* stk = lvl + L;
-    int32_t* gs = stk + 3 * (L + 1);
-    int32_t* he = gs + L;
-    int32_t* brk = he + L;
-    int32_t* vote = brk + 3 * M;
-    unsigned char* mask = reinterpret_cast<unsigned char*>(vote + POST_WAVES);
+    const ConLds lay{L, C, M};
+    post_t* al = reinterpret_cast<post_t*>(con_smem + lay.p.al);
+    post_t* be = reinterpret_cast<post_t*>(con_smem + lay.p.be);
+    const unsigned char* mask = con_smem + lay.m.mask;
     constexpr int NT = POST_WAVES * 64;
     const post_t ninf = -INFINITY;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     (void)split;
-    int n = lengths ? lengths[b] : L;
-    bool bad = n < 1 || n > L;
-    if (bad) n = 0;
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
-    auto row_of = [&](int level, int pos) { return (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level; };
+    bool bad;
+    const int n = sentence_length(lengths, b, L, bad);
+    Tri t{L, C, B, b, n, lvl_base, Sp};
     float* mu = marg ? marg + (size_t)b * C : nullptr;
     if (mu) for (int c = threadIdx.x; c < C; c += NT) mu[c] = 0.f;
     if (spans) for (int i = threadIdx.x; i < 2 * (L - 1); i += NT) spans[(size_t)b * (L - 1) * 2 + i] = -1;
-    for (int c = threadIdx.x; c < L; c += NT) lvl[c] = lvl_base[c];
+    stage_levels<NT>(t, reinterpret_cast<int32_t*>(con_smem + lay.p.lvl));
 
     // ---- the mask
-    const int masked = con_build_mask(L, C, n, bad, brackets + (size_t)b * M * 3, M, brk, gs, he, vote, mask);
+    const int masked = con_build_mask(t, bad, brackets + (size_t)b * M * 3, M, con_smem, lay.m);
     if (masked < 0) {
         if (threadIdx.x == 0) {
             atomicAdd(status, 1);
@@ -194,40 +186,33 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void constrained_kernel(int
     }
     const bool constrained = masked > 0;             // some cell of the triangle is disallowed
 
-    // ---- the best tree, levels up: cky_kernel over the allowed cells
-    float* val = reinterpret_cast<float*>(con_smem);
-    int32_t* bsp = reinterpret_cast<int32_t*>(con_smem) + C;
+    // ---- the best tree, levels up: cky_kernel's step (best_split) over the allowed cells
+    float* val = reinterpret_cast<float*>(con_smem + lay.p.val);
+    int32_t* bsp = reinterpret_cast<int32_t*>(con_smem + lay.p.bsp);
     for (int c = threadIdx.x; c < n; c += NT) { val[c] = (mask[c] & CON_ALLOWED) ? 1.f : -INFINITY; bsp[c] = -1; }
     __syncthreads();
     for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            if (!(mask[off + pos] & CON_ALLOWED)) {
-                if (lane == 0) { val[off + pos] = -INFINITY; bsp[off + pos] = -1; }
+        for (int pos = wave; pos < n - level; pos += POST_WAVES) {
+            const int cell = t.cell(level, pos);
+            if (!(mask[cell] & CON_ALLOWED)) {
+                if (lane == 0) { val[cell] = -INFINITY; bsp[cell] = -1; }
                 continue;
             }
             float s, s1;
-            const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
-            const bool an = lane < level;
-            float best = -INFINITY; int bi = an ? lane : 0x7fffffff;
-            if (an) best = (val[coff(lane) + pos] + val[coff(level - lane - 1) + pos + lane + 1]) + (s - smax);
-            if constexpr (LONG) {
-                if (lane + 64 < level) {
-                    const float c1 = (val[coff(lane + 64) + pos] + val[coff(level - lane - 65) + pos + lane + 65]) + (s1 - smax);
-                    if (c1 > best) { best = c1; bi = lane + 64; }
-                }
-            }
-            wave_first_max(best, bi);
-            if (lane == 0) { val[off + pos] = best; bsp[off + pos] = bi; }
+            const float smax = load_split_scores<LONG>(Sp + t.row(level, pos), level, lane, s, s1);
+            float best; int bi;
+            best_split<LONG>(val, t.left(level, pos, lane), t.right(level, pos, lane), t.left(level, pos, lane + 64),
+                             t.right(level, pos, lane + 64), s - smax, s1 - smax, level, lane, best, bi);
+            if (lane == 0) { val[cell] = best; bsp[cell] = bi; }
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const float root = val[coff(n - 1)];
+        const float root = val[t.root()];
         const bool feas = root > -INFINITY;          // a finite root has finite children all the way down: the walk stays on them
         feasible[b] = feas ? 1 : 0;
         score[b] = feas ? root - (float)n : -INFINITY;
-        if (spans && feas && n > 1) emit_spans(bsp, L, C, n, stk, spans + (size_t)b * (L - 1) * 2);
+        if (spans && feas && n > 1) emit_spans(bsp, t, reinterpret_cast<int32_t*>(con_smem + lay.p.stk), spans + (size_t)b * (L - 1) * 2);
     }
     __syncthreads();                                 // the walk has read bsp: the fp64 tables take its place
 
@@ -238,49 +223,12 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void constrained_kernel(int
         if (constrained) au[c] = 0;
     }
     __syncthreads();
-    con_inside<LONG>(al, au, mask, constrained, lvl, L, C, B, b, n, Sp);
-    const post_t lzc = al[coff(n - 1)], lz = constrained ? au[coff(n - 1)] : lzc;
+    con_inside<LONG>(al, au, mask, constrained, t);
+    const post_t lzc = al[t.root()], lz = constrained ? au[t.root()] : lzc;
     if (threadIdx.x == 0) { log_zc[b] = (float)lzc; log_z[b] = (float)lz; log_prob[b] = (float)(lzc - lz); }
     if (!mu || !(lzc > ninf)) return;
     __syncthreads();                                 // every thread holds log_z: be takes au's place
-
-    // ---- outside, levels down, over the allowed cells; mu as each cell's be is known
-    for (int level = n - 1; level >= 0; --level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const int mk = mask[off + pos];
-            if (!(mk & CON_ALLOWED)) {                                      // its mu stays 0
-                if (lane == 0 && level > 0) be[off + pos] = ninf;
-                continue;
-            }
-            post_t bt = 0;                                                  // the sentence's root
-            if (level < n - 1) {
-                const int nr = n - 1 - pos - level, cnt = n - 1 - level;    // uses as a left child; all uses
-                auto term = [&](int u) -> post_t {
-                    int plevel, ppos, k, sib;
-                    if (u < nr) { plevel = level + u + 1; ppos = pos; k = level; sib = coff(u) + pos + level + 1; }
-                    else { const int j = u - nr; plevel = level + j + 1; ppos = pos - j - 1; k = j; sib = coff(j) + ppos; }
-                    return be[coff(plevel) + ppos] + al[sib] + (post_t)Sp[row_of(plevel, ppos) + k];
-                };
-                const post_t t0 = lane < cnt ? term(lane) : ninf;
-                const post_t t1 = LONG && lane + 64 < cnt ? term(lane + 64) : ninf;
-                bt = con_wave_lse<LONG>(t0, t1);
-            }
-            if (level > 0) {                                                // what the children read: be - rowmax
-                float s, s1;
-                const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
-                if (lane == 0) be[off + pos] = bt - (post_t)smax;
-            }
-            if (lane == 0) mu[off + pos] = (mk & CON_REQUIRED) ? 1.f : (float)exp(al[off + pos] + bt - lzc);
-        }
-        __syncthreads();
-    }
-}
-
-// Dynamic LDS of the kernel for a chart of length L and M rows per sentence (the mask's C bytes rounded up to a word).
-static inline size_t constrained_lds(int L, int C, int M) {
-    return (size_t)2 * C * sizeof(post_t) + ((size_t)L + 3 * ((size_t)L + 1) + 2 * (size_t)L + 3 * (size_t)M + POST_WAVES) * sizeof(int32_t) +
-           (((size_t)C + 3) & ~(size_t)3);
+    post_outside<LONG, true>(t, al, be, mask, lzc, mu);
 }
 
 }  // namespace cliora

@@ -8,7 +8,7 @@
 //   inside   am[leaf] = wc cost[leaf],  am[cell] = wc cost[cell] + sum_k q_k (am[left_k] + am[right_k] - we r[cell, k]),
 //            q_k = exp(al[left_k] + al[right_k] + r[cell, k] - al[cell]);  E[V] = am[root]
 //   outside  bm[root] = 0,  bm[cell] = sum over its uses of w_u (bm[parent] + am[sibling] + v[parent, k]),
-//            w_u = exp(be[parent] + al[sibling] + r[parent, k] - be[cell]); the uses are posterior_kernels.hpp's closed forms
+//            w_u = exp(be[parent] + al[sibling] + r[parent, k] - be[cell]); the uses are posterior_kernels.hpp's cell_use
 //   E[V | e] = bm[cell] + am[left] + am[right] + v[e]
 //   G[cell, k] = G_r[cell, k] - [k == k*] sum_k G_r[cell, .], k* the row's first maximum (wave_first_max): every row sums to zero.
 // What the tables hold is what a child reads: be - rowmax(cell), as in posterior_kernels.hpp, and bm + wc cost[cell] -- the cell's
@@ -22,7 +22,7 @@
 // leaves and the root) and E[R] = sum over the edges of nu r, each a register partial per wavefront in loop order, the eight partials
 // added in wavefront order by one thread; neither depends on wc or we.  L <= 64 only (a lane per split; the chart backward's bound).
 //
-// LDS: the four fp64 tables (32 C bytes), the 16 partials, the row maxima (4 C) and the level bases (L ints): 36 C + 4 L + 128 bytes
+// LDS (ExpectationLds): the four fp64 tables (32 C bytes), the 16 partials, the row maxima (4 C) and the level bases (L ints): 36 C + 4 L + 128 bytes
 // -- 7.6 KiB at L 20, 29.1 KiB at L 40, 73.5 KiB at L 64.  All of it is dynamic (above 64 KiB the launch raises the limit).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +31,15 @@
 #include "posterior_kernels.hpp"
 
 namespace cliora {
+
+// Dynamic LDS of tree_expectation_kernel for a chart of length L: the four fp64 tables, the 16 partials, the row maxima, the level
+// bases.
+struct ExpectationLds {
+    int L, C;
+    size_t al = 0, am = al + (size_t)C * sizeof(post_t), be = am + (size_t)C * sizeof(post_t), bm = be + (size_t)C * sizeof(post_t);
+    size_t part = bm + (size_t)C * sizeof(post_t), rmax = part + 2 * POST_WAVES * sizeof(post_t), lvl = rmax + (size_t)C * sizeof(float);
+    size_t total = lvl + (size_t)L * sizeof(int32_t);
+};
 
 // lengths (B) or NULL; cost (B, C) in the cell order of inside_s or NULL (0); w_cost (B) or NULL (1); w_entropy (B) or NULL (0);
 // G: the inside split-score rows of the batch (row B lvl_base[level] + (b (L - level) + pos) level + k), every element written;
@@ -46,83 +55,69 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void tree_expectation_kerne
                                                                                   float* __restrict__ risk, float* __restrict__ entropy,
                                                                                   float* __restrict__ log_z) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ex_smem[];
-    post_t* al = reinterpret_cast<post_t*>(ex_smem);
-    post_t* am = al + C;
-    post_t* be = am + C;
-    post_t* bm = be + C;
-    post_t* part = bm + C;
-    float* rmax = reinterpret_cast<float*>(part + 2 * POST_WAVES);
-    int32_t* lvl = reinterpret_cast<int32_t*>(rmax + C);
+    const ExpectationLds lay{L, C};
+    post_t* al = reinterpret_cast<post_t*>(ex_smem + lay.al);
+    post_t* am = reinterpret_cast<post_t*>(ex_smem + lay.am);
+    post_t* be = reinterpret_cast<post_t*>(ex_smem + lay.be);
+    post_t* bm = reinterpret_cast<post_t*>(ex_smem + lay.bm);
+    post_t* part = reinterpret_cast<post_t*>(ex_smem + lay.part);
+    float* rmax = reinterpret_cast<float*>(ex_smem + lay.rmax);
     constexpr int NT = POST_WAVES * 64;
     const post_t ninf = -INFINITY;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     (void)split; (void)spans;
-    const int n = lengths ? lengths[b] : L;
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
-    auto row_of = [&](int level, int pos) { return (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level; };
-    if (n < 1 || n > L) {                             // nothing of the sentence is read: not its weights, not its costs
-        for (int level = 1; level < L; ++level) {     // a level's rows of one sentence are contiguous
-            float* g = G + (size_t)B * lvl_base[level] + (size_t)b * (L - level) * level;
-            for (int i = threadIdx.x; i < (L - level) * level; i += NT) g[i] = 0.f;
-        }
+    bool bad;
+    const int n = sentence_length(lengths, b, L, bad);
+    Tri t{L, C, B, b, n, lvl_base, Sp};
+    if (bad) {                                        // nothing of the sentence is read: not its weights, not its costs
+        zero_split_rows<NT>(G, t);
         if (threadIdx.x == 0) { atomicAdd(status, 1); risk[b] = 0.f; entropy[b] = 0.f; log_z[b] = 0.f; }
         return;
     }
     const float* cst = cost ? cost + (size_t)b * C : nullptr;
     auto cost_of = [&](int cell) { return cst ? (post_t)cst[cell] : (post_t)0; };
     const post_t wc = w_cost ? (post_t)w_cost[b] : (post_t)1, we = w_entropy ? (post_t)w_entropy[b] : (post_t)0;
-    for (int c = threadIdx.x; c < L; c += NT) lvl[c] = lvl_base[c];
+    stage_levels<NT>(t, reinterpret_cast<int32_t*>(ex_smem + lay.lvl));
     for (int c = threadIdx.x; c < n; c += NT) { al[c] = 0; am[c] = wc * cost_of(c); }               // the sentence's leaves
     __syncthreads();
 
-    // ---- inside, levels up: al by post_inside's operations in its order (log_z has cliora_span_posteriors' bits), am beside it
+    // ---- inside, levels up: al by inside_lse on split_terms, as post_inside (log_z has cliora_span_posteriors' bits), am beside it
     for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const bool an = lane < level;
-            float s, s1;
-            const float smax = load_split_scores<false>(Sp + row_of(level, pos), level, lane, s, s1);
-            post_t t = ninf, val = 0;
-            if (an) {
-                const int l = coff(lane) + pos, q = coff(level - lane - 1) + pos + lane + 1;
-                const post_t r = (post_t)s - (post_t)smax;
-                t = al[l] + al[q] + r;
-                val = am[l] + am[q] - we * r;
-            }
-            const post_t a = post_wave_lse<false>(t, ninf);
-            const post_t w = an ? exp(t - a) : (post_t)0;
+        for (int pos = wave; pos < n - level; pos += POST_WAVES) {
+            const int cell = t.cell(level, pos);
+            const SplitTerms x = split_terms<false>(t, level, pos, lane);
+            const post_t tl = x.t0(al), val = x.an ? am[x.l0] + am[x.q0] - we * x.r0 : (post_t)0;
+            const post_t a = inside_lse<false>(tl, x.t1(al));
+            const post_t w = x.an ? exp(tl - a) : (post_t)0;
             const post_t mean = post_wave_sum(w > 0 ? w * val : (post_t)0);
-            if (lane == 0) { al[off + pos] = a; am[off + pos] = wc * cost_of(off + pos) + mean; rmax[off + pos] = smax; }
+            if (lane == 0) { al[cell] = a; am[cell] = wc * cost_of(cell) + mean; rmax[cell] = x.smax; }
         }
         __syncthreads();
     }
-    const post_t lz = al[coff(n - 1)], ev = am[coff(n - 1)];
+    const post_t lz = al[t.root()], ev = am[t.root()];
 
     // ---- outside, levels down to 1 (no one reads a leaf's outside score): be - rowmax and bm + wc cost, what a child reads; risk
     post_t rk = 0;                                    // this wavefront's share of sum mu cost, the same in every lane
     for (int level = n - 1; level >= 1; --level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
+        for (int pos = wave; pos < n - level; pos += POST_WAVES) {
+            const int cell = t.cell(level, pos);
             post_t bt = 0, mean = 0;                                        // the sentence's root
             if (level < n - 1) {
-                const int nr = n - 1 - pos - level, cnt = n - 1 - level;    // uses as a left child; all uses
-                post_t t = ninf, val = 0;
-                if (lane < cnt) {
-                    int plevel, ppos, k, sib;
-                    if (lane < nr) { plevel = level + lane + 1; ppos = pos; k = level; sib = coff(lane) + pos + level + 1; }
-                    else { const int j = lane - nr; plevel = level + j + 1; ppos = pos - j - 1; k = j; sib = coff(j) + ppos; }
-                    const float s = Sp[row_of(plevel, ppos) + k];
-                    const int par = coff(plevel) + ppos;
-                    t = be[par] + al[sib] + (post_t)s;
-                    val = bm[par] + am[sib] - we * ((post_t)s - (post_t)rmax[par]);
+                const bool use = lane < cell_uses(t, level);
+                post_t tu = ninf, val = 0;
+                if (use) {
+                    const CellUse x = cell_use(t, level, pos, lane);
+                    const float s = Sp[x.score];
+                    tu = be[x.parent] + al[x.sib] + (post_t)s;
+                    val = bm[x.parent] + am[x.sib] - we * ((post_t)s - (post_t)rmax[x.parent]);
                 }
-                bt = post_wave_lse<false>(t, ninf);
-                const post_t w = lane < cnt ? exp(t - bt) : (post_t)0;
+                bt = post_wave_lse<false>(tu, ninf);
+                const post_t w = use ? exp(tu - bt) : (post_t)0;
                 mean = post_wave_sum(w > 0 ? w * val : (post_t)0);
             }
-            const post_t cc = cost_of(off + pos);
-            rk += exp(al[off + pos] + bt - lz) * cc;
-            if (lane == 0) { be[off + pos] = bt - (post_t)rmax[off + pos]; bm[off + pos] = mean + wc * cc; }
+            const post_t cc = cost_of(cell);
+            rk += exp(al[cell] + bt - lz) * cc;
+            if (lane == 0) { be[cell] = bt - (post_t)rmax[cell]; bm[cell] = mean + wc * cc; }
         }
         __syncthreads();
     }
@@ -131,25 +126,25 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void tree_expectation_kerne
     // ---- G: a lane per element; E[R] on the way
     post_t er = 0;                                    // this wavefront's share of sum nu r, the same in every lane
     for (int level = 1; level < L; ++level) {
-        const int off = coff(level), mine = n - level;
+        const int mine = n - level;
         for (int pos = wave; pos < L - level; pos += POST_WAVES) {
-            float* g = G + row_of(level, pos);
+            float* g = G + t.row(level, pos);
             if (pos >= mine) {                                              // beyond the sentence's triangle
                 if (lane < level) g[lane] = 0.f;
                 continue;
             }
             const bool an = lane < level;
             float s, s1;
-            load_split_scores<false>(Sp + row_of(level, pos), level, lane, s, s1);
+            load_split_scores<false>(Sp + t.row(level, pos), level, lane, s, s1);
             float best = s; int kstar = an ? lane : 0x7fffffff;
             wave_first_max(best, kstar);
             post_t d = 0, nr = 0;
             if (an) {
-                const int l = coff(lane) + pos, q = coff(level - lane - 1) + pos + lane + 1;
-                const post_t r = (post_t)s - (post_t)rmax[off + pos];
-                const post_t nu = exp(be[off + pos] + al[l] + al[q] + (post_t)s - lz);
+                const int cell = t.cell(level, pos), l = t.left(level, pos, lane), q = t.right(level, pos, lane);
+                const post_t r = (post_t)s - (post_t)rmax[cell];
+                const post_t nu = exp(be[cell] + al[l] + al[q] + (post_t)s - lz);
                 if (nu > 0) {
-                    d = nu * ((bm[off + pos] + am[l] + am[q] - we * r) - ev);
+                    d = nu * ((bm[cell] + am[l] + am[q] - we * r) - ev);
                     nr = nu * r;
                 }
             }
@@ -165,11 +160,6 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void tree_expectation_kerne
         for (int w = 0; w < POST_WAVES; ++w) { r += part[w]; e += part[POST_WAVES + w]; }
         risk[b] = (float)r; entropy[b] = (float)(lz - e); log_z[b] = (float)lz;
     }
-}
-
-// Dynamic LDS of the kernel for a chart of length L.
-static inline size_t tree_expectation_lds(int L, int C) {
-    return ((size_t)4 * C + 2 * POST_WAVES) * sizeof(post_t) + (size_t)C * sizeof(float) + (size_t)L * sizeof(int32_t);
 }
 
 }  // namespace cliora

@@ -53,12 +53,22 @@ __device__ __forceinline__ void kbest_offer(const float* tv, int lo, int ro, int
     }
 }
 
+// Dynamic LDS of kbest_kernel (in_lds selects its IN_LDS instance): the table when it fits the CU's 160 KiB beside the K walk stacks
+// of 4 (L + 1) ints, then the stacks.  table_bytes: one sentence's table, wherever it lives.
+struct KbestLds {
+    int L, C, K;
+    size_t table_bytes = (size_t)C * K * (sizeof(float) + sizeof(int32_t)), stack_ints = (size_t)4 * (L + 1);
+    size_t stacks = K * stack_ints * sizeof(int32_t);
+    bool in_lds = table_bytes + stacks <= (size_t)160 * 1024;
+    size_t tv = 0, stk = in_lds ? table_bytes : 0, total = stk + stacks;
+};
+
 // One workgroup of KBEST_WAVES wavefronts per sentence; levels upward, a wavefront per cell, one barrier per level.
 // lengths (B) or NULL (every sentence has L words; status may be NULL then).  spans (B, K, L-1, 2) (NULL when L = 1): tree t's n - 1
 // constituents in emit_spans' order, (-1, -1) beyond them and beyond count; scores (B, K): root value - (float)n = the tree's sum of
 // r, -inf beyond count; count (B): min(K, Catalan(n - 1)).  A length outside [1, L]: count 0, scores -inf, rows -1, one count in
 // *status, no chart read.  `split` is launch_decode's slot and always NULL here.
-// LDS: the table when IN_LDS (8 C K bytes), then K walk stacks of 4 (L + 1) ints.  scratch: the tables otherwise.
+// LDS: KbestLds.  scratch: the tables when not IN_LDS.
 template <bool LONG, bool IN_LDS>
 static __global__ __launch_bounds__(KBEST_WAVES * 64) void kbest_kernel(int L, int C, const int32_t* __restrict__ lvl_base, int B,
                                                                         const float* __restrict__ Sp, const int32_t* __restrict__ lengths,
@@ -69,18 +79,14 @@ static __global__ __launch_bounds__(KBEST_WAVES * 64) void kbest_kernel(int L, i
     constexpr int NT = KBEST_WAVES * 64;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     (void)split;
-    float* tv;
-    int32_t* stk;
-    if constexpr (IN_LDS) {
-        tv = reinterpret_cast<float*>(kbest_smem);
-        stk = reinterpret_cast<int32_t*>(kbest_smem) + 2 * (size_t)C * K;
-    } else {
-        tv = scratch + (size_t)b * 2 * C * K;
-        stk = reinterpret_cast<int32_t*>(kbest_smem);
-    }
+    const KbestLds lay{L, C, K};
+    float* tv = IN_LDS ? reinterpret_cast<float*>(kbest_smem + lay.tv) : scratch + (size_t)b * 2 * C * K;
     int32_t* tk = reinterpret_cast<int32_t*>(tv + (size_t)C * K);
-    int n = lengths ? lengths[b] : L;
-    if (n < 1 || n > L) { n = 0; if (threadIdx.x == 0) atomicAdd(status, 1); }
+    int32_t* stk = reinterpret_cast<int32_t*>(kbest_smem + lay.stk);
+    bool bad;
+    const int n = sentence_length(lengths, b, L, bad);
+    if (bad && threadIdx.x == 0) atomicAdd(status, 1);
+    const Tri t{L, C, B, b, n, lvl_base, Sp};
     const int nroot = n ? kbest_count(n - 1, K) : 0;
     if (spans) for (int i = threadIdx.x; i < K * 2 * (L - 1); i += NT) spans[(size_t)b * K * (L - 1) * 2 + i] = -1;
     for (int i = threadIdx.x; i < K; i += NT) scores[(size_t)b * K + i] = -INFINITY;
@@ -88,18 +94,17 @@ static __global__ __launch_bounds__(KBEST_WAVES * 64) void kbest_kernel(int L, i
     for (int c = threadIdx.x; c < n; c += NT) { tv[c * K] = 1.f; tk[c * K] = -1; }                    // the sentence's leaves
     __syncthreads();                                 // also orders the fills before the stores below (same workgroup, same addresses)
     if (n == 0) return;
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
 
     for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level, cn = kbest_count(level, K);
+        const int off = t.off(level), mine = n - level, cn = kbest_count(level, K);
         const bool an = lane < level, an1 = LONG && lane + 64 < level;
-        const float* rows = Sp + (size_t)B * lvl_base[level] + (size_t)b * (L - level) * level;
+        const float* rows = Sp + t.row(level, 0);
         for (int pos = wave; pos < mine; pos += KBEST_WAVES) {             // operands live on lower levels: final since the last barrier
             float s, s1;
             const float smax = load_split_scores<LONG>(rows + (size_t)pos * level, level, lane, s, s1);
             const int k0 = lane, k1 = lane + 64;
-            const int lo0 = (coff(k0) + pos) * K, ro0 = an ? (coff(level - k0 - 1) + pos + k0 + 1) * K : 0;
-            const int lo1 = an1 ? (coff(k1) + pos) * K : 0, ro1 = an1 ? (coff(level - k1 - 1) + pos + k1 + 1) * K : 0;
+            const int lo0 = t.left(level, pos, k0) * K, ro0 = an ? t.right(level, pos, k0) * K : 0;
+            const int lo1 = an1 ? t.left(level, pos, k1) * K : 0, ro1 = an1 ? t.right(level, pos, k1) * K : 0;
             const int cl0 = an ? kbest_count(k0, K) : 0, cr0 = an ? kbest_count(level - k0 - 1, K) : 0;
             const int cl1 = an1 ? kbest_count(k1, K) : 0, cr1 = an1 ? kbest_count(level - k1 - 1, K) : 0;
             uint64_t p0 = 0, p1 = 0;
@@ -125,28 +130,18 @@ static __global__ __launch_bounds__(KBEST_WAVES * 64) void kbest_kernel(int L, i
         __syncthreads();
     }
 
-    const int root = coff(n - 1) * K;
+    const int root = t.root() * K;
     if ((int)threadIdx.x < nroot) {                  // a lane per tree: its score, and its walk on a stack of its own
-        const int t = threadIdx.x;
-        scores[(size_t)b * K + t] = tv[root + t] - (float)n;
+        const int tree = threadIdx.x;
+        scores[(size_t)b * K + tree] = tv[root + tree] - (float)n;
         if (spans && n > 1)
-            walk_spans<true>(n, t, stk + (size_t)t * 4 * (L + 1), spans + ((size_t)b * K + t) * (L - 1) * 2,
+            walk_spans<true>(n, tree, stk + tree * lay.stack_ints, spans + ((size_t)b * K + tree) * (L - 1) * 2,
                              [&](int level, int pos, int rank, int& lr, int& rr) {
-                                 const int key = tk[chart_cell(L, C, level, pos) * K + rank];
+                                 const int key = tk[t.cell(level, pos) * K + rank];
                                  lr = (key >> 4) & 15; rr = key & 15;
                                  return key >> 8;
                              });
     }
-}
-
-// Bytes of the K walk stacks, and of one sentence's table.
-static inline size_t kbest_stack_bytes(int L, int K) { return (size_t)K * 4 * (L + 1) * sizeof(int32_t); }
-static inline size_t kbest_table_bytes(int C, int K) { return (size_t)C * K * (sizeof(float) + sizeof(int32_t)); }
-// The table lives in LDS when it fits the CU's 160 KiB beside the stacks.
-static inline bool kbest_in_lds(int L, int C, int K) { return kbest_table_bytes(C, K) + kbest_stack_bytes(L, K) <= (size_t)160 * 1024; }
-// Dynamic LDS of the kernel.
-static inline size_t kbest_lds(int L, int C, int K) {
-    return (kbest_in_lds(L, C, K) ? kbest_table_bytes(C, K) : 0) + kbest_stack_bytes(L, K);
 }
 
 }  // namespace cliora

@@ -7,17 +7,22 @@
 //   outside   be[(n - 1, 0)] = 0,  be[cell] = logsumexp over its n - 1 - level uses of be[parent] + al[sibling] + r[parent, split]
 //   posterior mu[cell] = exp(al + be - log_z)
 //   MBR       v[leaf] = 0,  v[cell] = max_k(v[left] + v[right]) + mu[cell] in fp32, first maximum wins; the walk of cky_kernel
-//             (wave_first_max and emit_spans of decode_kernels.hpp, which cky_kernel calls too).
+//             (best_split and emit_spans of decode_kernels.hpp, which cky_kernel calls too).
+// The pieces, each written once for this header and the four over it (sample_, constrained_, bracket_grad_, expectation_kernels.hpp):
+// split_terms + inside_lse (a cell's inside terms and their reduction: post_inside, con_inside, the expectation's inside loop, the
+// sampler's draws), cell_use (a cell's uses: every outside pass), post_outside<LONG, MASKED> (outside table and posteriors: here and
+// constrained_kernel), zero_split_rows (the two gradient entries); the geometry (Tri), the first-maximum step
+// (best_split) and the walk are decode_kernels.hpp's.
 // Gather form throughout: a wavefront owns a cell and sums what the cell reads, a lane per split (inside, MBR) or per use (outside),
 // a second one at lane + 64 in the LONG instance (64 < L <= 128); no cell is ever added into.  The uses of a cell are closed forms
-// (long plans build no use lists):
+// (cell_use; long plans build no use lists):
 //   as a LEFT child, right sibling (j, pos + level + 1), j = 0 .. n - 2 - pos - level: parent (level + j + 1, pos), its split `level`;
 //   as a RIGHT child, left sibling (j, pos - j - 1), j = 0 .. pos - 1: parent (level + j + 1, pos - j - 1), its split j.
 //
 // Tables: al and be are fp64 (post_t).  Every cell has a split with r = 0, so 0 <= al <= log(Catalan(n - 1)) < 176 at 128 words: an
 // fp32 ulp there is 1.5e-5, a sixth of the bound on mu, and every level's rounding enters the exponent of mu; fp64 leaves the
 // rounding of the two fp32 outputs as the only error (the decision and its figures: DESIGN.md section 15).  The outside table holds be - rowmax(cell), which is what a child reads (be[parent] + r[parent, k] = (be[parent] -
-// max[parent]) + Sp[.]), so there is no table of row maxima: 16 C bytes + 16 L + 12 = 131 KiB at L 128, inside the CU's 160 KiB.
+// max[parent]) + Sp[.]), so there is no table of row maxima: PostLds, 16 C bytes + 16 L + 12 = 131 KiB at L 128, inside the CU's 160 KiB.
 // The MBR pass runs after the last read of al / be and keeps its value and split tables (8 C bytes) in their place.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,38 +56,130 @@ __device__ __forceinline__ post_t post_wave_lse(post_t t0, post_t t1) {
     return m + log(post_wave_sum(e));
 }
 
-// The inside table of sentence b's n words, levels up: al[leaf] = 0 is the caller's (before a barrier), al[cell] = logsumexp_k(al[left]
+// post_wave_lse for terms that may all be -inf (a masked pass): the wave skips the reduction then (the ballot is the same in every
+// lane), so -inf stays -inf and no NaN is formed.
+template <bool LONG>
+__device__ __forceinline__ post_t con_wave_lse(post_t t0, post_t t1) {
+    const post_t ninf = -INFINITY;
+    if (!__ballot(t0 > ninf || (LONG && t1 > ninf))) return ninf;
+    return post_wave_lse<LONG>(t0, t1);
+}
+constexpr int CON_ALLOWED = 1, CON_REQUIRED = 2;     // bits of a cell's mask byte (constrained_kernels.hpp)
+
+// This lane's splits of cell (level, pos), lane and (an1: LONG) lane + 64: the operand cells (l, q), r = (post_t)s - (post_t)smax
+// formed in fp64, and the row maximum.  The one former of the inside terms: post_inside, con_inside (constrained_kernels.hpp), the
+// inside loop of tree_expectation_kernel and the draws of sample_trees_kernel.
+struct SplitTerms {
+    bool an, an1;
+    int l0, q0, l1, q1;
+    post_t r0, r1;
+    float smax;
+    // al[left] + al[right] + r in table `tab`; -inf in a lane without the split
+    __device__ __forceinline__ post_t t0(const post_t* tab) const { return an ? tab[l0] + tab[q0] + r0 : (post_t)-INFINITY; }
+    __device__ __forceinline__ post_t t1(const post_t* tab) const { return an1 ? tab[l1] + tab[q1] + r1 : (post_t)-INFINITY; }
+};
+template <bool LONG>
+__device__ __forceinline__ SplitTerms split_terms(const Tri& t, int level, int pos, int lane) {
+    float s, s1;
+    const float smax = load_split_scores<LONG>(t.Sp + t.row(level, pos), level, lane, s, s1);
+    return {lane < level, LONG && lane + 64 < level, t.left(level, pos, lane), t.right(level, pos, lane), t.left(level, pos, lane + 64),
+            t.right(level, pos, lane + 64), (post_t)s - (post_t)smax, (post_t)s1 - (post_t)smax, smax};
+}
+// al[cell] from the lanes' terms t0 / t1 of SplitTerms: the one reduction call of every inside pass.  MASKED: they may all be -inf.
+template <bool LONG, bool MASKED = false>
+__device__ __forceinline__ post_t inside_lse(post_t t0, post_t t1) {
+    return MASKED ? con_wave_lse<LONG>(t0, t1) : post_wave_lse<LONG>(t0, t1);
+}
+
+// The inside table of sentence t's n words, levels up: al[leaf] = 0 is the caller's (before a barrier), al[cell] = logsumexp_k(al[left]
 // + al[right] + beta r[cell, k]) with beta r formed in fp64 -- beta = 1 multiplies exactly, so cliora_span_posteriors' table is what
 // it was before the tree sampler (sample_kernels.hpp) shared it.  Called by every thread of a workgroup of POST_WAVES wavefronts: a
-// wavefront per cell, one barrier per level, the last one before it returns.  lvl: the plan's level bases, in LDS.
+// wavefront per cell, one barrier per level, the last one before it returns.  t.lvl: the plan's level bases, in LDS.
 template <bool LONG>
-__device__ __forceinline__ void post_inside(post_t* al, const int32_t* lvl, int L, int C, int B, int b, int n,
-                                            const float* __restrict__ Sp, post_t beta) {
-    const post_t ninf = -INFINITY;
+__device__ __forceinline__ void post_inside(post_t* al, const Tri& t, post_t beta) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
-    for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const bool an = lane < level, an1 = LONG && lane + 64 < level;
-            float s, s1;
-            const float smax = load_split_scores<LONG>(Sp + (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level, level, lane, s, s1);
-            post_t t0 = ninf, t1 = ninf;
-            if (an) t0 = al[coff(lane) + pos] + al[coff(level - lane - 1) + pos + lane + 1] + beta * ((post_t)s - (post_t)smax);
-            if (an1) t1 = al[coff(lane + 64) + pos] + al[coff(level - lane - 65) + pos + lane + 65] + beta * ((post_t)s1 - (post_t)smax);
-            const post_t a = post_wave_lse<LONG>(t0, t1);
-            if (lane == 0) al[off + pos] = a;
+    for (int level = 1; level < t.n; ++level) {
+        for (int pos = wave; pos < t.n - level; pos += POST_WAVES) {
+            SplitTerms x = split_terms<LONG>(t, level, pos, lane);
+            x.r0 = beta * x.r0; x.r1 = beta * x.r1;
+            const post_t a = inside_lse<LONG>(x.t0(al), x.t1(al));
+            if (lane == 0) al[t.cell(level, pos)] = a;
         }
         __syncthreads();
     }
 }
+
+// Use u of cell (level, pos), u = 0 .. cell_uses(t, level) - 1, by the closed forms of the header: the parent cell, the sibling
+// cell and the index in Sp of the parent's score of that split.  The one enumeration of every outside pass.
+struct CellUse { int parent, sib; size_t score; };
+__device__ __forceinline__ int cell_uses(const Tri& t, int level) { return t.n - 1 - level; }
+__device__ __forceinline__ CellUse cell_use(const Tri& t, int level, int pos, int u) {
+    const int nr = t.n - 1 - pos - level;            // its uses as a left child
+    int plevel, ppos, k, sib;
+    if (u < nr) { plevel = level + u + 1; ppos = pos; k = level; sib = t.cell(u, pos + level + 1); }
+    else { const int j = u - nr; plevel = level + j + 1; ppos = pos - j - 1; k = j; sib = t.cell(j, ppos); }
+    return {t.cell(plevel, ppos), sib, t.row(plevel, ppos) + k};
+}
+
+// The outside table and the posteriors of sentence t, levels down, from its inside table al and lz = al[root]: be holds be - rowmax,
+// mu[cell] = exp(al + be - lz) is stored as each cell's be is known.  MASKED (constrained_kernel): a cell without CON_ALLOWED in
+// mask is skipped -- be = -inf, its mu stays the caller's 0 --, the terms may all be -inf, and a CON_REQUIRED cell has mu = 1.
+// Called by every thread of the workgroup; one barrier per level, the last one before it returns.
+template <bool LONG, bool MASKED>
+__device__ __forceinline__ void post_outside(const Tri& t, const post_t* al, post_t* be, const unsigned char* mask, post_t lz, float* mu) {
+    const post_t ninf = -INFINITY;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int level = t.n - 1; level >= 0; --level) {
+        for (int pos = wave; pos < t.n - level; pos += POST_WAVES) {
+            const int cell = t.cell(level, pos), mk = MASKED ? mask[cell] : CON_ALLOWED;
+            if (!(mk & CON_ALLOWED)) {                                      // its mu stays 0
+                if (lane == 0 && level > 0) be[cell] = ninf;
+                continue;
+            }
+            post_t bt = 0;                                                  // the sentence's root
+            if (level < t.n - 1) {
+                const int cnt = cell_uses(t, level);
+                auto term = [&](int u) -> post_t {
+                    const CellUse x = cell_use(t, level, pos, u);
+                    return be[x.parent] + al[x.sib] + (post_t)t.Sp[x.score];
+                };
+                const post_t t0 = lane < cnt ? term(lane) : ninf;
+                const post_t t1 = LONG && lane + 64 < cnt ? term(lane + 64) : ninf;
+                bt = MASKED ? con_wave_lse<LONG>(t0, t1) : post_wave_lse<LONG>(t0, t1);
+            }
+            if (level > 0) {                                                // what the children read: be - rowmax
+                float s, s1;
+                const float smax = load_split_scores<LONG>(t.Sp + t.row(level, pos), level, lane, s, s1);
+                if (lane == 0) be[cell] = bt - (post_t)smax;
+            }
+            if (lane == 0) mu[cell] = (mk & CON_REQUIRED) ? 1.f : (float)exp(al[cell] + bt - lz);
+        }
+        __syncthreads();
+    }
+}
+
+// Every split-score row of sentence t in G (the gradient entries' output) <- 0; a level's rows of one sentence are contiguous.
+template <int NT>
+__device__ __forceinline__ void zero_split_rows(float* __restrict__ G, const Tri& t) {
+    for (int level = 1; level < t.L; ++level) {
+        float* g = G + t.row(level, 0);
+        for (int i = threadIdx.x; i < (t.L - level) * level; i += NT) g[i] = 0.f;
+    }
+}
+
+// Dynamic LDS of span_posteriors_kernel for a chart of length L: al (C), be (C) post_t; lvl (L) ints; the walk stack.  The MBR pass
+// keeps val and bsp (C each) in al's place.
+struct PostLds {
+    int L, C;
+    size_t al = 0, be = al + (size_t)C * sizeof(post_t), lvl = be + (size_t)C * sizeof(post_t), stk = lvl + (size_t)L * sizeof(int32_t);
+    size_t total = stk + walk_stack_bytes(L), val = al, bsp = val + (size_t)C * sizeof(float);
+};
 
 // One workgroup per sentence; POST_WAVES wavefronts, one cell each per turn, one barrier per level of each pass.
 // lengths (B) or NULL (every sentence has L words).  marg (B, C): mu in the cell order of inside_s, exactly 0 outside the sentence's
 // triangle; log_z (B).  split (B, C) / spans (B, L-1, 2), either NULL: the MBR tree in cky_kernel's layout (-1 at the leaves
 // and outside the triangle; n - 1 spans, children before parents, (-1, -1) beyond).  A length outside [1, L]: mu = 0, log_z = 0,
 // every row -1, one count in *status, no chart read.
-// LDS: al (C), be (C) post_t; lvl (L) ints; walk stack 3 (L + 1) ints.
 template <bool LONG = false>
 static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel(int L, int C, const int32_t* __restrict__ lvl_base, int B,
                                                                                  const float* __restrict__ Sp,
@@ -91,87 +188,47 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void span_posteriors_kernel
                                                                                  int32_t* __restrict__ status, float* marg,
                                                                                  float* __restrict__ log_z) {
     extern __shared__ __attribute__((aligned(16))) unsigned char post_smem[];
-    post_t* al = reinterpret_cast<post_t*>(post_smem);
-    post_t* be = al + C;
-    int32_t* lvl = reinterpret_cast<int32_t*>(be + C);
-    int32_t* stk = lvl + L;
+    const PostLds lay{L, C};
+    post_t* al = reinterpret_cast<post_t*>(post_smem + lay.al);
+    post_t* be = reinterpret_cast<post_t*>(post_smem + lay.be);
     constexpr int NT = POST_WAVES * 64;
-    const post_t ninf = -INFINITY;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int n = lengths ? lengths[b] : L;
-    if (n < 1 || n > L) { n = 0; if (threadIdx.x == 0) atomicAdd(status, 1); }
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
-    auto row_of = [&](int level, int pos) { return (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level; };
+    bool bad;
+    const int n = sentence_length(lengths, b, L, bad);
+    if (bad && threadIdx.x == 0) atomicAdd(status, 1);
+    Tri t{L, C, B, b, n, lvl_base, Sp};
     float* mu = marg + (size_t)b * C;
     for (int c = threadIdx.x; c < C; c += NT) mu[c] = 0.f;
     if (split) for (int c = threadIdx.x; c < C; c += NT) split[(size_t)b * C + c] = -1;
     if (spans) for (int i = threadIdx.x; i < 2 * (L - 1); i += NT) spans[(size_t)b * (L - 1) * 2 + i] = -1;
-    for (int c = threadIdx.x; c < L; c += NT) lvl[c] = lvl_base[c];
+    stage_levels<NT>(t, reinterpret_cast<int32_t*>(post_smem + lay.lvl));
     for (int c = threadIdx.x; c < n; c += NT) al[c] = 0;                                            // the sentence's leaves
     if (n == 0 && threadIdx.x == 0) log_z[b] = 0.f;
     __syncthreads();                                 // also orders the fills before the stores below (same workgroup, same addresses)
     if (n == 0) return;
 
-    post_inside<LONG>(al, lvl, L, C, B, b, n, Sp, (post_t)1);
-    const post_t lz = al[coff(n - 1)];
+    post_inside<LONG>(al, t, (post_t)1);
+    const post_t lz = al[t.root()];
     if (threadIdx.x == 0) log_z[b] = (float)lz;
-
-    // ---- outside, levels down; mu as each cell's be is known
-    for (int level = n - 1; level >= 0; --level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            post_t bt = 0;                                                  // the sentence's root
-            if (level < n - 1) {
-                const int nr = n - 1 - pos - level, cnt = n - 1 - level;    // uses as a left child; all uses
-                auto term = [&](int u) -> post_t {
-                    int plevel, ppos, k, sib;
-                    if (u < nr) { plevel = level + u + 1; ppos = pos; k = level; sib = coff(u) + pos + level + 1; }
-                    else { const int j = u - nr; plevel = level + j + 1; ppos = pos - j - 1; k = j; sib = coff(j) + ppos; }
-                    return be[coff(plevel) + ppos] + al[sib] + (post_t)Sp[row_of(plevel, ppos) + k];
-                };
-                const post_t t0 = lane < cnt ? term(lane) : ninf;
-                const post_t t1 = LONG && lane + 64 < cnt ? term(lane + 64) : ninf;
-                bt = post_wave_lse<LONG>(t0, t1);
-            }
-            if (level > 0) {                                                // what the children read: be - rowmax
-                float s, s1;
-                const float smax = load_split_scores<LONG>(Sp + row_of(level, pos), level, lane, s, s1);
-                if (lane == 0) be[off + pos] = bt - (post_t)smax;
-            }
-            if (lane == 0) mu[off + pos] = (float)exp(al[off + pos] + bt - lz);
-        }
-        __syncthreads();
-    }
+    post_outside<LONG, false>(t, al, be, nullptr, lz, mu);
     if (!split && !spans) return;
 
     // ---- MBR, levels up: al / be are dead, the value and split tables take their place
-    float* val = reinterpret_cast<float*>(post_smem);
-    int32_t* bsp = reinterpret_cast<int32_t*>(post_smem) + C;
+    float* val = reinterpret_cast<float*>(post_smem + lay.val);
+    int32_t* bsp = reinterpret_cast<int32_t*>(post_smem + lay.bsp);
     for (int c = threadIdx.x; c < n; c += NT) { val[c] = 0.f; bsp[c] = -1; }
     __syncthreads();
     for (int level = 1; level < n; ++level) {
-        const int off = coff(level), mine = n - level;
-        for (int pos = wave; pos < mine; pos += POST_WAVES) {
-            const bool an = lane < level;
-            float best = -INFINITY; int bi = an ? lane : 0x7fffffff;
-            if (an) best = val[coff(lane) + pos] + val[coff(level - lane - 1) + pos + lane + 1];
-            if constexpr (LONG) {
-                if (lane + 64 < level) {
-                    const float c1 = val[coff(lane + 64) + pos] + val[coff(level - lane - 65) + pos + lane + 65];
-                    if (c1 > best) { best = c1; bi = lane + 64; }
-                }
-            }
-            wave_first_max(best, bi);
-            if (lane == 0) { val[off + pos] = best + mu[off + pos]; bsp[off + pos] = bi; if (split) split[(size_t)b * C + off + pos] = bi; }
+        for (int pos = wave; pos < n - level; pos += POST_WAVES) {
+            const int cell = t.cell(level, pos);
+            float best; int bi;
+            best_split<LONG>(val, t.left(level, pos, lane), t.right(level, pos, lane), t.left(level, pos, lane + 64),
+                             t.right(level, pos, lane + 64), -0.f, -0.f, level, lane, best, bi);
+            if (lane == 0) { val[cell] = best + mu[cell]; bsp[cell] = bi; if (split) split[(size_t)b * C + cell] = bi; }
         }
         __syncthreads();
     }
-    if (spans && threadIdx.x == 0 && n > 1) emit_spans(bsp, L, C, n, stk, spans + (size_t)b * (L - 1) * 2);
-}
-
-// Dynamic LDS of the kernel for a chart of length L.
-static inline size_t span_posteriors_lds(int L, int C) {
-    return (size_t)2 * C * sizeof(post_t) + ((size_t)L + 3 * ((size_t)L + 1)) * sizeof(int32_t);
+    if (spans && threadIdx.x == 0 && n > 1) emit_spans(bsp, t, reinterpret_cast<int32_t*>(post_smem + lay.stk), spans + (size_t)b * (L - 1) * 2);
 }
 
 }  // namespace cliora

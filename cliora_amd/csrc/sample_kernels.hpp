@@ -1,7 +1,7 @@
 // Draws from the distribution over binary trees whose mode cky_kernel returns (cliora_sample_trees; include/cliora_chart.h, DESIGN.md
 // section 18).  The potentials are those of posterior_kernels.hpp, r[cell, k] = Sp[row(cell) + k] - max_k Sp[row(cell) + .], scaled by
 // an inverse temperature beta >= 0: a tree weighs exp(beta * sum of r over its internal cells).  Per sentence of n words:
-//   inside   post_inside (posterior_kernels.hpp): al[leaf] = 0, al[cell] = logsumexp_k(al[left] + al[right] + beta r[cell, k]), fp64;
+//   inside   post_inside (posterior_kernels.hpp; a draw forms its weights from the same split_terms): al[leaf] = 0, al[cell] = logsumexp_k(al[left] + al[right] + beta r[cell, k]), fp64;
 //            log_z = al[(n - 1, 0)].
 //   draws    sample s walks from the root.  At an internal cell (level, pos), N = level splits:
 //              w_k = exp(al[left_k] + al[right_k] + beta r_k - al[cell]),  c_k = w_0 + .. + w_k (a fixed-order inclusive scan),
@@ -35,7 +35,13 @@ __device__ __forceinline__ post_t post_wave_scan(post_t v, int lane) {
 // lengths (B) or NULL; ids (B) or NULL (sentence id = b).  spans (B, S, L-1, 2) (NULL when L = 1): sample s's n - 1 constituents,
 // (-1, -1) beyond; log_prob (B, S); log_z (B).  A length outside [1, L]: every row -1, log_prob 0, log_z 0, one count in *status, no
 // chart read.  `split` is launch_decode's slot and always NULL here.
-// LDS: al (C) post_t; lvl (L) ints; POST_WAVES walk stacks of 4 (L + 1) ints.
+// LDS (SampleLds): al (C) post_t; lvl (L) ints; POST_WAVES walk stacks of 4 (L + 1) ints: 8 C + 4 L + POST_WAVES * 16 (L + 1) bytes,
+// 81 KiB at L 128.
+struct SampleLds {
+    int L, C;
+    size_t stack_ints = (size_t)4 * (L + 1), al = 0, lvl = al + (size_t)C * sizeof(post_t), stk = lvl + (size_t)L * sizeof(int32_t);
+    size_t total = stk + POST_WAVES * stack_ints * sizeof(int32_t);
+};
 template <bool LONG = false>
 static __global__ __launch_bounds__(POST_WAVES * 64) void sample_trees_kernel(int L, int C, const int32_t* __restrict__ lvl_base, int B,
                                                                               const float* __restrict__ Sp,
@@ -45,18 +51,20 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void sample_trees_kernel(in
                                                                               uint64_t first_sample, float beta_f,
                                                                               float* __restrict__ log_prob, float* __restrict__ log_z) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sample_smem[];
-    post_t* al = reinterpret_cast<post_t*>(sample_smem);
-    int32_t* lvl = reinterpret_cast<int32_t*>(al + C);
+    const SampleLds lay{L, C};
+    post_t* al = reinterpret_cast<post_t*>(sample_smem + lay.al);
     constexpr int NT = POST_WAVES * 64;
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int32_t* stk = lvl + L + (size_t)wave * 4 * (L + 1);
+    int32_t* stk = reinterpret_cast<int32_t*>(sample_smem + lay.stk) + wave * lay.stack_ints;
     const post_t beta = (post_t)beta_f;
     (void)split;
-    int n = lengths ? lengths[b] : L;
-    if (n < 1 || n > L) { n = 0; if (threadIdx.x == 0) atomicAdd(status, 1); }
+    bool bad;
+    const int n = sentence_length(lengths, b, L, bad);
+    if (bad && threadIdx.x == 0) atomicAdd(status, 1);
+    Tri t{L, C, B, b, n, lvl_base, Sp};
     const size_t rows = (size_t)2 * (L - 1);         // ints of one sample's spans
     if (spans) for (size_t i = threadIdx.x; i < (size_t)S * rows; i += NT) spans[(size_t)b * S * rows + i] = -1;
-    for (int c = threadIdx.x; c < L; c += NT) lvl[c] = lvl_base[c];
+    stage_levels<NT>(t, reinterpret_cast<int32_t*>(sample_smem + lay.lvl));
     for (int c = threadIdx.x; c < n; c += NT) al[c] = 0;                                            // the sentence's leaves
     if (n == 0) {
         for (int s = threadIdx.x; s < S; s += NT) log_prob[(size_t)b * S + s] = 0.f;
@@ -64,10 +72,9 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void sample_trees_kernel(in
     }
     __syncthreads();                                 // also orders the -1 fill before the stores below (same workgroup, same addresses)
     if (n == 0) return;
-    auto coff = [&](int level) { return chart_cell(L, C, level, 0); };
 
-    post_inside<LONG>(al, lvl, L, C, B, b, n, Sp, beta);
-    const post_t lz = al[coff(n - 1)];
+    post_inside<LONG>(al, t, beta);
+    const post_t lz = al[t.root()];
     if (threadIdx.x == 0) log_z[b] = (float)lz;
 
     const uint32_t sid = ids ? (uint32_t)ids[b] : (uint32_t)b;
@@ -81,20 +88,12 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void sample_trees_kernel(in
             const int level = stk[4 * sp], pos = stk[4 * sp + 1], phase = stk[4 * sp + 2];
             if (level == 0) { --sp; continue; }
             if (phase == 0) {                        // draw the cell's split
-                const bool an = lane < level, an1 = LONG && lane + 64 < level;
-                float sc, sc1;
-                const float smax = load_split_scores<LONG>(Sp + (size_t)B * lvl[level] + ((size_t)b * (L - level) + pos) * level, level,
-                                                           lane, sc, sc1);
-                const post_t here = al[coff(level) + pos];
+                const SplitTerms x = split_terms<LONG>(t, level, pos, lane);
+                const bool an = x.an, an1 = x.an1;
+                const post_t here = al[t.cell(level, pos)];
                 post_t br0 = 0, br1 = 0, w0 = 0, w1 = 0;
-                if (an) {
-                    br0 = beta * ((post_t)sc - (post_t)smax);
-                    w0 = exp(al[coff(lane) + pos] + al[coff(level - lane - 1) + pos + lane + 1] + br0 - here);
-                }
-                if (an1) {
-                    br1 = beta * ((post_t)sc1 - (post_t)smax);
-                    w1 = exp(al[coff(lane + 64) + pos] + al[coff(level - lane - 65) + pos + lane + 65] + br1 - here);
-                }
+                if (an) { br0 = beta * x.r0; w0 = exp(al[x.l0] + al[x.q0] + br0 - here); }
+                if (an1) { br1 = beta * x.r1; w1 = exp(al[x.l1] + al[x.q1] + br1 - here); }
                 const post_t c0 = post_wave_scan(w0, lane);
                 post_t total = __shfl(c0, 63);       // lanes without a split add 0: lane 63 holds c_{N-1} of its half
                 post_t c1 = 0;
@@ -121,11 +120,6 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void sample_trees_kernel(in
         }
         if (lane == 0) log_prob[(size_t)b * S + s] = (float)(acc - lz);
     }
-}
-
-// Dynamic LDS of the kernel for a chart of length L: 8 C + 4 L + POST_WAVES * 16 (L + 1) bytes, 81 KiB at L 128.
-static inline size_t sample_trees_lds(int L, int C) {
-    return (size_t)C * sizeof(post_t) + ((size_t)L + (size_t)POST_WAVES * 4 * ((size_t)L + 1)) * sizeof(int32_t);
 }
 
 }  // namespace cliora

@@ -144,6 +144,30 @@ def test_no_brackets_is_the_other_decoders_bit_for_bit(L):
         assert (got['log_prob'] == 0).all() and not np.signbit(got['log_prob']).any(), what
 
 
+@pytest.mark.parametrize('L', [66, 128])
+def test_no_brackets_is_the_other_decoders_bit_for_bit_long(L):
+    """The same comparison in a long chart (B 2, D 16): L 66 is the smallest in which a lane carries a second split (level 65) and a
+    second use (the leaves' 65), L 128 the plan's limit -- every sentence at L words, then lengths (L, 65)."""
+    from cliora_amd.kbest import kbest_spans
+    from cliora_amd.ragged import cky_spans_ragged
+    B = 2
+    m = _uniform(L, B)['m']
+    for lengths in (None, [L, 65]):
+        what = 'L %d, lengths %r' % (L, lengths)
+        lt = None if lengths is None else torch.tensor(lengths, dtype=torch.int32)
+        post = m.span_posteriors(lt)
+        log_z, marg = post.log_z.cpu().numpy(), post.marginals.cpu().numpy()
+        score = kbest_spans(m, 1, lt).scores.cpu().numpy()[:, 0]
+        spans = (m.cky_spans_device() if lengths is None else cky_spans_ragged(m, lt)[0]).cpu().numpy()
+        got = _parse(m, None, lengths)
+        assert got['status'] == [0] and got['feasible'].tolist() == [1] * B, what
+        assert got['spans'].shape == (B, L - 1, 2) and np.array_equal(got['spans'], spans), what
+        assert np.array_equal(_bits(got['score']), _bits(score)), what
+        assert np.array_equal(_bits(got['log_z']), _bits(log_z)) and np.array_equal(_bits(got['log_z_c']), _bits(log_z)), what
+        assert np.array_equal(_bits(got['marginals']), _bits(marg)), what
+        assert (got['log_prob'] == 0).all() and not np.signbit(got['log_prob']).any(), what
+
+
 # ---- 2. against constrained_numpy ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('L', CC.NUMPY_LENGTHS)
 def test_bracket_sets_are_constrained_numpy(L):
