@@ -91,6 +91,9 @@ ABI = {
     'cliora_kbest_spans': (i32, [vp, vp, vp, i32] + [vp] * 6),
     'cliora_sample_trees': (i32, [vp, vp, vp, vp, i32, u64, u64, f32] + [vp] * 5),
     'cliora_constrained_parse': (i32, [vp, vp, vp, vp, i32] + [vp] * 9),
+    'cliora_kbest_constrained_scratch_bytes': (sz, [vp, i32, i32]),
+    'cliora_kbest_spans_constrained': (i32, [vp, vp, vp, vp, i32, i32] + [vp] * 7),
+    'cliora_sample_trees_constrained': (i32, [vp, vp, vp, vp, vp, i32, i32, u64, u64, f32] + [vp] * 7),
     'cliora_plan_split_score_count': (sz, [vp]),
     'cliora_bracket_grad': (i32, [vp, vp, vp, vp, i32] + [vp] * 6),
     'cliora_tree_expectation': (i32, [vp] * 12),

@@ -15,6 +15,12 @@ A cell [i, j] is allowed iff it crosses no required bracket [s, e] (i < s <= j <
 a binary tree "nothing crosses [s, e]" is "[s, e] is a constituent", so the qualifying trees are the trees built from allowed cells.
 ``constrained_numpy`` restates the kernel for tests: the best tree in fp32 in the kernel's operation order, the rest in fp64 from the
 definitions.
+
+The other two questions about the conditioned distribution (cliora_kbest_spans_constrained, cliora_sample_trees_constrained; DESIGN.md
+section 25): its K best trees and draws from it, with their restatements ``constrained_kbest_numpy`` and ``constrained_sample_numpy``.
+
+    kb = constrained_kbest(net.diora, pack_brackets(req), 16)           # ConstrainedKBest: rank 0 is constrained_parse's tree
+    ts = constrained_samples(net.diora, pack_brackets(req), 64, seed=7) # every draw keeps the brackets; log_prob given them
 """
 import collections
 import ctypes as C
@@ -22,10 +28,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, kbest as _kbest, sample as _sample
 from ._lib import ptr_or_null as _p, stream as _stream
-from .diora import span_buffer
-from .posterior import cell_id, cell_uses
+from .diora import span_buffer, workspace_slices
+from .posterior import cell_id, cell_uses, inside_numpy
 
 MAX_M = 256              # csrc/constrained_kernels.hpp CON_MAX_M: bracket rows per sentence
 REQUIRED, FORBIDDEN = 1, 0
@@ -130,11 +136,11 @@ def host_results(cp):
             int(host[nsp + 2 * nb:].sum()))
 
 
-def refuse_rejected(count):
-    """The one message for a non-zero status of cliora_constrained_parse."""
+def refuse_rejected(count, entry='cliora_constrained_parse'):
+    """The one message for a non-zero status of cliora_constrained_parse and of the other entries that take brackets."""
     if count:
-        raise _lib.ChartLibError('cliora_constrained_parse rejected %d sentence(s): a length outside the chart, or a bracket that is '
-                                 'not 0 <= start <= end < length with kind 0 or 1' % count)
+        raise _lib.ChartLibError('%s rejected %d sentence(s): a length outside the chart, or a bracket that is '
+                                 'not 0 <= start <= end < length with kind 0 or 1' % (entry, count))
 
 
 # ---- the restatement --------------------------------------------------------------------------------------------------------------
@@ -245,3 +251,229 @@ def constrained_numpy(pair_s, lengths, brackets, L=None):
                 if allowed[level, pos]:
                     mu[b, cell_id(L, level, pos)] = 1.0 if required[level, pos] else np.exp(al[level, pos] + be[level, pos] - log_zc[b])
     return ConstrainedParse(spans, score, log_z, log_zc, log_prob, feasible, mu, status)
+
+
+# ---- the K best trees and sampled trees under brackets ------------------------------------------------------------------------------
+class ConstrainedKBest(_kbest.KBest):
+    """``kbest.KBest`` of the trees that keep the brackets (cliora_kbest_spans_constrained) plus feasible (B,)
+    int32: 0 where no tree qualifies (count 0) and for a rejected sentence.  count (B,): min(k, the number of qualifying trees);
+    status counts bad lengths AND bad rows, which the caller must check (``refuse_rejected``).  Device tensors; nothing is synchronised."""
+
+    def __init__(self, spans, scores, count, status, feasible):
+        _kbest.KBest.__init__(self, spans, scores, count, status)
+        self.feasible = feasible
+
+
+# ``sample.TreeSamples`` of the draws given the brackets (cliora_sample_trees_constrained) plus log_z_c (B,) fp32 -- the constrained
+# log-partition at beta; log_prob = beta * (sum of r over the draw's splits) - log_z_c -- and feasible (B,) int32.  Without a qualifying
+# tree: rows -1, log_prob and log_z_c -inf, log_z the real value.  Device tensors; nothing is synchronised.
+ConstrainedTreeSamples = collections.namedtuple('ConstrainedTreeSamples', _sample.TreeSamples._fields + ('log_z_c', 'feasible'))
+
+
+def _bracket_args(diora, brackets, lengths, ids=None):
+    """The checks constrained_parse makes of brackets / lengths (and ids), on the chart's device: -> (dev, nws, M, lengths, brackets, ids)."""
+    plan, wss = diora._plan, diora._wss
+    nws, dev, rows = len(wss), wss[0].device, plan.B * len(wss)
+    for name, t in (('lengths', lengths), ('ids', ids)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != rows):
+            raise ValueError('%s must be int32, one per sentence of the chart (%d)' % (name, rows))
+    M = 0
+    if brackets is not None:
+        if brackets.dtype != torch.int32 or brackets.dim() != 3 or brackets.shape[0] != rows or brackets.shape[2] != 3:
+            raise ValueError('brackets must be int32 (%d, M, 3)' % rows)
+        M = int(brackets.shape[1])                         # a bad M is the library's to refuse, with its message
+    with torch.cuda.device(dev):
+        lengths, brackets, ids = (None if t is None else t.to(dev).contiguous() for t in (lengths, brackets, ids))
+    return dev, nws, M, lengths, brackets, ids
+
+
+def constrained_kbest(diora, brackets, k, lengths=None):
+    """cliora_kbest_spans_constrained on a chart module after its forward: the k best trees (1 .. 16) among those that keep the
+    brackets -- an int32 tensor (B, M, 3) of rows (start, end, kind) (``pack_brackets``), or None for no bracket at all, which gives
+    ``kbest.kbest_spans``' tensors bit for bit.  Rank 0 is ``constrained_parse``'s tree and score.  lengths: None or an int32 tensor (B,)
+    for a right-padded batch.  Allocates the scratch the library asks for.  -> ConstrainedKBest."""
+    plan = diora._plan
+    B, L = plan.B, plan.L
+    k = int(k)
+    dev, nws, M, lengths, brackets, _ = _bracket_args(diora, brackets, lengths)
+    with torch.cuda.device(dev):
+        width = max(k, 0)                                  # a bad k is the library's to refuse, with its message
+        spans = torch.empty((B * nws, width, L - 1, 2), dtype=torch.int32, device=dev)
+        scores = torch.empty((B * nws, width), dtype=torch.float32, device=dev)
+        count, feasible = (torch.empty(B * nws, dtype=torch.int32, device=dev) for _ in range(2))
+        status = torch.zeros(nws, dtype=torch.int32, device=dev)
+        need = _lib.fn('cliora_kbest_constrained_scratch_bytes')(plan.handle, k, M)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        for i, (ws, sl) in enumerate(workspace_slices(diora)):
+            _lib.call('cliora_kbest_spans_constrained', plan.handle, C.c_void_p(ws.data_ptr()),
+                      _p(lengths[sl]) if lengths is not None else None, _p(brackets[sl]) if M else None, M, k, _p(spans[sl]),
+                      C.c_void_p(scores[sl].data_ptr()), C.c_void_p(count[sl].data_ptr()), C.c_void_p(feasible[sl].data_ptr()),
+                      _p(scratch), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    return ConstrainedKBest(spans, scores, count, status, feasible)
+
+
+def constrained_samples(diora, brackets, S, seed, lengths=None, ids=None, first_sample=0, beta=1.0):
+    """cliora_sample_trees_constrained on a chart module after its forward: S trees per sentence (1 .. 2^20, numbered first_sample ..
+    first_sample + S - 1) drawn from the posterior over parses given the brackets, at inverse temperature beta.  brackets: as
+    ``constrained_kbest`` takes them; None gives ``sample.sample_spans``' spans, log_prob and log_z bit for bit.  lengths, ids: as
+    ``sample.sample_spans`` takes them.  -> ConstrainedTreeSamples."""
+    plan = diora._plan
+    B, L = plan.B, plan.L
+    S = int(S)
+    dev, nws, M, lengths, brackets, ids = _bracket_args(diora, brackets, lengths, ids)
+    with torch.cuda.device(dev):
+        if ids is None and nws > 1:
+            ids = torch.arange(B * nws, dtype=torch.int32, device=dev)
+        width = min(max(S, 0), _sample.MAX_S)              # a bad S is the library's to refuse, with its message
+        spans = torch.empty((B * nws, width, L - 1, 2), dtype=torch.int32, device=dev)
+        log_prob = torch.empty((B * nws, width), dtype=torch.float32, device=dev)
+        log_z, log_zc = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(2))
+        feasible = torch.empty(B * nws, dtype=torch.int32, device=dev)
+        status = torch.zeros(nws, dtype=torch.int32, device=dev)
+        for i, (ws, sl) in enumerate(workspace_slices(diora)):
+            _lib.call('cliora_sample_trees_constrained', plan.handle, C.c_void_p(ws.data_ptr()),
+                      _p(lengths[sl]) if lengths is not None else None, _p(ids[sl]) if ids is not None else None,
+                      _p(brackets[sl]) if M else None, M, S, int(seed) & (2 ** 64 - 1), int(first_sample) & (2 ** 64 - 1), float(beta),
+                      _p(spans[sl]), C.c_void_p(log_prob[sl].data_ptr()), C.c_void_p(log_zc[sl].data_ptr()),
+                      C.c_void_p(log_z[sl].data_ptr()), C.c_void_p(feasible[sl].data_ptr()), C.c_void_p(status[i:i + 1].data_ptr()),
+                      _stream())
+    return ConstrainedTreeSamples(spans, log_prob, log_z, status, log_zc, feasible)
+
+
+# ---- their restatements ---------------------------------------------------------------------------------------------------------------
+ConstrainedKBestNumpy = collections.namedtuple('ConstrainedKBestNumpy', 'spans scores count feasible status')
+ConstrainedSamplesNumpy = collections.namedtuple('ConstrainedSamplesNumpy', 'spans log_prob log_z log_z_c feasible margin status')
+
+
+def _chart_length(pair_s, lengths, L):
+    return (np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)) if L is None else L
+
+
+def constrained_kbest_numpy(pair_s, lengths, brackets, k, L=None):
+    """cliora_kbest_spans_constrained restated in fp32 in the kernel's operation order, for tests: ``kbest.kbest_numpy`` (its inputs,
+    its candidate expression and order: every candidate of a cell at once, (split, left rank, right rank) in key order, a stable sort
+    by value descending, the first k) with a cell's count from its children's, 0 at a cell ``allowed_cells`` disallows.  brackets
+    (B, M, 3) or None.  -> ConstrainedKBestNumpy as the kernel writes them; status: the number of rejected sentences."""
+    k = int(k)
+    if not 1 <= k <= _kbest.MAX_K:
+        raise ValueError('k must be in 1..%d' % _kbest.MAX_K)
+    lengths = [int(x) for x in lengths]
+    L = _chart_length(pair_s, lengths, L)
+    Bn = len(lengths)
+    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
+    spans = np.full((Bn, k, max(L - 1, 0), 2), -1, dtype=np.int32)
+    scores = np.full((Bn, k), -np.inf, dtype=np.float32)
+    count, feasible, status = np.zeros(Bn, dtype=np.int32), np.zeros(Bn, dtype=np.int32), 0
+    ii, jj = np.arange(k)[None, :, None], np.arange(k)[None, None, :]
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= L or any(bad_row(r, n) for r in brackets[b]):
+            status += 1
+            continue
+        allowed, _ = allowed_cells(n, brackets[b])
+        cnt = np.zeros((n, n), dtype=np.int64)                               # [level, pos]
+        cnt[0, :n] = allowed[0, :n]
+        val = np.full((n, n, k), -np.inf, dtype=np.float32)                  # [level, pos, rank]
+        val[0, :, 0] = 1.0
+        key = {}
+        for level in range(1, n):
+            s = np.asarray(pair_s[level][b], dtype=np.float32).reshape(-1, level)[:n - level]
+            rel = s - s.max(axis=1, keepdims=True)                           # over every split, allowed or not
+            ks = np.arange(level)
+            key[level] = np.zeros((n - level, k, 3), dtype=np.int64)
+            for pos in range(n - level):
+                if not allowed[level, pos]:
+                    continue
+                cl, cr = cnt[ks, pos], cnt[level - ks - 1, pos + ks + 1]
+                valid = ((ii < cl[:, None, None]) & (jj < cr[:, None, None])).reshape(-1)
+                kk, ci, cj = (a.reshape(-1)[valid] for a in np.broadcast_arrays(ks[:, None, None], ii, jj))
+                cand = (val[ks, pos][:, :, None] + val[level - ks - 1, pos + ks + 1][:, None, :]) + rel[pos][:, None, None]
+                cand = cand.reshape(-1)[valid]
+                top = np.argsort(-cand, kind='stable')[:k]
+                cnt[level, pos] = len(top)
+                val[level, pos, :len(top)] = cand[top]
+                key[level][pos, :len(top)] = np.stack([kk[top], ci[top], cj[top]], axis=1)
+        count[b] = cnt[n - 1, 0]
+        feasible[b] = count[b] > 0
+        scores[b, :count[b]] = val[n - 1, 0, :count[b]] - np.float32(n)
+        for t in range(count[b]):
+            rows = _kbest._walk(key, n, t)
+            spans[b, t, :len(rows)] = np.asarray(rows, dtype=np.int32).reshape(-1, 2)
+    return ConstrainedKBestNumpy(spans, scores, count, feasible, status)
+
+
+def choose_split(w, u, finite):
+    """The draw of one cell: w the weights of its N splits, u its uniform, finite[k] whether both children of split k have a finite
+    inside value (a split without has w_k = exactly 0).  split = #{k : c_k <= u c_{N-1}} over the inclusive sums c, clamped to the
+    largest k with finite[k] -- N - 1 where every child is finite, ``sample.sample_numpy``'s clamp.  -> (split, margin = the smallest
+    |u c_{N-1} - c_k| / c_{N-1})."""
+    c = np.cumsum(w)
+    thr = u * c[-1]
+    k = min(int((c <= thr).sum()), int(np.flatnonzero(finite)[-1]))
+    return k, float(np.abs(thr - c).min() / c[-1])
+
+
+def constrained_sample_numpy(pair_s, lengths, brackets, S, seed, ids=None, first_sample=0, beta=1.0, L=None):
+    """cliora_sample_trees_constrained restated in fp64 from the definitions, for tests: ``sample.sample_numpy`` (its inputs, its
+    ``draw_uniform`` and ``split_weights``) over the inside table of the cells ``allowed_cells`` allows.  brackets (B, M, 3) or None.
+    -> ConstrainedSamplesNumpy as the kernel writes them (log_prob = beta sum r - log_z_c; without a qualifying tree rows -1, log_prob
+    and log_z_c -inf; a rejected sentence the same with log_z 0); margin (B, S) as sample_numpy's; status: the rejected sentences."""
+    S = int(S)
+    if not 1 <= S <= _sample.MAX_S:
+        raise ValueError('S must be in 1..%d' % _sample.MAX_S)
+    beta = float(beta)
+    if not (beta >= 0 and np.isfinite(beta)):
+        raise ValueError('beta must be finite and >= 0')
+    lengths = [int(x) for x in lengths]
+    L = _chart_length(pair_s, lengths, L)
+    Bn = len(lengths)
+    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
+    ids = list(range(Bn)) if ids is None else [int(x) for x in ids]
+    spans = np.full((Bn, S, max(L - 1, 0), 2), -1, dtype=np.int32)
+    log_prob = np.full((Bn, S), -np.inf, dtype=np.float64)
+    log_z, log_zc = np.zeros(Bn, dtype=np.float64), np.full(Bn, -np.inf, dtype=np.float64)
+    feasible, status = np.zeros(Bn, dtype=np.int32), 0
+    margin = np.full((Bn, S), np.inf, dtype=np.float64)
+    samples = np.uint64(int(first_sample) & (2 ** 64 - 1)) + np.arange(S, dtype=np.uint64)
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= L or any(bad_row(r, n) for r in brackets[b]):
+            status += 1
+            continue
+        allowed, _ = allowed_cells(n, brackets[b])
+        r, au = inside_numpy(pair_s, b, n, beta)
+        al = np.full((n, n), -np.inf)
+        al[0, :n] = np.where(allowed[0, :n], 0.0, -np.inf)
+        for level in range(1, n):
+            k = np.arange(level)
+            for pos in range(n - level):
+                if allowed[level, pos]:
+                    al[level, pos] = _lse(al[k, pos] + al[level - k - 1, pos + k + 1] + beta * r[level, pos, :level])
+        log_z[b], log_zc[b] = au[n - 1, 0], al[n - 1, 0]
+        if not log_zc[b] > -np.inf:
+            continue
+        feasible[b] = 1
+        lv, ps = np.meshgrid(np.arange(n), np.arange(n), indexing='ij')
+        u = _sample.draw_uniform(lv[None], ps[None], samples[:, None, None], ids[b], seed)  # [sample, level, pos]
+        weights = {}                                  # of the cells a walk can reach: the finite ones
+        for s in range(S):
+            rows, acc, stack = [], 0.0, [(n - 1, 0, 0, 0)]
+            while stack:                              # the kernel's walk: draw, left subtree, right subtree, then the node
+                level, pos, phase, k = stack.pop()
+                if level == 0:
+                    continue
+                if phase == 0:
+                    if (level, pos) not in weights:
+                        ks = np.arange(level)
+                        weights[(level, pos)] = (_sample.split_weights(r, al, level, pos, beta),
+                                                 (al[ks, pos] + al[level - ks - 1, pos + ks + 1]) > -np.inf)
+                    w, finite = weights[(level, pos)]
+                    k, m = choose_split(w, u[s, level, pos], finite)
+                    margin[b, s] = min(margin[b, s], m)
+                    acc += beta * r[level, pos, k]
+                    stack += [(level, pos, 1, k), (k, pos, 0, 0)]
+                elif phase == 1:
+                    stack += [(level, pos, 2, k), (level - k - 1, pos + k + 1, 0, 0)]
+                else:
+                    rows.append((pos, pos + level))
+            spans[b, s, :len(rows)] = np.asarray(rows, dtype=np.int32).reshape(-1, 2)
+            log_prob[b, s] = acc - log_zc[b]
+    return ConstrainedSamplesNumpy(spans, log_prob, log_z, log_zc, feasible, margin, status)

@@ -2,7 +2,8 @@
 // parse under required and forbidden brackets, from the per-split scores of the last forward -- of every sentence of a chart, or of
 // each sentence's own triangle of a right-padded chart.  See include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY
 // kernel, kbest_kernels.hpp for the k-best lists, posterior_kernels.hpp for the sum-product model, sample_kernels.hpp for the draws
-// from it, constrained_kernels.hpp for the bracket mask over both, bracket_grad_kernels.hpp for the gradient of its log-probability
+// from it, constrained_kernels.hpp for the bracket mask over both, constrained_tree_kernels.hpp for the k-best lists and the draws
+// under that mask, bracket_grad_kernels.hpp for the gradient of its log-probability
 // and expectation_kernels.hpp for the expected cost, the entropy and their gradient.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
 #include <cmath>
@@ -10,6 +11,7 @@
 #include "api_common.hpp"
 #include "bracket_grad_kernels.hpp"
 #include "constrained_kernels.hpp"
+#include "constrained_tree_kernels.hpp"
 #include "decode_kernels.hpp"
 #include "expectation_kernels.hpp"
 #include "kbest_kernels.hpp"
@@ -139,6 +141,56 @@ extern "C" int cliora_constrained_parse(cliora_plan* plan, void* fwd_ws, const i
                          nullptr, spans_out, status, stream, [&](auto LONG, auto&& go) {
                              return go("constrained_kernel", constrained_kernel<decltype(LONG)::value>, brackets, M, score_out, log_z_out,
                                        log_zc_out, log_prob_out, feasible_out, marginals);
+                         });
+}
+
+// The tables of a plan's B sentences when they do not fit the LDS beside the count bytes and the mask tail (constrained_tree_kernels.hpp:
+// KbestConLds.in_lds), else 0.
+extern "C" size_t cliora_kbest_constrained_scratch_bytes(const cliora_plan* plan, int K, int M) {
+    if (!plan || K < 1 || K > KBEST_MAX_K || M < 0 || M > CON_MAX_M) return 0;
+    const Plan& p = plan->p;
+    const KbestConLds lay{p.L, p.C, K, M};
+    return lay.in_lds ? 0 : (size_t)p.B * lay.table_bytes;
+}
+
+extern "C" int cliora_kbest_spans_constrained(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, const int32_t* brackets, int M, int K,
+                                              int32_t* spans_out, float* scores_out, int32_t* count_out, int32_t* feasible_out, void* scratch,
+                                              int32_t* status, void* stream) {
+    if (K < 1 || K > KBEST_MAX_K) return fail(CLIORA_EINVAL, "cliora_kbest_spans_constrained: K outside 1..16");
+    if (M < 0 || M > CON_MAX_M) return fail(CLIORA_EINVAL, "cliora_kbest_spans_constrained: M outside 0..256");
+    if (!plan || !fwd_ws || !scores_out || !count_out || !feasible_out || !status)
+        return fail(CLIORA_EINVAL, "cliora_kbest_spans_constrained: NULL argument");
+    if (!spans_out && plan->p.L > 1) return fail(CLIORA_EINVAL, "cliora_kbest_spans_constrained: NULL spans_out");
+    if (!brackets && M > 0) return fail(CLIORA_EINVAL, "cliora_kbest_spans_constrained: NULL brackets");
+    if (!scratch && cliora_kbest_constrained_scratch_bytes(plan, K, M)) return fail(CLIORA_EINVAL, "cliora_kbest_spans_constrained: NULL scratch");
+    const bool in_lds = KbestConLds{plan->p.L, plan->p.C, K, M}.in_lds;
+    return launch_decode(plan, fwd_ws, "kbest_spans_constrained", KBEST_WAVES, [K, M](int L, int C) { return KbestConLds{L, C, K, M}; }, lengths,
+                         nullptr, spans_out, status, stream, [&](auto LONG, auto&& go) {
+                             constexpr bool LNG = decltype(LONG)::value;
+                             return in_lds ? go("kbest_constrained_kernel", kbest_constrained_kernel<LNG, true>, brackets, M, K, scores_out,
+                                                count_out, feasible_out, (float*)nullptr)
+                                           : go("kbest_constrained_kernel", kbest_constrained_kernel<LNG, false>, brackets, M, K, scores_out,
+                                                count_out, feasible_out, (float*)scratch);
+                         });
+}
+
+// Every table of the kernel fits the CU's LDS up to L = 128 and M = 256 (constrained_tree_kernels.hpp: 161 504 bytes there): no
+// scratch, no query.
+extern "C" int cliora_sample_trees_constrained(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, const int32_t* ids,
+                                               const int32_t* brackets, int M, int S, uint64_t seed, uint64_t first_sample, float beta,
+                                               int32_t* spans_out, float* log_prob_out, float* log_zc_out, float* log_z_out,
+                                               int32_t* feasible_out, int32_t* status, void* stream) {
+    if (S < 1 || S > SAMPLE_MAX_S) return fail(CLIORA_EINVAL, "cliora_sample_trees_constrained: S outside 1..1048576");
+    if (!(beta >= 0.f) || !std::isfinite(beta)) return fail(CLIORA_EINVAL, "cliora_sample_trees_constrained: beta negative or not finite");
+    if (M < 0 || M > CON_MAX_M) return fail(CLIORA_EINVAL, "cliora_sample_trees_constrained: M outside 0..256");
+    if (!plan || !fwd_ws || !log_prob_out || !log_zc_out || !log_z_out || !feasible_out || !status)
+        return fail(CLIORA_EINVAL, "cliora_sample_trees_constrained: NULL argument");
+    if (!spans_out && plan->p.L > 1) return fail(CLIORA_EINVAL, "cliora_sample_trees_constrained: NULL spans_out");
+    if (!brackets && M > 0) return fail(CLIORA_EINVAL, "cliora_sample_trees_constrained: NULL brackets");
+    return launch_decode(plan, fwd_ws, "sample_trees_constrained", POST_WAVES, [M](int L, int C) { return SampleConLds{L, C, M}; }, lengths,
+                         nullptr, spans_out, status, stream, [&](auto LONG, auto&& go) {
+                             return go("sample_trees_constrained_kernel", sample_trees_constrained_kernel<decltype(LONG)::value>, ids, brackets,
+                                       M, S, seed, first_sample, beta, log_prob_out, log_zc_out, log_z_out, feasible_out);
                          });
 }
 

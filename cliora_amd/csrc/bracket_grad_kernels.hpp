@@ -77,7 +77,7 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void bracket_grad_kernel(in
     // ---- inside, levels up
     for (int c = threadIdx.x; c < n; c += NT) { ac[c] = (mask[c] & CON_ALLOWED) ? (post_t)0 : ninf; au[c] = 0; }
     __syncthreads();
-    con_inside<false>(ac, au, mask, true, t);
+    con_inside<false>(ac, au, mask, true, t, (post_t)1);
     const post_t lzc = ac[t.root()], lz = au[t.root()];
     if (threadIdx.x == 0) { log_prob[b] = (float)(lzc - lz); feasible[b] = lzc > ninf ? 1 : 0; }
     if (!(lzc > ninf)) { zero_split_rows<NT>(G, t); return; }       // no qualifying tree

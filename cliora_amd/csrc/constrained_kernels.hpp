@@ -114,14 +114,16 @@ __device__ __forceinline__ int con_build_mask(const Tri& t, bool bad, const int3
 
 // The inside tables of sentence t, levels up: al over the allowed cells and, where `constrained`, au over every cell -- each cell
 // by inside_lse on split_terms, as post_inside, in one level loop.  The leaves are the caller's (before a barrier).  Called by every
-// thread of the workgroup; one barrier per level, the last one before it returns.  t.lvl: the plan's level bases, in LDS.
+// thread of the workgroup; one barrier per level, the last one before it returns.  t.lvl: the plan's level bases, in LDS.  beta: the
+// inverse temperature of the potentials, beta r formed in fp64 as post_inside forms it (1 multiplies exactly).
 template <bool LONG>
-__device__ __forceinline__ void con_inside(post_t* al, post_t* au, const unsigned char* mask, bool constrained, const Tri& t) {
+__device__ __forceinline__ void con_inside(post_t* al, post_t* au, const unsigned char* mask, bool constrained, const Tri& t, post_t beta) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int level = 1; level < t.n; ++level) {
         for (int pos = wave; pos < t.n - level; pos += POST_WAVES) {
             const int cell = t.cell(level, pos);
-            const SplitTerms x = split_terms<LONG>(t, level, pos, lane);
+            SplitTerms x = split_terms<LONG>(t, level, pos, lane);
+            x.r0 = beta * x.r0; x.r1 = beta * x.r1;
             post_t a = -INFINITY;
             if (mask[cell] & CON_ALLOWED) a = inside_lse<LONG, true>(x.t0(al), x.t1(al));
             if (constrained) {
@@ -223,7 +225,7 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void constrained_kernel(int
         if (constrained) au[c] = 0;
     }
     __syncthreads();
-    con_inside<LONG>(al, au, mask, constrained, t);
+    con_inside<LONG>(al, au, mask, constrained, t, (post_t)1);
     const post_t lzc = al[t.root()], lz = constrained ? au[t.root()] : lzc;
     if (threadIdx.x == 0) { log_zc[b] = (float)lzc; log_z[b] = (float)lz; log_prob[b] = (float)(lzc - lz); }
     if (!mu || !(lzc > ninf)) return;

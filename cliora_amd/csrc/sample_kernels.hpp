@@ -32,6 +32,60 @@ __device__ __forceinline__ post_t post_wave_scan(post_t v, int lane) {
     return v;
 }
 
+// One draw of sentence t (n >= 1, a finite al[root]) by the wavefront that calls it: the walk of the header over the inside table al,
+// sample index `sample`, sentence id `sid`, on the wave's stack stk (4 (L + 1) ints); the spans into out (lane 0).  -> the sum of
+// beta r over the chosen splits, in fp64.  The one walk of sample_trees_kernel and sample_trees_constrained_kernel
+// (constrained_tree_kernels.hpp).  MASKED: al holds -inf on the cells no qualifying tree has; a split with such a child weighs
+// exp(-inf) = exactly 0, so the scan never counts up to it and only the clamp could pick it: the clamp then goes to the largest k
+// whose children are both finite, not to N - 1.
+template <bool LONG, bool MASKED>
+__device__ __forceinline__ post_t sample_walk(const Tri& t, const post_t* al, post_t beta, uint64_t seed, uint64_t sample, uint32_t sid,
+                                              int32_t* stk, int32_t* __restrict__ out, int lane) {
+    post_t acc = 0;                                  // sum of beta r over the chosen splits
+    int sp = 0, cnt = 0;
+    stk[0] = t.n - 1; stk[1] = 0; stk[2] = 0; stk[3] = 0;
+    while (sp >= 0) {
+        const int level = stk[4 * sp], pos = stk[4 * sp + 1], phase = stk[4 * sp + 2];
+        if (level == 0) { --sp; continue; }
+        if (phase == 0) {                            // draw the cell's split
+            const SplitTerms x = split_terms<LONG>(t, level, pos, lane);
+            const bool an = x.an, an1 = x.an1;
+            const post_t here = al[t.cell(level, pos)];
+            post_t br0 = 0, br1 = 0, w0 = 0, w1 = 0, ch0 = -INFINITY, ch1 = -INFINITY;
+            if (an) { br0 = beta * x.r0; ch0 = al[x.l0] + al[x.q0]; w0 = exp(ch0 + br0 - here); }
+            if (an1) { br1 = beta * x.r1; ch1 = al[x.l1] + al[x.q1]; w1 = exp(ch1 + br1 - here); }
+            const post_t c0 = post_wave_scan(w0, lane);
+            post_t total = __shfl(c0, 63);           // lanes without a split add 0: lane 63 holds c_{N-1} of its half
+            post_t c1 = 0;
+            if constexpr (LONG) { c1 = total + post_wave_scan(w1, lane); total = __shfl(c1, 63); }
+            const post_t u = philox_uniform(make_uint4((uint32_t)(level * 256 + pos), (uint32_t)sample, (uint32_t)(sample >> 32), sid), seed);
+            const post_t thr = u * total;
+            int k = __popcll(__ballot(an && c0 <= thr));
+            if constexpr (LONG) k += __popcll(__ballot(an1 && c1 <= thr));
+            int top = level - 1;
+            if constexpr (MASKED) {                  // the cell is finite, so some split has finite children
+                const uint64_t f0 = __ballot(ch0 > (post_t)-INFINITY), f1 = LONG ? __ballot(ch1 > (post_t)-INFINITY) : 0;
+                top = f1 ? 127 - __clzll(f1) : f0 ? 63 - __clzll(f0) : top;           // none (scores that are NaN): inside the cell
+            }
+            k = k < top ? k : top;
+            const post_t r0 = __shfl(br0, k & 63);
+            post_t r1 = 0;
+            if constexpr (LONG) r1 = __shfl(br1, k & 63);
+            acc += k < 64 ? r0 : r1;
+            stk[4 * sp + 2] = 1; stk[4 * sp + 3] = k;
+            ++sp; stk[4 * sp] = k; stk[4 * sp + 1] = pos; stk[4 * sp + 2] = 0; stk[4 * sp + 3] = 0;
+        } else if (phase == 1) {
+            const int k = stk[4 * sp + 3];
+            stk[4 * sp + 2] = 2;
+            ++sp; stk[4 * sp] = level - k - 1; stk[4 * sp + 1] = pos + k + 1; stk[4 * sp + 2] = 0; stk[4 * sp + 3] = 0;
+        } else {
+            if (lane == 0) { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; }
+            ++cnt; --sp;
+        }
+    }
+    return acc;
+}
+
 // lengths (B) or NULL; ids (B) or NULL (sentence id = b).  spans (B, S, L-1, 2) (NULL when L = 1): sample s's n - 1 constituents,
 // (-1, -1) beyond; log_prob (B, S); log_z (B).  A length outside [1, L]: every row -1, log_prob 0, log_z 0, one count in *status, no
 // chart read.  `split` is launch_decode's slot and always NULL here.
@@ -79,45 +133,8 @@ static __global__ __launch_bounds__(POST_WAVES * 64) void sample_trees_kernel(in
 
     const uint32_t sid = ids ? (uint32_t)ids[b] : (uint32_t)b;
     for (int s = wave; s < S; s += POST_WAVES) {     // al is read only from here on: the waves go their own ways
-        const uint64_t sample = first_sample + (uint64_t)s;
-        int32_t* out = spans ? spans + ((size_t)b * S + s) * rows : nullptr;
-        post_t acc = 0;                              // sum of beta r over the chosen splits
-        int sp = 0, cnt = 0;
-        stk[0] = n - 1; stk[1] = 0; stk[2] = 0; stk[3] = 0;
-        while (sp >= 0) {
-            const int level = stk[4 * sp], pos = stk[4 * sp + 1], phase = stk[4 * sp + 2];
-            if (level == 0) { --sp; continue; }
-            if (phase == 0) {                        // draw the cell's split
-                const SplitTerms x = split_terms<LONG>(t, level, pos, lane);
-                const bool an = x.an, an1 = x.an1;
-                const post_t here = al[t.cell(level, pos)];
-                post_t br0 = 0, br1 = 0, w0 = 0, w1 = 0;
-                if (an) { br0 = beta * x.r0; w0 = exp(al[x.l0] + al[x.q0] + br0 - here); }
-                if (an1) { br1 = beta * x.r1; w1 = exp(al[x.l1] + al[x.q1] + br1 - here); }
-                const post_t c0 = post_wave_scan(w0, lane);
-                post_t total = __shfl(c0, 63);       // lanes without a split add 0: lane 63 holds c_{N-1} of its half
-                post_t c1 = 0;
-                if constexpr (LONG) { c1 = total + post_wave_scan(w1, lane); total = __shfl(c1, 63); }
-                const post_t u = philox_uniform(make_uint4((uint32_t)(level * 256 + pos), (uint32_t)sample, (uint32_t)(sample >> 32), sid), seed);
-                const post_t thr = u * total;
-                int k = __popcll(__ballot(an && c0 <= thr));
-                if constexpr (LONG) k += __popcll(__ballot(an1 && c1 <= thr));
-                k = k < level - 1 ? k : level - 1;
-                const post_t r0 = __shfl(br0, k & 63);
-                post_t r1 = 0;
-                if constexpr (LONG) r1 = __shfl(br1, k & 63);
-                acc += k < 64 ? r0 : r1;
-                stk[4 * sp + 2] = 1; stk[4 * sp + 3] = k;
-                ++sp; stk[4 * sp] = k; stk[4 * sp + 1] = pos; stk[4 * sp + 2] = 0; stk[4 * sp + 3] = 0;
-            } else if (phase == 1) {
-                const int k = stk[4 * sp + 3];
-                stk[4 * sp + 2] = 2;
-                ++sp; stk[4 * sp] = level - k - 1; stk[4 * sp + 1] = pos + k + 1; stk[4 * sp + 2] = 0; stk[4 * sp + 3] = 0;
-            } else {
-                if (lane == 0) { out[2 * cnt] = pos; out[2 * cnt + 1] = pos + level; }
-                ++cnt; --sp;
-            }
-        }
+        const post_t acc = sample_walk<LONG, false>(t, al, beta, seed, first_sample + (uint64_t)s, sid, stk,
+                                                    spans ? spans + ((size_t)b * S + s) * rows : nullptr, lane);
         if (lane == 0) log_prob[(size_t)b * S + s] = (float)(acc - lz);
     }
 }

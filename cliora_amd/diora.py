@@ -673,6 +673,27 @@ class DioraBase(nn.Module):
         constrained.refuse_rejected(int(status.sum()))
         return log_prob.tolist()
 
+    def kbest_constrained(self, k, required, forbidden=None):
+        """kbest() among the trees that keep every span of required[b] as a constituent and none of forbidden[b] (per-sentence lists
+        of (start, end) as cky_constrained takes them; cliora_amd.constrained.constrained_kbest): per sentence
+        the list of its (tree, score), best first -- min(k, the number of qualifying trees) of them, [] where none qualifies; rank 0
+        is cky_constrained's tree.  One device-to-host copy."""
+        from . import constrained
+        kb = constrained.constrained_kbest(self, constrained.pack_brackets(required, forbidden), k)
+        spans, scores, count, status = host_copy(kb.spans, kb.scores, kb.count, kb.status)
+        constrained.refuse_rejected(int(status.sum()), 'cliora_kbest_spans_constrained')
+        return [list(zip(self.trees_from_spans(spans[b, :count[b]]), scores[b, :count[b]].tolist())) for b in range(len(count))]
+
+    def sample_trees_constrained(self, S, seed, required, forbidden=None, beta=1.0):
+        """sample_trees() from the posterior over parses given the brackets (cliora_amd.constrained.constrained_samples, DESIGN.md
+        section 25): per sentence the list of its S sampled (tree, log_prob), every tree keeping the brackets and log_prob the log of
+        its probability among the trees that do; [] where no tree qualifies.  One device-to-host copy."""
+        from . import constrained
+        ts = constrained.constrained_samples(self, constrained.pack_brackets(required, forbidden), S, seed, beta=beta)
+        spans, log_prob, feasible, status = host_copy(ts.spans, ts.log_prob, ts.feasible, ts.status)
+        constrained.refuse_rejected(int(status.sum()), 'cliora_sample_trees_constrained')
+        return [list(zip(self.trees_from_spans(spans[b]), log_prob[b].tolist())) if feasible[b] else [] for b in range(len(feasible))]
+
     def bracket_nll(self, required, forbidden=None, reduction='mean'):
         """The loss -log_prob of the brackets, in the autograd graph of the last forward (cliora_amd.structured.bracket_nll; DESIGN.md
         section 20): required / forbidden as cky_constrained takes them -- per-sentence lists of (start, end); a gold tree is its inner

@@ -249,6 +249,19 @@ def oracle_f1(spans_k, count, gold):
                 corpus_f1=first.corpus_f1, sent_f1=mean(first))
 
 
+def oracle_f1_given_brackets(diora, entity_labels, gold, k, lengths=None):
+    """``oracle_f1`` over the k best trees that keep the annotated phrases: the upper bound on a model's span F1 once the gold noun
+    phrases are given.  diora: a chart module after its forward; entity_labels: batch_map['entity_labels'], turned into required
+    brackets by ``constrained.brackets_from_entity_labels`` (crossing phrases dropped, so some tree always qualifies); gold, k: as
+    ``oracle_f1`` and ``kbest.kbest_spans`` take them; lengths: an int32 tensor (B,) for a right-padded batch.  A rejected sentence (a
+    phrase outside its sentence) raises.  -> oracle_f1's dict: corpus_f1 / sent_f1 are the best constrained tree's."""
+    from . import constrained
+    required = constrained.brackets_from_entity_labels(entity_labels)
+    kb = constrained.constrained_kbest(diora, constrained.pack_brackets(required), k, lengths)
+    constrained.refuse_rejected(int(kb.status.sum().item()), 'cliora_kbest_spans_constrained')
+    return oracle_f1(kb.spans, kb.count, gold)
+
+
 def expected_f1(spans_s, gold):
     """Expected span F1 under sampled trees, on the host.  spans_s (B, S, L-1, 2): the trees of cliora_amd.sample (an array or a
     tensor; (-1, -1) rows are padding); gold: per sentence its constituents, the root excluded.  Each sample is counted as

@@ -12,6 +12,7 @@ the posterior mass), and how many there are.  Rank 0 is the CKY tree.  The refer
 The order is the contract: every cell holds at most K derivations (value, split k, left rank i, right rank j); a leaf holds one of
 value 1.0; a candidate is (val_left[i] + val_right[j]) + (s_k - smax) in fp32, in that order; the list is the first K candidates by
 value descending, then split, left rank, right rank ascending.  ``kbest_numpy`` restates it in fp32 for tests, bit for bit.
+The same lists among the trees that keep required and forbidden brackets: ``constrained.constrained_kbest``.
 """
 import ctypes as C
 

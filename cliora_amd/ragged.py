@@ -449,6 +449,18 @@ def parse_ragged_samples(net, sentences, S, seed, beta=1.0, max_batch=64, max_wa
     return out
 
 
+def _ragged_brackets(sentences, required, forbidden):
+    """required / forbidden as the ragged entries take them -> one list of spans per sentence each; refused before any pack has run."""
+    from . import constrained
+    required = [list(r) for r in required]
+    forbidden = [[] for _ in sentences] if forbidden is None else [list(f) for f in forbidden]
+    if len(required) != len(sentences) or len(forbidden) != len(sentences):
+        raise ValueError('required and forbidden hold one list of spans per sentence (%d)' % len(sentences))
+    if max([len(r) + len(f) for r, f in zip(required, forbidden)] or [0]) > constrained.MAX_M:
+        raise ValueError('at most %d brackets per sentence' % constrained.MAX_M)
+    return required, forbidden
+
+
 def parse_ragged_constrained(net, sentences, required, forbidden=None, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, obj_feats=None,
                              max_len=MAX_L_INSIDE):
     """The best binary tree of every sentence under its brackets (cliora_amd.constrained), in the caller's order: per sentence
@@ -460,12 +472,7 @@ def parse_ragged_constrained(net, sentences, required, forbidden=None, max_batch
     from . import constrained
     diora = net.diora
     out = [None] * len(sentences)
-    required = [list(r) for r in required]
-    forbidden = [[] for _ in sentences] if forbidden is None else [list(f) for f in forbidden]
-    if len(required) != len(sentences) or len(forbidden) != len(sentences):      # refused before any pack has run
-        raise ValueError('required and forbidden hold one list of spans per sentence (%d)' % len(sentences))
-    if max([len(r) + len(f) for r, f in zip(required, forbidden)] or [0]) > constrained.MAX_M:
-        raise ValueError('at most %d brackets per sentence' % constrained.MAX_M)
+    required, forbidden = _ragged_brackets(sentences, required, forbidden)
 
     def decode_pack(idx, lens):
         brackets = constrained.pack_brackets([required[i] for i in idx], [forbidden[i] for i in idx])
@@ -474,6 +481,64 @@ def parse_ragged_constrained(net, sentences, required, forbidden=None, max_batch
         for b, i in enumerate(idx):
             tree = diora.trees_from_spans(spans[b:b + 1, :len(sentences[i]) - 1])[0] if feasible[b] else None
             out[i] = (tree, float(log_prob[b]))
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
+    return out
+
+
+def parse_ragged_kbest_constrained(net, sentences, k, required, forbidden=None, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0,
+                                   obj_feats=None, max_len=MAX_L_INSIDE):
+    """``parse_ragged_kbest`` among the trees that keep every span of required[i] and none of forbidden[i] (per-sentence lists of
+    (start, end), inclusive word positions; cliora_amd.constrained.constrained_kbest), in the caller's order: per sentence the list of
+    its (tree, score), best first -- min(k, the number of qualifying trees) of them, [] where none qualifies.  A sentence's result does
+    not depend on the pack it lands in.  Sentences of up to 128 words are taken (max_len).  One device-to-host copy per pack; a
+    bracket outside its sentence raises ChartLibError."""
+    from . import constrained, kbest
+    diora = net.diora
+    out = [None] * len(sentences)
+    k = int(k)
+    if not 1 <= k <= kbest.MAX_K:                    # refused before any pack has run
+        raise ValueError('k must be in 1..%d' % kbest.MAX_K)
+    required, forbidden = _ragged_brackets(sentences, required, forbidden)
+
+    def decode_pack(idx, lens):
+        brackets = constrained.pack_brackets([required[i] for i in idx], [forbidden[i] for i in idx])
+        kb = constrained.constrained_kbest(diora, brackets, k, lens)
+        rows, scores, count, status = host_copy(kb.spans, kb.scores, kb.count, kb.status)
+        constrained.refuse_rejected(int(status.sum()), 'cliora_kbest_spans_constrained')
+        for b, i in enumerate(idx):
+            trees = diora.trees_from_spans(rows[b, :count[b], :len(sentences[i]) - 1])
+            out[i] = list(zip(trees, scores[b, :count[b]].tolist()))
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
+    return out
+
+
+def parse_ragged_samples_constrained(net, sentences, S, seed, required, forbidden=None, beta=1.0, max_batch=64, max_waste=DEFAULT_MAX_WASTE,
+                                     pad_id=0, obj_feats=None, max_len=MAX_L_INSIDE):
+    """``parse_ragged_samples`` from each sentence's posterior over parses given its brackets (required / forbidden as
+    ``parse_ragged_kbest_constrained`` takes them; cliora_amd.constrained.constrained_samples), in the caller's order: per sentence the
+    list of its S (tree, log_prob), log_prob the log of the draw's probability among the qualifying trees; [] where no tree qualifies.
+    A sentence's id in the draw is its index in `sentences`, so its samples do not depend on the pack it lands in.  Sentences of up to
+    128 words are taken (max_len).  One device-to-host copy per pack; a bracket outside its sentence raises ChartLibError."""
+    from . import constrained, sample
+    diora = net.diora
+    out = [None] * len(sentences)
+    S = int(S)
+    if not 1 <= S <= sample.MAX_S:                   # refused before any pack has run
+        raise ValueError('S must be in 1..%d' % sample.MAX_S)
+    if not (beta >= 0 and np.isfinite(beta)):
+        raise ValueError('beta must be finite and >= 0')
+    required, forbidden = _ragged_brackets(sentences, required, forbidden)
+
+    def decode_pack(idx, lens):
+        brackets = constrained.pack_brackets([required[i] for i in idx], [forbidden[i] for i in idx])
+        ts = constrained.constrained_samples(diora, brackets, S, seed, lens, ids=torch.tensor(idx, dtype=torch.int32), beta=beta)
+        rows, log_prob, feasible, status = host_copy(ts.spans, ts.log_prob, ts.feasible, ts.status)
+        constrained.refuse_rejected(int(status.sum()), 'cliora_sample_trees_constrained')
+        for b, i in enumerate(idx):
+            trees = diora.trees_from_spans(rows[b, :, :len(sentences[i]) - 1]) if feasible[b] else []
+            out[i] = list(zip(trees, log_prob[b].tolist()))
 
     _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len)
     return out

@@ -13,6 +13,7 @@ The draw is the contract: top-down from the root, at cell (level, pos) with N = 
 r_k - a[cell]) over the fp64 inside table a, c_k = w_0 + .. + w_k, split = #{k : c_k <= u c_{N-1}} clamped to N - 1, and u = (m + 0.5)
 2^-53 from Philox4x32-10 at counter (level * 256 + pos, sample_lo, sample_hi, sentence id) under key (seed_lo, seed_hi).  A draw
 depends on (seed, sentence id, sample index, cell) and the sentence's scores alone.  ``sample_numpy`` restates it in fp64 for tests.
+The same draws from the distribution given required and forbidden brackets: ``constrained.constrained_samples``.
 """
 import collections
 import ctypes as C

@@ -461,6 +461,52 @@ int cliora_sample_trees(cliora_plan* plan, void* fwd_workspace, const int32_t* l
 int cliora_constrained_parse(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* brackets, int M,
                              int32_t* spans_out, float* score_out, float* log_z_out, float* log_zc_out, float* log_prob_out,
                              int32_t* feasible_out, float* marginals, int32_t* status, void* stream);
+/* The K best trees and SAMPLED trees under required and forbidden brackets: cliora_kbest_spans and cliora_sample_trees over the
+ * distribution cliora_constrained_parse conditions -- the trees built from allowed cells, under the unchanged potentials r = s_k -
+ * max_k s over every split of the cell, allowed or not.  brackets (B, M, 3), M, lengths and status are
+ * cliora_constrained_parse's: status is always required and counts, once each, the sentences with a length outside [1, L] or a bad row;
+ * such a sentence is not decoded and none of its scores is read.  A sentence with no qualifying tree is no error and is not counted:
+ * feasible_out (B) int32 is 0 for it, as for a rejected one.  Every plan cliora_cky_spans takes is taken: long plans, padded charts,
+ * TreeLSTM plans.  One workgroup per sentence, fixed-order reductions, no floating-point atomics: two calls give equal bits.
+ *
+ * cliora_kbest_spans_constrained: the contract of cliora_kbest_spans -- the candidate (val_left[i] + val_right[j]) + (s_k - smax) in
+ *   fp32 in that order, a list the first K candidates by value descending, then split, left rank, right rank ascending -- over the
+ *   derivations built from allowed cells.  A cell keeps a count: 1 at an allowed leaf, min(K, sum_k count[left_k] * count[right_k]) at
+ *   an allowed cell, 0 at a disallowed one; a split with an empty child offers nothing.
+ *   count_out (B): min(K, the number of qualifying trees); scores_out (B, K), spans_out (B, K, L-1, 2): as cliora_kbest_spans writes
+ *   them.  No qualifying tree, or a rejected sentence: count 0, scores -inf, every row -1.
+ *   With no disallowed cell every output is bitwise cliora_kbest_spans'.  Always, rank 0's spans and score are bitwise the spans_out /
+ *   score_out of cliora_constrained_parse.
+ *   scratch: device memory of cliora_kbest_constrained_scratch_bytes(plan, K, M) bytes -- 0 when the lists fit the LDS beside the walk
+ *   stacks, the count bytes and the mask, else B lists of 8 C K bytes; NULL when that is 0.
+ *   Refused with CLIORA_EINVAL and a message, before any launch: K outside 1..16; M outside 0..256; a NULL plan, workspace, scores_out,
+ *   count_out, feasible_out or status; NULL spans_out with L > 1; NULL brackets with M > 0; NULL scratch when the query is not 0; a plan
+ *   that has not run a forward.
+ *
+ * cliora_sample_trees_constrained: the draws of cliora_sample_trees -- S, seed, first_sample, beta, ids, the Philox counter (level *
+ *   256 + pos, sample_lo, sample_hi, sentence id), the fixed-order scan and split = #{k : c_k <= u c_{N-1}} are its -- over the inside
+ *   table of the allowed cells at inverse temperature beta, fp64.  A split with a child that no qualifying tree holds weighs exactly 0;
+ *   by the scan it could only be chosen through the clamp, so the clamp goes to the largest k whose children both have a finite inside
+ *   value, not to N - 1 (without a disallowed cell that is N - 1).
+ *   log_prob_out (B, S) fp32: beta * (sum of r over the chosen splits) - log_zc, summed in fp64: the log-probability of the draw given
+ *   the brackets.  log_zc_out, log_z_out (B) fp32: the constrained and the unconstrained log-partition at beta, computed in one level
+ *   loop; at beta = 1 bitwise the log_zc_out / log_z_out of cliora_constrained_parse.  spans_out (B, S, L-1, 2): as cliora_sample_trees.
+ *   No qualifying tree: every row -1, log_prob and log_zc -inf, log_z the real value.  A rejected sentence: every row -1, log_prob and
+ *   log_zc -inf, log_z 0.
+ *   With no disallowed cell spans, log_prob and log_z are bitwise cliora_sample_trees' for the same (seed, ids, first_sample, beta).
+ *   A draw depends on (seed, sentence id, sample index, cell), the sentence's scores and its brackets alone.  The tables fit the LDS up
+ *   to L = 128 and M = 256 (161 504 bytes there): no scratch.
+ *   Refused with CLIORA_EINVAL and a message, before any launch: S outside 1 .. 2^20; beta negative or not finite; M outside 0..256; a
+ *   NULL plan, workspace, log_prob_out, log_zc_out, log_z_out, feasible_out or status; NULL spans_out with L > 1; NULL brackets with
+ *   M > 0; a plan that has not run a forward. */
+size_t cliora_kbest_constrained_scratch_bytes(const cliora_plan* plan, int K, int M);
+int cliora_kbest_spans_constrained(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* brackets, int M, int K,
+                                   int32_t* spans_out, float* scores_out, int32_t* count_out, int32_t* feasible_out, void* scratch,
+                                   int32_t* status, void* stream);
+int cliora_sample_trees_constrained(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* ids,
+                                    const int32_t* brackets, int M, int S, uint64_t seed, uint64_t first_sample, float beta,
+                                    int32_t* spans_out, float* log_prob_out, float* log_zc_out, float* log_z_out, int32_t* feasible_out,
+                                    int32_t* status, void* stream);
 /* The gradient of cliora_constrained_parse's log_prob with respect to the per-split inside scores: what a loss -log_prob (distant
  * supervision from annotated phrases, the log-likelihood of a gold tree as its n - 2 inner brackets, forbidden-bracket penalties)
  * hands to cliora_chart_backward_split.  With a_x / b_x the inside / outside tables of the constrained (x = c,
