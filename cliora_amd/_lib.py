@@ -103,6 +103,10 @@ ABI = {
     'cliora_knn_ip_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'cliora_knn_ip': (i32, [i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, sz, vp]),
     'cliora_knn_filter': (i32, [i32, i32, vp, i64, vp, i64, vp, vp, i32, i32, vp, vp, vp, vp]),
+    'cliora_maxsim_workspace_bytes': (sz, [i32, i32, i32, i32, i32]),
+    'cliora_maxsim_scores': (i32, [i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp, sz, vp]),
+    'cliora_retrieval_ranks': (i32, [i32, i32, vp, i64, vp, vp, vp, vp, vp]),
+    'cliora_score_topk': (i32, [i32, i32, i32, vp, i64, i64, vp, vp, vp]),
     'cliora_token_counts': (i32, [i64, vp, i32, vp, vp, vp]),
     'cliora_neg_sample_workspace_bytes': (sz, [i32, i32, i32]),
     'cliora_neg_sample': (i32, [i32, vp, i32, i32, i32, u64, u64, C.c_uint32, vp, vp, vp, sz, vp]),

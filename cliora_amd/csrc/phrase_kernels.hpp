@@ -28,7 +28,7 @@ constexpr int KNN_FRAG = 512;            // dwords per fragment block: 64 lanes 
 // ---- gather -----------------------------------------------------------------------------------------------------------
 // table (N, 3) int32: sentence, pos, size.  Cell = C - (L-size+1)(L-size+2)/2 + pos.  out row r = [inside | outside], 2D floats at
 // out + (row0 + r) * ldo.  A row outside the chart is not read: it is written as zeros and counted in *status.
-__global__ __launch_bounds__(PHRASE_THREADS) void phrase_gather_kernel(
+static __global__ __launch_bounds__(PHRASE_THREADS) void phrase_gather_kernel(
         int B, int L, int D, const float* __restrict__ ins, int64_t isb, int64_t isc, const float* __restrict__ outs, int64_t osb,
         int64_t osc, int N, const int32_t* __restrict__ table, int normalize, float* __restrict__ out, int64_t ldo, int64_t row0,
         int32_t* __restrict__ status) {
@@ -127,6 +127,22 @@ struct KnnList {
     }
 };
 
+// One lane's eight values of a fragment block -> its eight dwords.  SPLIT: dwords 0-3 the bf16 hi parts (pairs, low half first), 4-7
+// the lo parts (split_bf16x8); else the fp32 values.
+template <bool SPLIT>
+__device__ __forceinline__ void knn_store_lane(const float (&v)[8], uint32_t* __restrict__ dst) {
+    uint4* o = reinterpret_cast<uint4*>(dst);
+    if (SPLIT) {
+        u32x4 hi, lo;
+        split_bf16x8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
+        o[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+        o[1] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    } else {
+        o[0] = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+        o[1] = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
+    }
+}
+
 // rows [0, n) of src (leading dimension ld, D columns) -> fragment blocks dst[(tile * nchunks + chunk) * 512 + lane * 8 + j]:
 // lane l of block (tile, chunk) holds row 16 tile + (l & 15), columns 32 chunk + 8 (l >> 4) + (0..7); zero outside the matrix.
 // SPLIT: dwords 0-3 the bf16 hi parts of the eight values (pairs, low half first), 4-7 the lo parts (split_bf16x8); else the fp32
@@ -143,16 +159,7 @@ __global__ __launch_bounds__(256) void knn_pack_kernel(const float* __restrict__
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = (row < n && k0 + j < D) ? src[(int64_t)row * ld + k0 + j] : 0.f;
-    uint4* o = reinterpret_cast<uint4*>(dst + t * 8);
-    if (SPLIT) {
-        u32x4 hi, lo;
-        split_bf16x8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
-        o[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-        o[1] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-    } else {
-        o[0] = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-        o[1] = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
-    }
+    knn_store_lane<SPLIT>(v, dst + t * 8);
 }
 
 // grid (query tiles of 64, S key ranges).  Range s covers key steps [s*T/S, (s+1)*T/S) of T = ceil(nk / 256).  Each step: every
@@ -277,7 +284,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const uint64_t* __restri
 
 // phrase_embed.py:250-263 per query: walk the kc candidates, skip I == -1, the query's own example and its own phrase; keep the
 // first k_top.  One thread per query.
-__global__ __launch_bounds__(256) void knn_filter_kernel(int nq, int kc, const int64_t* __restrict__ I, int64_t ldi, const float* __restrict__ Dv,
+static __global__ __launch_bounds__(256) void knn_filter_kernel(int nq, int kc, const int64_t* __restrict__ I, int64_t ldi, const float* __restrict__ Dv,
                                                          int64_t ldd, const int32_t* __restrict__ example, const int32_t* __restrict__ phrase,
                                                          int n_ids, int k_top, int64_t* __restrict__ Iout, float* __restrict__ Dout,
                                                          int32_t* __restrict__ count) {

@@ -718,6 +718,47 @@ int cliora_knn_ip(int nq, int nk, int D, int k, const float* q, int64_t ldq, con
 int cliora_knn_filter(int nq, int k_candidates, const int64_t* I, int64_t ldi, const float* D, int64_t ldd, const int32_t* example_ids,
                       const int32_t* phrase_ids, int n_ids, int k_top, int64_t* I_out, float* D_out, int32_t* count, void* stream);
 
+/* Caption-image retrieval scores: the weighted late-interaction ("MaxSim") product of grouped rows,
+ *   S[n][m] = sum over the tokens t of caption n of  w[t] * max over the regions r of image m of <Q[t], O[r]>,
+ * the logit of the reference's VGLoss (cliora.py:460, 463-464; trainer.py:145-152) for any set of captions against any set of images.
+ *   Q (NT, D) / O (MR, D) fp32 on the device at leading dimensions ldq, ldo >= D, any D >= 1 (padded to 32 internally); caption n
+ *   owns rows q_off[n] .. q_off[n+1] of Q (q_off: N + 1 int32 on the device), image m rows o_off[m] .. o_off[m+1] of O; w (NT) fp32.
+ *   S (N, M) fp32 at leading dimension lds >= M.  No host synchronisation; everything is enqueued on `stream`.
+ *   Arithmetic: the mode of cliora_set_mfma_mode, as cliora_knn_ip; fp32 accumulation.  No buffer of NT x MR or NT x M elements is
+ *   written: a scan kernel lays the groups out in 16-row MFMA tiles (a caption tile belongs to one caption, an image's tiles never
+ *   straddle a 256-row key step), the operands are packed into fragment blocks, each workgroup scores 64 packed query rows against
+ *   a range of key steps, reduces every accumulator tile to its per-row maximum over the VALID key rows (padding is masked, never
+ *   scored), combines an image's tiles, multiplies by w and sums the 16 rows of a query tile in a fixed butterfly order; one fp32
+ *   partial per (query tile, image) goes to the workspace and a second kernel adds a caption's tiles in ascending order.
+ *   Determinism: S[n][m] is a function of caption n's rows and weights and image m's rows alone -- bitwise the same whatever else
+ *   is in the call, in whatever order, however the key steps were split over workgroups; two runs are bitwise equal.
+ *   An empty caption gives a row of 0.0; an empty image a column of -inf (0.0 against an empty caption).  A NaN in a token makes
+ *   that caption's row NaN, a NaN in a region that image's column; nothing else.
+ *   status (2 int32 on the device, zeroed by the call): [0] the number of images with more than 256 regions (their columns are
+ *   NaN); [1] the number of groups with a decreasing offset or an offset outside [0, NT] / [0, MR], or that no longer fit the
+ *   layout bound because earlier groups overlap (such a group reads nothing; its row / column is NaN).  The caller must check it.
+ *   Refused before any launch with CLIORA_EINVAL: D < 1, negative counts, ldq / ldo < D, lds < M, a NULL argument; CLIORA_ENOMEM:
+ *   ws_bytes below cliora_maxsim_workspace_bytes(N, NT, M, MR, D) (0 for invalid arguments). */
+size_t cliora_maxsim_workspace_bytes(int N, int NT, int M, int MR, int D);
+int cliora_maxsim_scores(int N, int NT, int M, int MR, int D, const float* Q, int64_t ldq, const int32_t* q_off, const float* w,
+                         const float* O, int64_t ldo, const int32_t* o_off, float* S, int64_t lds, int32_t* status, void* ws,
+                         size_t ws_bytes, void* stream);
+
+/* Ranks of the paired items in a score matrix S (N captions x M images, leading dimension lds >= M), ordered as cliora_knn_ip
+ * orders candidates: descending score, ascending index on ties, NaN below every number.  image_of (N) int32: the image of caption n.
+ *   rank_t2i[n]: the number of images m != image_of[n] that order before it in row n (0 = retrieved first).
+ *   rank_i2t[m]: over the captions n of image m, the smallest number of captions of OTHER images that order before n in column m;
+ *   -1 for an image without captions.
+ *   image_of[n] outside [0, M): rank_t2i[n] = -1, the caption belongs to no image, and *status (one int32, zeroed by the call) counts it. */
+int cliora_retrieval_ranks(int N, int M, const float* S, int64_t lds, const int32_t* image_of, int32_t* rank_t2i, int32_t* rank_i2t,
+                           int32_t* status, void* stream);
+
+/* The k best entries (1 <= k <= 128) of every row of a strided matrix, S[r * row_stride + c * col_stride], under the same order:
+ * D_out (rows, k) fp32 and I_out (rows, k) int64, contiguous; slots past `cols` hold -inf / -1.  One wavefront per row.  Swapping
+ * the strides (and rows / cols) ranks the columns: the captions per image. */
+int cliora_score_topk(int rows, int cols, int k, const float* S, int64_t row_stride, int64_t col_stride, float* D_out, int64_t* I_out,
+                      void* stream);
+
 /* Corpus token counts, the frequency vector of the reference's negative sampler (cliora/blocks/negative_sampler.py:15-24): ids (n)
  * int64 on the device -> counts (V) fp32, counts[v] = the number of ids equal to v, converted from an exact integer count (so the
  * reference's np.asarray(counts, float32) bit for bit).  Counted with integer atomics in LDS for V <= 16384, in HBM above.  Ids
