@@ -107,6 +107,9 @@ ABI = {
     'cliora_maxsim_scores': (i32, [i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp, sz, vp]),
     'cliora_retrieval_ranks': (i32, [i32, i32, vp, i64, vp, vp, vp, vp, vp]),
     'cliora_score_topk': (i32, [i32, i32, i32, vp, i64, i64, vp, vp, vp]),
+    'cliora_vocab_workspace_bytes': (sz, [i32, i32, i32, i32]),
+    'cliora_vocab_nll_forward': (i32, [i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'cliora_vocab_nll_backward': (i32, [i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, sz, vp]),
     'cliora_token_counts': (i32, [i64, vp, i32, vp, vp, vp]),
     'cliora_neg_sample_workspace_bytes': (sz, [i32, i32, i32]),
     'cliora_neg_sample': (i32, [i32, vp, i32, i32, i32, u64, u64, C.c_uint32, vp, vp, vp, sz, vp]),

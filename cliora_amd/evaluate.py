@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .interchange import SpanF1, parse_record
+from .vocab import word_prediction      # the exact held-out word prediction (nll, perplexity, acc@k, mrr): its own pass, its own result
 
 METRICS = ('corpus_f1', 'sent_f1', 'ground_acc', 'ccra', 'recon_loss', 'vg_loss', 'contr_loss', 'total_loss')
 LOSS_NAMES = ('reconstruct_softmax_loss', 'vg_loss', 'contrastive_loss')     # harness.Net's loss names, as in the reference's Net

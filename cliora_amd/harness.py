@@ -99,15 +99,28 @@ class ImageEncoder(nn.Module):
 class ReconstructionSoftmaxLoss(nn.Module):
     name = 'reconstruct_softmax_loss'
 
-    def __init__(self, embeddings, input_size, size, k_neg=3):
+    def __init__(self, embeddings, input_size, size, k_neg=3, full_vocab=False):
+        """full_vocab: the exact loss over the whole table instead of the sampled one (cliora_amd.vocab): the mean over the tokens of
+        logsumexp_v <mat^T o_t, emb[v]> - <mat^T o_t, emb[tok_t]>; neg_samples is then ignored."""
         super().__init__()
-        self.k_neg, self.embeddings = k_neg, embeddings
+        self.k_neg, self.embeddings, self.full_vocab = k_neg, embeddings, bool(full_vocab)
+        self.vocab_status = None             # full_vocab on the device: the last call's count of ids outside the table (forward)
         self.mat = nn.Parameter(torch.empty(size, input_size))
         _normal_(self)
 
     def forward(self, tokens, neg_samples, diora):
         B, L = tokens.shape
         w = self.embeddings.weight
+        if self.full_vocab:
+            q = diora.outside_h[:, :L].reshape(B * L, -1) @ self.mat                 # B*L,E: the gradient to mat and outside_h flows through this product
+            from . import vocab
+            if _native(w, tokens, q) and vocab.supported(q, w, tokens):
+                # An id outside the table raises in the torch formula below.  Here it is left out of the sum (while 1 / T still counts
+                # it) and counted in vocab_status, a one-element int32 tensor on the device: reading it is a synchronisation, so it is
+                # the caller's to check, once per epoch or when a loss looks wrong.
+                loss, _, _, _, _, self.vocab_status = vocab.vocab_nll(q, w, tokens.reshape(-1))
+                return loss
+            return F.cross_entropy(q @ w.t(), tokens.reshape(-1))
         if _native(w, tokens, neg_samples, diora.outside_h) and w.shape[1] % 16 == 0:
             return heads.recon_loss(w, self.mat, diora.outside_h, tokens, neg_samples)
         pos = self.embeddings(tokens) @ self.mat.t()                     # B,L,D
@@ -406,12 +419,13 @@ def select_diora(arch, obj_feats):
 
 def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=True, normalize='unit',
               vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp', bracket_loss_weight=0.0,
-              risk_loss_weight=0.0, entropy_loss_weight=0.0):
-    """What trainer.py:504-582 assembles, on the native chart modules."""
+              risk_loss_weight=0.0, entropy_loss_weight=0.0, full_softmax=False):
+    """What trainer.py:504-582 assembles, on the native chart modules.  full_softmax: the reconstruction loss is the exact one over the
+    whole table (ReconstructionSoftmaxLoss(full_vocab=True)) instead of the reference's sampled loss."""
     embed = Embed(embeddings, embeddings.weight.shape[1], size)
     enc = ImageEncoder(img_dim, size)
     diora = select_diora(arch, obj_feats)(size, outside=True, normalize=normalize, compress=False, share=share)
-    losses = [ReconstructionSoftmaxLoss(embeddings, embeddings.weight.shape[1], size, k_neg=k_neg)]
+    losses = [ReconstructionSoftmaxLoss(embeddings, embeddings.weight.shape[1], size, k_neg=k_neg, full_vocab=full_softmax)]
     if vg_loss:
         losses.append(VGLoss(alpha_vg))
     if obj_feats and use_contr:

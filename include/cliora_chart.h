@@ -759,6 +759,60 @@ int cliora_retrieval_ranks(int N, int M, const float* S, int64_t lds, const int3
 int cliora_score_topk(int rows, int cols, int k, const float* S, int64_t row_stride, int64_t col_stride, float* D_out, int64_t* I_out,
                       void* stream);
 
+/* The exact word-prediction loss over the whole vocabulary: for token t with projected outside row Q[t] = o_t . mat and word tok[t],
+ *   s[t][v] = <Q[t], K[v]>   (the reference's score, trainer.py:58-66, for every word v of the table K),
+ *   nll[t] = logsumexp_v s[t][v] - s[t][tok[t]],   loss = sum_t w[t] nll[t].
+ *   Q (T, E) / K (V, E) fp32 on the device at leading dimensions ldq, ldk >= E, any E >= 1 (padded to 32 internally); tok (T) int64;
+ *   w (T) fp32: 1 / T for the mean, 1 / n_valid on the real words of a padded chart and 0 on its padding.
+ *   Outputs (T each, on the device): lse, tgt (the target's logit), nll fp32; lse_lo fp32 or NULL: what fp32 drops of lse (lse is
+ *   combined in fp64; lse + lse_lo carries it to 2^-48, and the backward's p = exp((s - lse) - lse_lo) then does not inherit the half
+ *   ulp of an lse of magnitude 100, 4e-6 relative on every p of the token); rank int32 or NULL: the number of words that order
+ *   before tok[t] as cliora_knn_ip orders candidates (descending score, ascending index on ties, NaN below every number);
+ *   loss: one fp32.  No host synchronisation; everything is enqueued on `stream`.
+ *   Arithmetic: the mode of cliora_set_mfma_mode, as cliora_knn_ip, and its score chain instruction for instruction; fp32
+ *   accumulation.  No buffer of T x V elements is written: each workgroup scores 64 tokens against a range of 8 x 256 words, keeps a
+ *   running (max, sum exp(. - max)) per token over the VALID words of a step (words at or past V are masked, never scored; the
+ *   maximum is subtracted before every exp), one (max, sum) pair and one count per (token, range) go to the workspace by plain
+ *   stores, and a second kernel combines a token's ranges in ascending order.  The ranges are a function of V alone.  tgt comes
+ *   from the same chain on the rows K[tok[t]] packed in token order, so it is bit for bit the main pass's score of (t, tok[t]):
+ *   rank[t] == 0 exactly when cliora_knn_ip(k = 1) returns tok[t].  loss is one fp64 chain in ascending token order, rounded once.
+ *   Determinism: no float atomics; a token's lse / tgt / nll / rank are a function of its row, its word and K alone -- bitwise the
+ *   same whatever else is in the call and in whatever order; two runs are bitwise equal.
+ *   Edge cases: a tok[t] outside [0, V) is counted in *status (one int32, zeroed by the call; the caller must check it), gets
+ *   nll = tgt = NaN and rank = -1, and adds nothing to loss or to the gradients.  A token with w[t] == 0 adds nothing BY SELECTION
+ *   (a NaN in a padded row does not leak).  A NaN in Q[t] makes token t's outputs, and loss if w[t] != 0, NaN; no other token's.
+ *   V = 1: nll = 0, rank = 0.  T = 0: loss = 0.
+ *   ws: cliora_vocab_workspace_bytes(T, V, E, want_backward) bytes; every byte read is written first.  With al(x) = x rounded up to
+ *   256, c = ceil(E / 32), F = 2048 c (one packed 16-row tile), qt = ceil(T / 64), kt = ceil(V / 256), q4 = ceil(T / 256):
+ *     forward  = 2 al(4 qt F) + al(16 kt F) + al(8 T ceil(kt / 8)) + al(4 T ceil(kt / 8))
+ *     backward = al(16 q4 F) + al(16 kt F) + al(4 T) + al(16384 ceil(E / 16) kt) + al(16384 ceil(E / 16) q4)
+ *                + al(64 ceil(E / 16) max(ceil(kt / r) 64 qt, ceil(q4 / 16) 64 ceil(V / 64))),  r = 2 for kt <= 64, 16 for kt >= 512,
+ *                  ceil(kt / 32) between
+ *   and the size is `forward`, or max(forward, backward) with want_backward (0 for T < 0, V < 1, E < 1).
+ *   Refused before any launch with CLIORA_EINVAL: T < 0, V < 1, E < 1, a leading dimension below E, a NULL argument (rank may be
+ *   and lse_lo may be NULL; with T = 0 only K, loss, status and ws are needed); CLIORA_ENOMEM: ws_bytes below the size above. */
+size_t cliora_vocab_workspace_bytes(int T, int V, int E, int want_backward);
+int cliora_vocab_nll_forward(int T, int V, int E, const float* Q, int64_t ldq, const float* K, int64_t ldk, const int64_t* tok,
+                             const float* w, float* loss, float* nll, float* lse, float* lse_lo, float* tgt, int32_t* rank, int32_t* status,
+                             void* ws, size_t ws_bytes, void* stream);
+
+/* Its gradients for the upstream cotangent g (one fp32 on the device), from lse and lse_lo (or NULL: zeros) of the forward (nothing
+ * else is kept): with p[t][v] = exp((s[t][v] - lse[t]) - lse_lo[t]) recomputed tile by tile -- each score the forward's chain, the
+ * word's block its A operand on either side, so the same bits -- and wsel[t] = w[t] on the tokens that count (w[t] != 0, tok[t] inside
+ * [0, V)), 0 elsewhere,
+ *   dQ[t] = g wsel[t] sum_v (p[t][v] - [v == tok[t]]) K[v],     dK[v] = g sum_t wsel[t] (p[t][v] - [v == tok[t]]) Q[t].
+ *   dQ (T, E) at lddq, dK (V, E) at lddk: written, not accumulated; either may be NULL and is then skipped (the other half is
+ *   bitwise what it is with both).  One kernel, the stationary side a template parameter (tokens: dQ, words: dK): 64 stationary rows
+ *   per workgroup, the other side streamed 256 rows at a time, the coefficients through the LDS score tile into a second MFMA product
+ *   against the streamed operand packed along its rows; ranges of r x 256 words for dQ (about 32 ranges, so that a batch's few token tiles fill the device) and of
+ *   16 x 256 tokens for dK (a function of the streamed side's size
+ *   alone) give partials that a second kernel adds in ascending order.  Widths above 448 take ceil(E / 448) passes over the output
+ *   columns, each computing the scores again.  No float atomics; a token's dQ row is bitwise the same whatever else is in the call.
+ *   ws: cliora_vocab_workspace_bytes(T, V, E, 1) bytes (it may be the forward's; its contents are not needed).  Refusals as above. */
+int cliora_vocab_nll_backward(int T, int V, int E, const float* Q, int64_t ldq, const float* K, int64_t ldk, const int64_t* tok,
+                              const float* w, const float* lse, const float* lse_lo, const float* g, float* dQ, int64_t lddq, float* dK,
+                              int64_t lddk, void* ws, size_t ws_bytes, void* stream);
+
 /* Corpus token counts, the frequency vector of the reference's negative sampler (cliora/blocks/negative_sampler.py:15-24): ids (n)
  * int64 on the device -> counts (V) fp32, counts[v] = the number of ids equal to v, converted from an exact integer count (so the
  * reference's np.asarray(counts, float32) bit for bit).  Counted with integer atomics in LDS for V <= 16384, in HBM above.  Ids
