@@ -122,6 +122,8 @@ ABI = {
     'cliora_set_resident': (i32, [i32]),
     'cliora_device_side_stream': (i32, [vp, pvp]),
     'cliora_resident_trace': (i32, [vp, vp, sz, vp]),
+    'cliora_launch_record': (i32, [i32]),
+    'cliora_launch_record_read': (i32, [C.c_char_p, sz, psz]),
 }
 
 _lib = None
@@ -298,6 +300,37 @@ def prof_read(kclass, stream=0):
     ms, n = C.c_double(), C.c_longlong()
     call('cliora_prof_read', KCLASS[kclass], C.byref(ms), C.byref(n), C.c_void_p(stream))
     return ms.value, n.value
+
+
+def launch_record_read():
+    """The distinct kernel instances noted since the launch record was turned on (include/cliora_chart.h: cliora_launch_record), as a set."""
+    read = fn('cliora_launch_record_read')
+    n = C.c_size_t()
+    call('cliora_launch_record_read', None, 0, C.byref(n))
+    while True:         # the record is process-wide: another host thread's launch may lengthen it between the size query and the read
+        cap = n.value + 256
+        buf = C.create_string_buffer(cap)
+        rc = read(buf, cap, C.byref(n))
+        if rc == 0:
+            return set(buf.value.decode().split('\n')) - {''}
+        if n.value <= cap:     # refused, and not for want of room
+            check(rc, 'cliora_launch_record_read')
+
+
+class launch_record(object):
+    """`with _lib.launch_record() as rec:` -- `rec` is a set of strings that, when the block ends, holds the kernel instances the library's
+    dispatchers launched inside it ('level_compose_bwd<5,0,f32>', 'tn_gemm<2,2,colsum>', ...).  The record is process-wide: launches of
+    other host threads during the block are in it too.  Turns the record off again unless it was on already."""
+
+    def __enter__(self):
+        self.rec = set()
+        self.prev = fn('cliora_launch_record')(1)
+        return self.rec
+
+    def __exit__(self, *a):
+        self.rec.update(launch_record_read())
+        if not self.prev:        # (turning it on again would clear it: a block inside another one restarts the outer one's record)
+            fn('cliora_launch_record')(0)
 
 
 MFMA_MODES = {'f32': 0, 'bf16x3': 1}

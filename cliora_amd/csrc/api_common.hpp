@@ -80,6 +80,23 @@ static inline int fail(int code, const std::string& msg) { g_cliora_err = msg; r
         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                \
     } while (0)
 
+// The launch record (api_core.hip, include/cliora_chart.h: cliora_launch_record): while it is on, the dispatchers of gemm_launch.hpp and
+// api_mlp_launch.hpp note the instance they launch, the kernel's name with its template arguments as chosen.  Off: one flag test per launch.
+extern int g_cliora_launch_record;
+void cliora_launch_note(const std::string& entry);
+static inline bool launch_record_on() { return __builtin_expect(__atomic_load_n(&g_cliora_launch_record, __ATOMIC_RELAXED) != 0, 0); }
+// "name<a,b,...>" of integer and word template arguments, e.g. inst("tn_gemm", 2, 2, "colsum")
+static inline void inst_arg(std::string& s, int v) { s += std::to_string(v); }
+static inline void inst_arg(std::string& s, const char* v) { s += v; }
+template <class... A>
+static std::string inst(const char* name, A... a) {
+    std::string s = std::string(name) + "<";
+    int k = 0;
+    ((s += (k++ ? "," : ""), inst_arg(s, a)), ...);
+    return s + ">";
+}
+#define NOTE_LAUNCH(entry) do { if (launch_record_on()) cliora_launch_note(entry); } while (0)
+
 // kernels that need more than 64 KiB of dynamic LDS: the attribute is per device, so it is set once per (function, device)
 int cliora_ensure_max_lds(const void* fn);
 // uploads the plan's index tables on first use (current device) and checks that later calls run on that device

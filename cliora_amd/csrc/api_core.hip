@@ -22,6 +22,35 @@ int cliora_ensure_max_lds(const void* fn) {
     return CLIORA_OK;
 }
 
+// ------------------------------------------------------------------ launch record
+// Process-wide: the distinct instances the dispatchers launched since the record was turned on, whichever host thread launched them.
+int g_cliora_launch_record = 0;
+static std::mutex g_launch_record_mu;
+static std::set<std::string> g_launch_record;
+
+void cliora_launch_note(const std::string& entry) {
+    std::lock_guard<std::mutex> lk(g_launch_record_mu);
+    g_launch_record.insert(entry);
+}
+
+extern "C" int cliora_launch_record(int on) {
+    std::lock_guard<std::mutex> lk(g_launch_record_mu);
+    const int prev = g_cliora_launch_record;
+    if (on) g_launch_record.clear();
+    __atomic_store_n(&g_cliora_launch_record, on ? 1 : 0, __ATOMIC_RELAXED);
+    return prev;
+}
+
+extern "C" int cliora_launch_record_read(char* buf, size_t cap, size_t* needed) {
+    std::lock_guard<std::mutex> lk(g_launch_record_mu);
+    std::string all;
+    for (const std::string& e : g_launch_record) { all += e; all += '\n'; }       // std::set: sorted, distinct
+    if (needed) *needed = all.size() + 1;
+    if (!buf || cap < all.size() + 1) return buf || !needed ? fail(CLIORA_EINVAL, "cliora_launch_record_read: buffer too small") : CLIORA_OK;
+    memcpy(buf, all.c_str(), all.size() + 1);
+    return CLIORA_OK;
+}
+
 extern "C" int cliora_prof_enable(int cls, int on) {
     if (cls < 0 || cls >= CLIORA_KCLASS_COUNT) return fail(CLIORA_EINVAL, "bad kernel class");
     std::lock_guard<std::mutex> lk(g_cliora_prof_mu);

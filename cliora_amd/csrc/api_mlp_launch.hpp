@@ -52,6 +52,7 @@ static int launch_level_compose(hipStream_t st, const ComposeSeg& sg, int S3, in
         hipLaunchKernelGGL((level_compose_fwd<ct_, k16, f32>), dim3(sg.gx, ncb), dim3(512), compose_lds_bytes(ct_, S, true), st, sg.Wimg, S, Dp, sg.lv,
                            sg.PA, sg.lda, sg.PB, sg.ldb, sg.bias, Pp, sg.TG, sg.SP, sg.ntask, sg.HP, hp_stride, Dp, ymask, Y);
         LAUNCHOK("level_compose_fwd");
+        NOTE_LAUNCH(inst("level_compose_fwd", ct_, k16, f32 ? "f32" : "bf16x3"));
         return CLIORA_OK;
     });
 }
@@ -70,10 +71,12 @@ static int launch_level_compose2(hipStream_t st, const ComposeSeg& a, const Comp
             OKR(cliora_ensure_max_lds((const void*)level_compose_fwd2<ct_, k16, f32, 2>));
             hipLaunchKernelGGL((level_compose_fwd2<ct_, k16, f32, 2>), dim3(gx, ncb), dim3(512), lds_dual, st, a, b, S, Dp, Pp, hp_stride, Dp, ymask, Y);
             LAUNCHOK("level_compose_fwd2(dual)");
+            NOTE_LAUNCH(inst("level_compose_fwd2", ct_, k16, "bf16x3", "dual"));
         } else {
             OKR(cliora_ensure_max_lds((const void*)level_compose_fwd2<ct_, k16, f32>));
             hipLaunchKernelGGL((level_compose_fwd2<ct_, k16, f32>), dim3(gx, ncb), dim3(512), compose_lds_bytes(ct_, S, true), st, a, b, S, Dp, Pp, hp_stride, Dp, ymask, Y);
             LAUNCHOK("level_compose_fwd2");
+            NOTE_LAUNCH(inst("level_compose_fwd2", ct_, k16, f32 ? "f32" : "bf16x3"));
         }
         return CLIORA_OK;
     });
@@ -94,6 +97,7 @@ static int launch_level_compose_bwd(hipStream_t st, const float* WT, const float
         hipLaunchKernelGGL((level_compose_bwd<ct_, k16, f32, tiled_>), dim3(gx, ncb), dim3(512), compose_lds_bytes(ct_, S, false) + (size_t)((K + 31) / 32 * 32) * sizeof(float), st, I, S, K, lv, dG, ymask,
                            Pp, PA, lda, PB, ldb, b2, K, DA, DZ, X, DPP, DPB);
         LAUNCHOK("level_compose_bwd");
+        NOTE_LAUNCH(tiled_ ? inst("level_compose_bwd", ct_, k16, "bf16x3", "tiled") : inst("level_compose_bwd", ct_, k16, f32 ? "f32" : "bf16x3"));
         return CLIORA_OK;
     };
     if (tiled) {         // X, DZ as tiled split-bf16 operands of tn_gemm_tiles (pair_tiles_ok: d = 400, split mode)
@@ -117,6 +121,7 @@ static int launch_level_project(hipStream_t st, int SP, const ProjSeg& q, hipEve
                           dim3(256), 0, st, q.Wfrag, q.K, nrg, nrgp, ncb, q.ncell, q.Lc, q.C, q.off, q.HP, q.hp_stride, q.normalize, q.bias, q.P,
                           q.ldp, q.H, q.nrm, q.sc);
         LAUNCHOK("level_project");
+        NOTE_LAUNCH(inst("level_project", decltype(CT)::value, decltype(SP_)::value, decltype(LONG)::value ? "long" : "short"));
         return CLIORA_OK;
     };
     // a block's MFMA work and operand bytes are fixed by its tile: wide tiles only when the launch still covers the chip
@@ -136,6 +141,7 @@ static int launch_level_project2(hipStream_t st, int SP0, int SP1, const ProjSeg
             return with_parts2(SP1, [&](auto S1) {
                 hipLaunchKernelGGL((level_project2<decltype(S0)::value, decltype(S1)::value, decltype(LONG)::value>), dim3(n), dim3(256), 0, st, a, b);
                 LAUNCHOK("level_project2");
+                NOTE_LAUNCH(inst("level_project2", decltype(S0)::value, decltype(S1)::value, decltype(LONG)::value ? "long" : "short"));
                 return CLIORA_OK;
             });
         });

@@ -48,6 +48,7 @@ static int launch_rows_inst(hipStream_t st, const float* W, int Kseg, int nseg, 
     hipLaunchKernelGGL((rows_gemm_ws<CT, SC, WAVES, AP, EP>), dim3(ws_grid((nrows + 15) / 16, gy, WAVES), gy), dim3(WAVES * 64), lds, st, W, Kseg * nseg,
                        Kseg, nseg, nrows, ap, ep);
     LAUNCHOK("rows_gemm_ws");
+    NOTE_LAUNCH(inst("rows_gemm_ws", CT, SC, WAVES));
     return CLIORA_OK;
 }
 
@@ -83,6 +84,7 @@ static int launch_rows3_k(hipStream_t st, const uint32_t* Wimg, int S, int K, in
     hipLaunchKernelGGL((rows_gemm_ws3<CT, WAVES, PD, K16, AP, EP>), dim3(ws_grid((nrows + 15) / 16, gy, WAVES), gy), dim3(WAVES * 64), lds, st, Wimg, S, K,
                        nrows, ap, ep);
     LAUNCHOK("rows_gemm_ws3");
+    NOTE_LAUNCH(inst("rows_gemm_ws3", CT, WAVES, K16));
     return CLIORA_OK;
 }
 template <class AP, class EP>
@@ -115,6 +117,7 @@ static int launch_ksplit_tile(hipStream_t st, const float* W, int K, int nt, int
     const RowGroups g = row_groups(nrows, RT);
     hipLaunchKernelGGL((rows_gemm_ksplit<RT, CT, FRAG, AP, EP>), dim3(g.nrgp * (nt / CT)), dim3(256), 0, st, W, K, g.nrg, g.nrgp, nt / CT, nrows, ap, ep);
     LAUNCHOK("rows_gemm_ksplit");
+    NOTE_LAUNCH(inst("rows_gemm_ksplit", RT, CT, FRAG ? "frag" : "plain"));
     return CLIORA_OK;
 }
 // blocks a split-K launch must have to take the wider tile: MI355X sweep 0..2000: 5.61 ms/step at 0, 5.44 at 160, 5.37 at 1000
@@ -168,6 +171,7 @@ static int launch_rows_direct3x(hipStream_t st, const float* img3, int K, int nc
         const RowGroups g = row_groups(nrows, rt);
         hipLaunchKernelGGL((rows_gemm_ksplit3x<rt, ct, AP, EP>), dim3(g.nrgp * ((nt + ct - 1) / ct)), dim3(256), 0, st, I, K, g.nrg, g.nrgp, nt, nrows, ap, ep);
         LAUNCHOK("rows_gemm_ksplit3x");
+        NOTE_LAUNCH(inst("rows_gemm_ksplit3x", rt, ct));
         return CLIORA_OK;
     });
 }
@@ -186,6 +190,7 @@ static int launch_rows_direct3(hipStream_t st, const float* img3, int K, int nco
         constexpr int ct = decltype(CT)::value;
         hipLaunchKernelGGL((rows_gemm_ksplit3<ct, AP, EP>), dim3(g.nrgp * (nt / ct)), dim3(256), 0, st, I, K, g.nrg, g.nrgp, nrows, ap, ep);
         LAUNCHOK("rows_gemm_ksplit3");
+        NOTE_LAUNCH(inst("rows_gemm_ksplit3", ct));
         return CLIORA_OK;
     });
 }
@@ -220,6 +225,7 @@ static int launch_tn_slab(hipStream_t st, int nrows, int Mi, int Nj, AP ap, BP b
     hipLaunchKernelGGL((tn_gemm<TI, TJ, COLSUM, AP, BP>), dim3(blocks, s.nsl / 4), dim3(WS_THREADS), 0, st, nrows, s.rps, Mi, Nj, ap, bp, slab,
                        slab_colsums(slab, s.nsl, n));
     LAUNCHOK(rule.name);
+    NOTE_LAUNCH(inst(rule.name, TI, TJ, COLSUM ? "colsum" : "nocolsum"));
     return finish_slab(st, slab, s.nsl, n, out, accumulate, (size_t)Mi, colsum_out);
 }
 
@@ -240,6 +246,7 @@ static int launch_tn(hipStream_t st, int nrows, int Mi, int Nj, int Dp, AP ap, B
             hipLaunchKernelGGL((tn_gemm_direct<decltype(COLSUM)::value, AP, BP>), dim3(blocks), dim3(TND_WAVES * 64), 0, st, nrows, Mi, Nj, ap, bp, out, colsum_out,
                                accumulate);
             LAUNCHOK("tn_gemm_direct");
+            NOTE_LAUNCH(inst("tn_gemm_direct", decltype(COLSUM)::value ? "colsum" : "nocolsum"));
             return CLIORA_OK;
         });
     return with_int<5, 4, 2, 1>(pick_tiles(Dp / 16), [&](auto T) {
@@ -260,7 +267,9 @@ static size_t dma3_lds_bytes(int Dp, int NJT) { return (size_t)2 * TN3_RS * (Dp 
 constexpr int DMA3X_NIT = 7, DMA3X_NJT = 9, DMA3X_NKB = 3;
 static bool tn_pairs_strided_ok(int Dp) {
     const int NT = Dp / 16;
-    return split_bf16() && NT > 20 && NT <= 27;       // the <7, 9> instance: d = 400
+    // the <7, 9> instance (d = 400) while its stages fit a CU's LDS: 27 tiles (Dp = 432) need 162 KiB, and launch_dma3x's callers
+    // (the level-row remap, the two-range launch) have no other kernel to fall back on as launch_tn_pairs_inst has
+    return split_bf16() && NT > 20 && NT <= 27 && dma3_lds_bytes(Dp, DMA3X_NJT) <= 160 * 1024;
 }
 template <class... Tail>
 static int launch_dma3x(hipStream_t st, const char* name, const float* A, int lda, const float* Bm, int ldb, int nrows, int rps, int nsl, int Dp, int ny,
@@ -269,6 +278,12 @@ static int launch_dma3x(hipStream_t st, const char* name, const float* A, int ld
     hipLaunchKernelGGL((tn_gemm_dma3x<DMA3X_NIT, DMA3X_NJT, 5, true>), dim3(dma_grid(DMA3X_NKB, nsl), ny), dim3(512), dma3_lds_bytes(Dp, DMA3X_NJT), st, A, lda,
                        Bm, ldb, nrows, rps, nsl, Dp, Dp, DMA3X_NKB, slab, csl, tail...);
     LAUNCHOK(name);
+    if (launch_record_on()) {        // "tn_gemm_dma3x(two ranges)" is noted as "tn_gemm_dma3x<7,9,5>(two ranges)", the level rows with their
+        const char* variant = strchr(name, '(');      // problem count (gridDim.y: 3 or 5 projection blocks): "...(level rows x5)"
+        std::string v = variant ? variant : "";
+        if (v == "(level rows)") v = "(level rows x" + std::to_string(ny) + ")";
+        cliora_launch_note(inst("tn_gemm_dma3x", DMA3X_NIT, DMA3X_NJT, 5) + v);
+    }
     return CLIORA_OK;
 }
 
@@ -293,6 +308,7 @@ static int launch_tn_pairs_inst(hipStream_t st, const float* DZ, const float* X,
             hipLaunchKernelGGL((tn_gemm_dma3<NIT, NJT, true>), dim3(dma_grid(nkb, s.nsl)), dim3(256), dma3_lds_bytes(Dp, NJT), st, DZ, X, nrows, s.rps, s.nsl, Dp,
                                Dp, nkb, slab, slab_colsums(slab, s.nsl, n));
             LAUNCHOK("tn_gemm_dma3");
+            NOTE_LAUNCH(inst("tn_gemm_dma3", NIT, NJT));
         }
     } else {
         if (strided) return fail(CLIORA_EINVAL, "strided operands need the eight-wave weight-gradient kernel (tn_pairs_strided_ok)");
@@ -300,6 +316,7 @@ static int launch_tn_pairs_inst(hipStream_t st, const float* DZ, const float* X,
         OKR(cliora_ensure_max_lds((const void*)tn_gemm_dma<NIT, NJT, true>));
         hipLaunchKernelGGL((tn_gemm_dma<NIT, NJT, true>), dim3(nkb * s.nsl), dim3(256), lds, st, DZ, X, nrows, s.rps, Dp, Dp, nkb, slab, slab_colsums(slab, s.nsl, n));
         LAUNCHOK("tn_gemm_dma");
+        NOTE_LAUNCH(inst("tn_gemm_dma", NIT, NJT));
     }
     return finish_slab(st, slab, s.nsl, n, out, accumulate, (size_t)Dp, colsum_out);
 }
@@ -381,6 +398,7 @@ static int launch_tn_tiles(hipStream_t st, const float* DZt, const float* Xt, lo
                        reinterpret_cast<const uint32_t*>(Xt), tile0, (int)ntiles, (int)t.rps, nsl, nkb, slab, slab_colsums(slab, nsl, n), (int)t.s1, tile0b,
                        (int)ntilesb);
     LAUNCHOK("tn_gemm_tiles");
+    NOTE_LAUNCH(inst("tn_gemm_tiles", NTc, NIT, NJT, NJW));
     return finish_slab(st, slab, nsl, n, out, accumulate, (size_t)Dp, colsum_out);
 }
 

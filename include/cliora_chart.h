@@ -910,6 +910,18 @@ int cliora_device_side_stream(void* caller_stream, void** out);
  * copies `count` 64-bit words of the device's stamp buffer to `out` (host) after synchronising `stream`. */
 int cliora_resident_trace(cliora_plan* plan, unsigned long long* out, size_t count, void* stream);
 
+/* The launch record: which kernel instances the run-time dispatchers chose.  Each rule of csrc/gemm_launch.hpp and
+ * csrc/api_mlp_launch.hpp turns a width or a row count into a template instance; while the record is on, every launch of theirs notes
+ * the kernel's name with its template arguments as chosen -- "level_compose_bwd<5,0,f32>", "rows_gemm_ksplit<2,4,frag>",
+ * "tn_gemm_dma3x<7,9,5>(two ranges)", "tn_gemm<2,2,colsum>", "level_project<5,2,short>" -- so that a test can hold its shape to the
+ * instance it was written for (tests/dispatch_cases.py).  Host code only, process-wide, safe with several host threads; off (the
+ * default) it costs one flag test per launch.
+ * cliora_launch_record(on): turns it on (and clears what was recorded) or off; returns the previous state.
+ * cliora_launch_record_read: the distinct entries, sorted, one per line, NUL-terminated, into buf[cap]; *needed (optional) gets the bytes
+ * that takes.  buf == NULL with needed: the size alone.  CLIORA_EINVAL if buf is too small. */
+int cliora_launch_record(int on);
+int cliora_launch_record_read(char* buf, size_t cap, size_t* needed);
+
 const char* cliora_version(void);
 
 #ifdef __cplusplus

@@ -345,9 +345,14 @@ def test_length_40_chart():
 
 @pytest.mark.parametrize('D', [48, 64, 96, 400])
 def test_weight_stationary_kernels_other_widths(D, mfma_mode):
-    """Levels above 1 500 pair rows run the weight-stationary compose kernels; d = 400 has its own unrolled instance,
-    every other width the run-time-K one with 1, 2 or 4 column tiles per block (Dp = 48 / 96 / 64).  B = 32, L = 14
-    (5 824 rows at the widest level) against the CPU oracle, forward and backward, both arithmetic modes."""
+    """The weight-stationary compose kernels at four widths: d = 400 has its own unrolled instance, every other width the
+    run-time-K one with 1, 2 or 4 column tiles per block (Dp = 48 / 96 / 64).  What the shapes reach, by the launch record
+    (_lib.launch_record(); tests/dispatch_cases.py has a case per instance): B = 32, L = 14 (1 365 span pairs per sentence: off
+    the sentence-resident kernels) runs level_compose_fwd<1,0> at Dp 48 and, on the merged schedule, level_compose_fwd2<4,0> /
+    <2,0> at Dp 64 / 96, with level_compose_bwd<1 / 4 / 2,0> and the pair rows' weight gradient on tn_gemm_dma<1,4> / <2,8>
+    (split mode: tn_gemm_dma3); B = 8, L = 20 at d = 400 runs level_compose_fwd2<5,25> (split mode: the dual instance),
+    level_compose_bwd<5,25> (split mode: tiled) and tn_gemm_dma<7,9> (split mode: tn_gemm_dma3x<7,9,5> and tn_gemm_tiles).
+    Against the CPU oracle, forward and backward, both arithmetic modes."""
     from oracle import diora_ref as R
     from oracle import synth
     B, L = (32, 14) if D < 400 else (8, 20)
