@@ -280,6 +280,7 @@ struct FwdCall {
         with_regions(p.R, [&](auto NR) {
             hipLaunchKernelGGL(cell_attend_fwd<decltype(NR)::value>, dim3(p.B * g.Lc), dim3(256), 0, st, g, p.L, HP, hp_stride, SP, T, OBJ, p.R,
                                drop_mask, p.normalize, IH, ws + f.nrmi, ws + f.att_u, ws + f.att_nrmu, ws + f.att_pk, ctx_out, p.D, IS);
+            NOTE_LAUNCH(inst("cell_attend_fwd", decltype(NR)::value));
         });
         LAUNCHOK(name);
         return CLIORA_OK;
@@ -892,6 +893,7 @@ struct BwdCall {
                 const size_t lds = (size_t)3 * 2 * nr * 64 * sizeof(float4);
                 OKR(cliora_ensure_max_lds((const void*)obj_grad_reduce<nr>));
                 hipLaunchKernelGGL(obj_grad_reduce<nr>, dim3(B, 4), dim3(512), lds, sw, B, C, Dp, p.R, wb + bw.dctx, ws + f.att_u, wb + bw.pmo, wb + bw.dsc, dO);
+                NOTE_LAUNCH(inst("obj_grad_reduce", nr));
                 return CLIORA_OK;
             }));
             LAUNCHOK("obj_grad_reduce");
@@ -964,6 +966,7 @@ struct BwdCall {
             with_regions(p.R, [&](auto NR) {
                 hipLaunchKernelGGL(cell_attend_bwd<decltype(NR)::value>, dim3(ncell), dim3(256), 0, sa, g, VH, IH, ws + f.nrmi, p.normalize, OBJ, p.R,
                                    drop_mask, ws + f.att_pk, wb + bw.dctx, wb + bw.pmo, wb + bw.dsc, IHn, nrmIn, level >= 1 ? dG : (float*)nullptr);
+                NOTE_LAUNCH(inst("cell_attend_bwd", decltype(NR)::value));
             });
             LAUNCHOK("cell_attend_bwd");
         }

@@ -147,6 +147,7 @@ extern "C" int cliora_vl_scores_max_backward(cliora_plan* plan, const float* ins
         }
         hipLaunchKernelGGL(region_max_bwd_obj, dim3(B * R, nchunk), dim3(256), 0, st, B, C, R, Dp, a_per_chunk, d_all_max, all_arg, v.sump, v.slab);
         LAUNCHOK("region_max_bwd_obj");
+        NOTE_LAUNCH("region_max_bwd_obj(nchunk " + std::to_string(nchunk) + ")");
         launch_slab_reduce(st, v.slab, nchunk, n, v.gobj, 0);
         LAUNCHOK("slab_reduce");
         CopyTable t; t.n = 0;
@@ -189,6 +190,7 @@ extern "C" int cliora_vl_scores_backward(cliora_plan* plan, const float* inside_
     const bool any_all = d_all || eval_vg;
     int Kseg = NRp, nseg = 1;
     region_segments(NRp, Dp, &Kseg, &nseg);
+    NOTE_LAUNCH(nseg == 1 ? std::string("region_segments(one)") : "region_segments(several x" + std::to_string(nseg) + ")");
     if (d_sum_h) {
         if (any_all) OKR(launch_rows(st, v.oallT, Kseg, nseg, Dp, B * C, gall, StoreAccE{d_sum_h, D, D, 0}));
         else HIPOK(hipMemsetAsync(d_sum_h, 0, (size_t)B * C * D * sizeof(float), st));

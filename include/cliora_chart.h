@@ -914,8 +914,11 @@ int cliora_resident_trace(cliora_plan* plan, unsigned long long* out, size_t cou
  * csrc/api_mlp_launch.hpp turns a width or a row count into a template instance; while the record is on, every launch of theirs notes
  * the kernel's name with its template arguments as chosen -- "level_compose_bwd<5,0,f32>", "rows_gemm_ksplit<2,4,frag>",
  * "tn_gemm_dma3x<7,9,5>(two ranges)", "tn_gemm<2,2,colsum>", "level_project<5,2,short>" -- so that a test can hold its shape to the
- * instance it was written for (tests/dispatch_cases.py).  Host code only, process-wide, safe with several host threads; off (the
- * default) it costs one flag test per launch.
+ * instance it was written for (tests/dispatch_cases.py).  The vision-language entries note theirs as well (tests/vl_cases.py): the
+ * attention launches "cell_attend_fwd<9>", "cell_attend_bwd<16>", "obj_grad_reduce<9>" (regions per wave), cliora_vl_scores_backward
+ * "region_segments(one)" or "region_segments(several x2)" (the LDS segments of the region axis), cliora_vl_scores_max_backward
+ * "region_max_bwd_obj(nchunk 7)", the scorer GEMMs "rows_gemm_ws<4,5,8>", "rows_gemm_ws3<5,4,25>", "tn_gemm(ij)<4,5,nocolsum>".
+ * Host code only, process-wide, safe with several host threads; off (the default) it costs one flag test per launch.
  * cliora_launch_record(on): turns it on (and clears what was recorded) or off; returns the previous state.
  * cliora_launch_record_read: the distinct entries, sorted, one per line, NUL-terminated, into buf[cap]; *needed (optional) gets the bytes
  * that takes.  buf == NULL with needed: the size alone.  CLIORA_EINVAL if buf is too small. */

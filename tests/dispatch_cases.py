@@ -289,8 +289,10 @@ def kink_free(fp32_dist):
 RELU_MARGIN = 5e-7
 
 
-def relu_margin(c):
-    """Smallest |pre-activation| / std of its layer and level over the fp64 forward of the case."""
+def relu_margin(c, forward=None):
+    """Smallest |pre-activation| / std of its layer and level over the fp64 forward of the case.  forward(R): runs that forward on the
+    oracle module R with whatever inputs the case has besides the words (vl_cases.py: the regions and the dropout mask); default: the
+    text-only forward on case_inputs(c)."""
     import torch
     import torch.nn.functional as F
 
@@ -304,11 +306,13 @@ def relu_margin(c):
         for z in (z1, z2):
             small[0] = min(small[0], float((z.abs() / z.std()).min()))
         return F.relu(z2), torch.full(z2.shape, 0, dtype=z2.dtype)
-    P, x, _ = case_inputs(c)
+    if forward is None:
+        P, x, _ = case_inputs(c)
+        forward = lambda R: R.diora_forward({k: v.double() for k, v in P.items()}, x.double(), x.double(), share=c['share'], training=True)
     R.compose_mlp = compose
     try:
         with torch.no_grad():
-            R.diora_forward({k: v.double() for k, v in P.items()}, x.double(), x.double(), share=c['share'], training=True)
+            forward(R)
     finally:
         R.compose_mlp = orig
     return small[0]
