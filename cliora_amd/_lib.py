@@ -18,6 +18,7 @@ MAX_L = 64               # csrc/plan.hpp CLIORA_MAX_L: the longest sentence of a
 MAX_L_FWD = 128          # csrc/plan.hpp CLIORA_MAX_L_FWD: the longest sentence of a forward-only ("long") DioraMLP / CLIORA plan
 FWD_NO_BACKWARD = 2      # include/cliora_chart.h: flag bits of cliora_chart_forward's run_outside word
 FWD_PAIR_STATES = 4
+FWD_HARD_DENSE = 16      # cliora_chart_forward_hard only: the one-hot weights through the dense compose kernels (cross-check / baseline)
 KCLASS = {'compose_fwd': 0, 'compose_bwd': 1, 'wgrad': 2}
 
 PARAM_FIELDS = ('leaf_w', 'leaf_b', 'in_w1', 'in_b1', 'in_w2', 'in_b2', 'in_mat',
@@ -49,6 +50,8 @@ ABI = {
     'cliora_plan_fwd_offset': (sz, [vp, C.c_char_p]),
     'cliora_plan_table': (i32, [vp, C.c_char_p, C.POINTER(C.POINTER(C.c_int32)), psz]),
     'cliora_chart_forward': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp]),
+    'cliora_chart_forward_hard': (i32, [vp, pp] + [vp] * 7 + [vp, sz, i32, vp]),
+    'cliora_hard_spans': (i32, [vp, vp, vp, vp]),
     'cliora_chart_backward': (i32, [vp, pp] + [vp] * 11 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_backward_split': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_forward_ragged': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),

@@ -70,6 +70,18 @@ extern "C" int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_ws, const in
     return launch_cky(plan, fwd_ws, "cky_spans_ragged", lengths, split_out, spans_out, status, stream);
 }
 
+// The spans of a hard chart's tree from its inside selections (no workspace: the selections are the caller's)
+extern "C" int cliora_hard_spans(cliora_plan* plan, const int32_t* sel_in, int32_t* spans, void* stream) {
+    if (!plan) return fail(CLIORA_EINVAL, "cliora_hard_spans: NULL argument");
+    const Plan& p = plan->p;
+    if (p.L < 2) return CLIORA_OK;                   // one word: no constituent, and no row to write
+    if (!sel_in || !spans) return fail(CLIORA_EINVAL, "cliora_hard_spans: NULL argument");
+    if (p.L > CLIORA_MAX_L_FWD) return fail(CLIORA_EINVAL, "cliora_hard_spans: L > 128");
+    hipLaunchKernelGGL(hard_spans_kernel, dim3(p.B), dim3(64), 0, (hipStream_t)stream, p.L, p.C, p.B, sel_in, spans);
+    LAUNCHOK("hard_spans_kernel");
+    return CLIORA_OK;
+}
+
 // Every table of the kernel fits the CU's LDS up to L = 128 (posterior_kernels.hpp), so no plan needs device scratch today; the query
 // is part of the contract so that a caller sizes the buffer as it sizes every other one.
 extern "C" size_t cliora_span_posteriors_scratch_bytes(const cliora_plan* plan) {

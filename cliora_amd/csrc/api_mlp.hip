@@ -122,9 +122,11 @@ enum class FwdSchedule {
     Wavefront,            // level by level: inside level k, outside level L-k -- on two streams where that pays (wavefront_pays), else on one
     InsideThenOutside,    // compress: the outside root is a projection of the inside root
     Ragged,               // mixed lengths in one padded chart: inside pass, mask, outside pass with root fix-ups (ragged_kernels.hpp)
+    Hard,                 // cliora_chart_forward_hard: every cell encodes its best split alone; the wavefront's step order on the caller's stream
 };
 
-static FwdSchedule pick_fwd_schedule(const cliora_plan* plan, bool vl, bool compress, int flags, const RaggedFwd* rg) {
+static FwdSchedule pick_fwd_schedule(const cliora_plan* plan, bool vl, bool compress, int flags, const RaggedFwd* rg, int hard) {
+    if (hard) return FwdSchedule::Hard;      // whatever cliora_set_wavefront / cliora_set_resident say
     if (rg) return FwdSchedule::Ragged;
     if (!(flags & CLIORA_FWD_PAIR_STATES) && resident_pays(plan, vl, compress)) return FwdSchedule::Resident;
     if (compress) return FwdSchedule::InsideThenOutside;
@@ -155,6 +157,10 @@ struct FwdCall {
     int flags;
     hipStream_t st;                           // the caller's stream: head, inside chain, tail
     const RaggedFwd* rg;
+    // cliora_chart_forward_hard: the caller's (B, C) selections of the two passes; hard = 1: the selected-pair compose, 2: the one-hot
+    // weights through the dense compose kernels (CLIORA_FWD_HARD_DENSE), 0: a soft chart
+    int32_t *sel_in = nullptr, *sel_out = nullptr;
+    int hard = 0;
 
     const Plan& p = plan->p;
     const FwdLayout& f = p.fwd;
@@ -163,7 +169,7 @@ struct FwdCall {
     // compress = True (diora.py:342-343): the outside root is a projection of the inside root, so the passes run one after the other
     const bool compress = P->root_mat != nullptr;
     const int run_outside = flags & 1;
-    const FwdSchedule schedule = pick_fwd_schedule(plan, vl, compress, flags, rg);
+    const FwdSchedule schedule = pick_fwd_schedule(plan, vl, compress, flags, rg, hard);
     const bool two_streams = schedule == FwdSchedule::Wavefront && run_outside && wavefront_pays(p, g_cliora_wavefront);
     const hipStream_t sb = two_streams ? plan->side : st;      // the outside chain's stream
     float *IH = padded ? ws + f.ihp : inside_h, *OH = padded ? ws + f.ohp : outside_h;      // the charts the kernels work on
@@ -219,7 +225,16 @@ struct FwdCall {
         sc.QRleaf = ws + f.qrleaf; sc.L = p.L;
         return sc;
     }
-    int launch_scores(hipStream_t s, const ScoreArgs& sc) const {
+    // (a hard chart: the hard tail, the selections into the scored pass's array)
+    int launch_scores(hipStream_t s, const ScoreArgs& sc, bool outside) const {
+        if (hard) {
+            int32_t* sel = outside ? sel_out : sel_in;
+            if (lng) hipLaunchKernelGGL(level_scores_hard<true>, dim3(sc.nscore), dim3(256), 0, s, sc, sel);
+            else hipLaunchKernelGGL(level_scores_hard<false>, dim3(sc.nscore), dim3(256), 0, s, sc, sel);
+            LAUNCHOK("level_scores_hard");
+            NOTE_LAUNCH(inst("level_scores_hard", lng ? "long" : "short"));
+            return CLIORA_OK;
+        }
         if (lng) hipLaunchKernelGGL(level_scores<true>, dim3(sc.nscore), dim3(256), 0, s, sc);
         else hipLaunchKernelGGL(level_scores<false>, dim3(sc.nscore), dim3(256), 0, s, sc);
         LAUNCHOK("level_scores");
@@ -365,7 +380,7 @@ struct FwdCall {
         // QR = M h of the leaves: the partner of a newest-level LEFT child is always a leaf (see level_project)
         OKR(launch_rows_direct(st, ws + f.matp, PROJ_IMG(f.matq3), Dp, Dp, B * L, LevelRowsA{IH, Dp, C, 0, L},
                                StoreRowsE{ws + f.qrleaf, Dp, nullptr, 0, Dp}));
-        return launch_scores(st, score_args(pass_ops(false), 1, -1, 0));
+        return launch_scores(st, score_args(pass_ops(false), 1, -1, 0), false);
     }
 
     // Root of the outside chart (diora.py:337-356) and the scores of the level below it: parents = the root only.  compress = True:
@@ -385,7 +400,7 @@ struct FwdCall {
         LAUNCHOK("unit_norm_rows(root)");
         if (L > 1) {
             OKR(launch_rows_direct(sb, ws + f.w1ro, PROJ_IMG(f.w1ro3), Dp, Dp, B, LevelRowsA{OH, Dp, C, C - 1, 1}, StoreLevelE{ws + f.po, Dp, C, C - 1, 1, nullptr, 0}));
-            OKR(launch_scores(sb, score_args(pass_ops(true), L - 2, -1, 0)));
+            OKR(launch_scores(sb, score_args(pass_ops(true), L - 2, -1, 0), true));
         }
         return CLIORA_OK;
     }
@@ -503,7 +518,44 @@ struct FwdCall {
             hipLaunchKernelGGL(ragged_root_seed, dim3(B), dim3(4 * 64), 0, st, level, p.level_offset[level], C, p.Dp, rg->lengths, OH, OS,
                                ws + f.nrmo, ws + f.po);
             LAUNCHOK("ragged_root_seed");
-            if (level >= 1) OKR(launch_scores(st, score_args(out, level - 1, -1, 0)));
+            if (level >= 1) OKR(launch_scores(st, score_args(out, level - 1, -1, 0), true));
+        }
+        return CLIORA_OK;
+    }
+
+    // ---- a hard chart ------------------------------------------------------------------------------
+    // One level of one pass: the selected pair of every cell composed (level_compose_hard; hard = 2: every pair, under the one-hot
+    // weights, by the dense kernel), then norm + projection + the next level's hard scores.  With a backward to follow the level's
+    // rows of the ReLU bits are cleared first: the compose writes the selected rows alone, and the backward reads every row.
+    int hard_level_step(const PassOps& o, int level) const {
+        ComposeSeg sg = compose_seg(o, level, false);
+        int32_t* sel = o.outside ? sel_out : sel_in;
+        {
+            ProfScope ps(CLIORA_KCLASS_COMPOSE_FWD, st);
+            if (hard == 2) OKR(launch_level_compose(st, sg, f.S3, p.Dp, f.ct3, f.ncb3, ws + f.pp, hp_stride, YM, nullptr));
+            else {
+                if (YM && sg.lv.N > 0)
+                    HIPOK(hipMemsetAsync(YM + (size_t)sg.lv.rowbase * f.ncb3 * 4, 0, (size_t)sg.lv.ncell * sg.lv.N * f.ncb3 * 4 * sizeof(uint32_t), st));
+                OKR(launch_level_compose_hard(st, sg, sel, f.S3, p.Dp, f.ct3, f.ncb3, YM, plan->ncu));
+                sg.SP = 1;
+            }
+        }
+        const ProjSeg q = project_seg(o, level, sg.SP);
+        if (q.nproj) return launch_level_project_hard(st, sg.SP, q, lng, sel);
+        if (q.nfin) {
+            hipLaunchKernelGGL(level_finish, dim3(q.nfin), dim3(256), 0, st, q.ncell, q.Lc, q.C, q.off, q.K, q.HP, q.hp_stride, q.SPfin,
+                               q.normalize, q.H, q.nrm);
+            LAUNCHOK((o.outside ? "level_finish(out)" : "level_finish"));
+        }
+        return CLIORA_OK;
+    }
+    // The wavefront's step order (inside level k, outside level L-k) on the caller's stream
+    int forward_hard() const {
+        const PassOps in = pass_ops(false), out = pass_ops(true);
+        OKR(start_outside_chart());
+        for (int k = 1; k <= L; ++k) {
+            if (k <= L - 1) OKR(hard_level_step(in, k));
+            if (run_outside && k >= 2) OKR(hard_level_step(out, L - k));
         }
         return CLIORA_OK;
     }
@@ -526,6 +578,7 @@ struct FwdCall {
             case FwdSchedule::Wavefront: OKR(forward_wavefront(fork_guard)); break;
             case FwdSchedule::InsideThenOutside: OKR(forward_inside_then_outside()); break;
             case FwdSchedule::Ragged: OKR(forward_ragged()); break;
+            case FwdSchedule::Hard: OKR(forward_hard()); break;
         }
         if (padded && !(resident && run_outside)) {      // un-pad the charts (a resident call writes its own)
             CopyTable t; t.n = 0;
@@ -539,10 +592,11 @@ struct FwdCall {
 
 // The body of cliora_chart_forward.  rg == nullptr: that entry, launch for launch.  rg != nullptr: a ragged forward entry
 // (api_ragged.hip, which has checked its own refusals, a long plan's among them) -- FwdSchedule::Ragged.
-int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
-                             const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
-                             float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
-                             void* stream, const RaggedFwd* rg) {
+// (sel_in / sel_out / hard: cliora_chart_forward_hard, which has made its own refusals first)
+static int chart_forward_body(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                              const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
+                              float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
+                              void* stream, const RaggedFwd* rg, int32_t* sel_in, int32_t* sel_out, int hard) {
     // every refusal before the first launch (run_outside: bit 0 and the CLIORA_FWD_* flags)
     if (!plan || !P || !x_span || !inside_h || !inside_s || !outside_h || !outside_s || !fwd_ws)
         return fail(CLIORA_EINVAL, "NULL argument");
@@ -564,14 +618,42 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
         if (run_outside & CLIORA_FWD_PAIR_STATES)
             return fail(CLIORA_EINVAL, "L > 64: CLIORA_FWD_PAIR_STATES is not supported (a long plan sizes no per-pair rows)");
         if (compress) return fail(CLIORA_EINVAL, "L > 64: compress (root_mat) is not supported");
-        if (g_cliora_resident == 1 && !vl && p.Dp <= 64)
+        if (!hard && g_cliora_resident == 1 && !vl && p.Dp <= 64)
             return fail(CLIORA_EINVAL, "L > 64: the sentence-resident kernels are not supported (cliora_set_resident / CLIORA_RESIDENT forces them on)");
     }
     hipStream_t st = (hipStream_t)stream;
     OKR(cliora_plan_ready(plan, st));
     std::lock_guard<std::mutex> lanes_lock(*plan->lanes_mu);
     ForkGuard fork_guard(st);                          // declared after the lock: runs (joins the side streams) before it is released
-    return FwdCall{plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, (float*)fwd_ws, run_outside, st, rg}.run(fork_guard);
+    return FwdCall{plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, (float*)fwd_ws, run_outside, st, rg,
+                   sel_in, sel_out, hard}.run(fork_guard);
+}
+int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
+                             const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,
+                             float* outside_s, float* inside_c, void* fwd_ws, size_t fwd_ws_bytes, int run_outside,
+                             void* stream, const RaggedFwd* rg) {
+    return chart_forward_body(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws, fwd_ws_bytes,
+                              run_outside, stream, rg, nullptr, nullptr, 0);
+}
+// A hard (single-tree, S-DIORA) chart: text-only DioraMLP.  Every refusal of its own before any launch, then the body's.
+extern "C" int cliora_chart_forward_hard(cliora_plan* plan, const cliora_params* P, const float* x_span, float* inside_h, float* inside_s,
+                                         float* outside_h, float* outside_s, int32_t* sel_in, int32_t* sel_out, void* fwd_ws,
+                                         size_t fwd_ws_bytes, int flags, void* stream) {
+    if (!plan || !P) return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: NULL argument");
+    const Plan& p = plan->p;
+    if (p.arch != 0) return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: TreeLSTM plan (a hard chart is text-only DioraMLP)");
+    if (p.R > 0)
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: a CLIORA plan (R > 0) is not supported (the attention re-normalises an inside cell "
+                                   "between its aggregate and the scoring)");
+    if (P->root_mat) return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: compress (root_mat) is not supported");
+    if (flags & CLIORA_FWD_PAIR_STATES)
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: CLIORA_FWD_PAIR_STATES is not supported (a hard level composes one pair per cell)");
+    if (flags & ~(1 | CLIORA_FWD_NO_BACKWARD | CLIORA_FWD_HARD_DENSE)) return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: unknown flag bit");
+    if (p.is_long() && !(flags & CLIORA_FWD_NO_BACKWARD))
+        return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: L > 64 is forward only: pass CLIORA_FWD_NO_BACKWARD");
+    if (!sel_in || !sel_out) return fail(CLIORA_EINVAL, "cliora_chart_forward_hard: NULL selection array (sel_in and sel_out are (B, C) int32 each)");
+    return chart_forward_body(plan, P, x_span, nullptr, nullptr, inside_h, inside_s, outside_h, outside_s, nullptr, fwd_ws, fwd_ws_bytes,
+                              flags & ~CLIORA_FWD_HARD_DENSE, stream, nullptr, sel_in, sel_out, (flags & CLIORA_FWD_HARD_DENSE) ? 2 : 1);
 }
 extern "C" int cliora_chart_forward(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span,
                                     const float* drop_mask, float* inside_h, float* inside_s, float* outside_h,

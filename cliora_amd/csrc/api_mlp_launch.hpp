@@ -3,6 +3,7 @@
 #pragma once
 #include "api_common.hpp"
 #include "level_kernels.hpp"
+#include "hard_kernels.hpp"
 
 // ------------------------------------------------------------------ one dispatcher per template axis
 // f(Int<NR>): the attention kernels keep a wave's regions in registers: 9 per wave cover R <= 36 (the reference's 36 boxes), 16 cover R <= 64
@@ -125,6 +126,46 @@ static int launch_level_project(hipStream_t st, int SP, const ProjSeg& q, hipEve
         return CLIORA_OK;
     };
     // a block's MFMA work and operand bytes are fixed by its tile: wide tiles only when the launch still covers the chip
+    const bool wide = nt % 5 == 0 && nrg * (nt / 5) >= KSPLIT_MIN_BLOCKS;
+    return with_long(lng, [&](auto LONG) {
+        return with_parts(SP, [&](auto SP_) { return wide ? launch(Int<5>{}, SP_, LONG) : launch(Int<1>{}, SP_, LONG); });
+    });
+}
+
+// ------------------------------------------------------------------ hard (single-tree) charts (hard_kernels.hpp)
+// y = relu(W2 relu(PL(a) + PR(b)) + b2) of the ONE pair each cell of the level selected (sel: the pass's (B, C) selections), into part 0
+// of sg.HP; ReLU bits at the selected pair rows of ymask (the caller has cleared the level's rows).  cus: the device's compute units.
+static int launch_level_compose_hard(hipStream_t st, const ComposeSeg& sg, const int32_t* sel, int S3, int Dp, int ct, int ncb, uint32_t* ymask,
+                                     int cus) {
+    if (sg.lv.N <= 0 || sg.lv.ncell <= 0) return CLIORA_OK;
+    const int S = compose_image_stride(S3, Dp);
+    const HardComposeGeom hg = hard_compose_geom((sg.lv.ncell + 15) / 16, ncb, cus > 0 ? cus : 256);
+    return with_compose_shape(ct, Dp, [&](auto CT, auto K16, auto F32) {
+        constexpr int ct_ = decltype(CT)::value, k16 = decltype(K16)::value;
+        constexpr bool f32 = decltype(F32)::value;
+        OKR(cliora_ensure_max_lds((const void*)level_compose_hard<ct_, k16, f32>));
+        hipLaunchKernelGGL((level_compose_hard<ct_, k16, f32>), dim3(hg.gx, ncb), dim3(512), compose_lds_bytes(ct_, S, false), st, sg.Wimg, S, Dp,
+                           sg.lv, sel, sg.PA, sg.lda, sg.PB, sg.ldb, sg.bias, hg.tpw, sg.HP, Dp, ymask);
+        LAUNCHOK("level_compose_hard");
+        NOTE_LAUNCH(inst("level_compose_hard", ct_, k16, f32 ? "f32" : "bf16x3"));
+        return CLIORA_OK;
+    });
+}
+
+// launch_level_project with the hard tail on the riding scores (sel: the selections of the scored pass); no stop event: the hard
+// schedule runs on one stream
+static int launch_level_project_hard(hipStream_t st, int SP, const ProjSeg& q, bool lng, int32_t* sel) {
+    const int nt = q.ntc, nrg = (q.ncell + 15) / 16;
+    const int nrgp = xcd_pad(nrg);
+    auto launch = [&](auto CT, auto SP_, auto LONG) {
+        const int ncb = nt / decltype(CT)::value;
+        hipLaunchKernelGGL((level_project_hard<decltype(CT)::value, decltype(SP_)::value, decltype(LONG)::value>), dim3(q.sc.nscore + nrgp * ncb),
+                           dim3(256), 0, st, q.Wfrag, q.K, nrg, nrgp, ncb, q.ncell, q.Lc, q.C, q.off, q.HP, q.hp_stride, q.normalize, q.bias, q.P,
+                           q.ldp, q.H, q.nrm, q.sc, sel);
+        LAUNCHOK("level_project_hard");
+        NOTE_LAUNCH(inst("level_project_hard", decltype(CT)::value, decltype(SP_)::value, decltype(LONG)::value ? "long" : "short"));
+        return CLIORA_OK;
+    };
     const bool wide = nt % 5 == 0 && nrg * (nt / 5) >= KSPLIT_MIN_BLOCKS;
     return with_long(lng, [&](auto LONG) {
         return with_parts(SP, [&](auto SP_) { return wide ? launch(Int<5>{}, SP_, LONG) : launch(Int<1>{}, SP_, LONG); });

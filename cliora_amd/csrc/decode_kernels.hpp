@@ -172,4 +172,19 @@ static __global__ __launch_bounds__(CKY_WAVES * 64) void cky_kernel(int L, int C
     if (spans && threadIdx.x == 0 && n > 1) emit_spans(bsp, t, reinterpret_cast<int32_t*>(cky_smem + lay.stk), spans + (size_t)b * (L - 1) * 2);
 }
 
+// The tree of a hard chart (cliora_chart_forward_hard): every inside cell already names its split, so the tree
+// falls out of the selections without a CKY pass.  One wave per sentence, of which lane 0 walks from the root with walk_spans' explicit
+// stack (3 (L + 1) ints of LDS): spans (B, L-1, 2) in emit_spans' order.  sel (B, C): the split of every cell above the leaves, kept
+// inside [0, level) whatever the array holds; L >= 2.
+static __global__ __launch_bounds__(64) void hard_spans_kernel(int L, int C, int B, const int32_t* __restrict__ sel, int32_t* __restrict__ spans) {
+    __shared__ int32_t stk[3 * (128 + 1)];           // walk_stack_bytes of the longest plan (128 words)
+    const int b = blockIdx.x;
+    if (b >= B || threadIdx.x != 0) return;
+    const int32_t* s = sel + (size_t)b * C;
+    walk_spans<false>(L, 0, stk, spans + (size_t)b * (L - 1) * 2, [&](int level, int pos, int, int&, int&) {
+        const int off = level * L - level * (level - 1) / 2;         // cells of the levels below `level`
+        return min(max(s[off + pos], 0), level - 1);
+    });
+}
+
 }  // namespace cliora

@@ -25,6 +25,19 @@ inline int ws_grid(int ntiles, int column_blocks, int waves, int cus = 256) {
     return xcd_pad_within(ceil_div(ntiles, waves * passes), cap);
 }
 
+// level_compose_hard (hard_kernels.hpp): `ntiles` (> 0) row tiles of one level, a workgroup of 8 waves per column block's weight image.
+// A level has few tiles and a workgroup pays for its image before its first MFMA, so the tiles are spread: tpw = the fewest tiles per
+// workgroup (one per wave, at most 8) with which one round of workgroups per column block still fits the chip; gx = the workgroups that
+// needs, at most the chip's share per column block (the waves then walk on by gx * tpw), XCD-padded within it.  Every tile is taken
+// exactly once: blocks with x * tpw >= ntiles return at once.
+struct HardComposeGeom { int tpw, gx; };
+inline HardComposeGeom hard_compose_geom(int ntiles, int column_blocks, int cus = 256) {
+    const int cap = std::max(1, cus / std::max(1, column_blocks));
+    const int tpw = std::min(8, std::max(1, ceil_div(ntiles, cap)));
+    const int gx = std::min(cap, ceil_div(ntiles, tpw));
+    return {tpw, xcd_pad_within(gx, cap)};
+}
+
 // Split-K kernels: row groups of `rt` sixteen-row tiles; linear id = rg + cb * nrgp, so the column blocks of a row group share an XCD
 struct RowGroups { int nrg, nrgp; };
 inline RowGroups row_groups(int nrows, int rt) {

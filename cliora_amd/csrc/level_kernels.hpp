@@ -612,9 +612,13 @@ struct ScoreArgs {
 // LONG: a level of a long plan (plan.hpp: 64 < L <= 128), up to 127 splits.  The walk above already covers them (lane j of a wave holds
 // split w + 4 j); sh_s then holds 128 scores and the softmax tail takes two splits per lane (n = lane and lane + 64), max and sums over
 // both.  A cell with N <= 64 gets the bits of the short tail (the second split adds an exact 0).
+//
+// HARD (S-DIORA): the tail writes a one-hot weight row instead of the softmax -- Pp = 1 at the LOWEST split that
+// attains the row's maximum, 0 elsewhere -- the cell's score is that split's score as it is (no p.s sum), and the split goes to
+// sel[chart row].  Sp as in the soft tail.  The soft instances do not read `sel`.
 constexpr int SCORE_KF = 2;
-template <bool LONG = false>
-__device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh_s) {
+template <bool LONG = false, bool HARD = false>
+__device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh_s, int32_t* __restrict__ sel = nullptr) {
     const LevelArgs& g = sc.g;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -714,6 +718,21 @@ __device__ __forceinline__ void score_cell(const ScoreArgs& sc, int t, float* sh
     }
     __syncthreads();
     if (wave != 0) return;
+    if constexpr (HARD) {
+        const bool h0 = lane < g.N, h1 = LONG && lane + 64 < g.N;
+        const float s0 = h0 ? sh_s[lane] : -INFINITY, s1 = h1 ? sh_s[lane + 64] : -INFINITY;
+        const float m = wave_max(LONG ? fmaxf(s0, s1) : s0);
+        // the first maximum: the lowest set bit of the lanes that hold it (a row of NaNs has none: split 0)
+        const unsigned long long b0 = __ballot(h0 && s0 == m), b1 = LONG ? __ballot(h1 && s1 == m) : 0ull;
+        const int k = b0 ? __ffsll(b0) - 1 : (b1 ? 63 + __ffsll(b1) : 0);
+        if (h0) { sc.Sp[row0 + lane] = s0; sc.Pp[row0 + lane] = lane == k ? 1.f : 0.f; }
+        if (h1) { sc.Sp[row0 + lane + 64] = s1; sc.Pp[row0 + lane + 64] = lane + 64 == k ? 1.f : 0.f; }
+        if (lane == (k & 63)) {
+            sc.Sout[(size_t)bC + g.off + p] = k < 64 ? s0 : s1;
+            sel[(size_t)bC + g.off + p] = k;
+        }
+        return;
+    }
     if constexpr (LONG) {
         const bool h0 = lane < g.N, h1 = lane + 64 < g.N;
         const float s0 = h0 ? sh_s[lane] : -INFINITY, s1 = h1 ? sh_s[lane + 64] : -INFINITY;
@@ -741,6 +760,13 @@ template <bool LONG = false>
 static __global__ __launch_bounds__(256) void level_scores(ScoreArgs sc) {
     __shared__ float sh_s[LONG ? 128 : 64];
     score_cell<LONG>(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), sh_s);
+}
+
+// ... and with the hard tail (the hard schedule's own instance: the soft one above keeps its arguments)
+template <bool LONG = false>
+static __global__ __launch_bounds__(256) void level_scores_hard(ScoreArgs sc, int32_t* __restrict__ sel) {
+    __shared__ float sh_s[LONG ? 128 : 64];
+    score_cell<LONG, true>(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), sh_s, sel);
 }
 
 // one projection block (16 rows x CT*16 columns) of level_project: block `bid` of nrgp * ncolblocks
@@ -863,6 +889,26 @@ __global__ __launch_bounds__(256) void level_project(const float* __restrict__ W
             score_cell<true>(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), reinterpret_cast<float*>(&part[0][0][0]));
         } else {
             score_cell(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), &sh_ss[0][0]);
+        }
+        return;
+    }
+    project_block<CT, SP>(part, sh_ss, (int)blockIdx.x - sc.nscore, Wfrag, K, nrg, nrgp, ncell, Lc, C, off, HP, hp_stride, normalize, bias, P, ldp, H, nrm);
+}
+
+// level_project whose riding scores end in the hard tail (sel: the selection array of the scored pass)
+template <int CT, int SP, bool LONG = false>
+__global__ __launch_bounds__(256) void level_project_hard(const float* __restrict__ Wfrag, int K, int nrg, int nrgp, int ncolblocks,
+                                                          int ncell, int Lc, int C, int off, const float* __restrict__ HP, size_t hp_stride,
+                                                          int normalize, const float* __restrict__ bias, float* __restrict__ P, int ldp,
+                                                          float* __restrict__ H, float* __restrict__ nrm, ScoreArgs sc, int32_t* __restrict__ sel) {
+    __shared__ float4 part[4][CT][64];
+    __shared__ float sh_ss[4][16];
+    (void)ncolblocks;
+    if ((int)blockIdx.x < sc.nscore) {
+        if constexpr (LONG) {
+            score_cell<true, true>(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), reinterpret_cast<float*>(&part[0][0][0]), sel);
+        } else {
+            score_cell<false, true>(sc, cell_of_block(blockIdx.x, sc.g.B, sc.g.Lc), &sh_ss[0][0], sel);
         }
         return;
     }

@@ -79,13 +79,15 @@ class ChartWorkspaces(list):
     cliora_amd.structured hands the chart node a cotangent on the inside split scores: `split_cot` is a one-element list that the
     node of that forward shares (ChartFunction keeps it in its ctx), so a cotangent left there can reach that forward's backward only.
     `lengths`: the int32 device lengths of a padded training chart of mixed lengths (RaggedChartFunction), else None; the structured
-    losses read each sentence's own triangle through them."""
-    __slots__ = ('split_cot', 'lengths')
+    losses read each sentence's own triangle through them.  `selection`: the (sel_in, sel_out) int32 (B, C) device tensors a hard chart
+    (cliora_chart_forward_hard) writes its selected splits into, set by the module before the node runs, else None."""
+    __slots__ = ('split_cot', 'lengths', 'selection')
 
     def __init__(self):
         super().__init__()
         self.split_cot = [None]
         self.lengths = None
+        self.selection = None
 
 
 def check_lengths(lengths, B, dev):
@@ -95,11 +97,13 @@ def check_lengths(lengths, B, dev):
     return lengths.contiguous()
 
 
-def _chart_forward(entry, plan, flags, x_span, obj_span, drop_mask, params, lengths=None, root_levels=None):
+def _chart_forward(entry, plan, flags, x_span, obj_span, drop_mask, params, lengths=None, root_levels=None, selection=None):
     """The call of a chart forward entry, for every route: the inputs made contiguous fp32, the parameters detached, the outputs and
     the workspace allocated (chart_buffers), inside_c zeroed for a plan with regions, then `entry` under the tensors' device.  With
     `lengths` (a padded chart of mixed lengths) the entry also gets them, `root_levels` as the entry takes it and a fresh status
-    word.  -> (x_span, lengths, obj_span, drop_mask, ptens, the four charts, inside_c or None, workspace, status or None)."""
+    word.  With `selection` (a hard chart, text-only: `entry` is cliora_chart_forward_hard) the entry gets the two selection arrays
+    in place of the regions' arguments.
+    -> (x_span, lengths, obj_span, drop_mask, ptens, the four charts, inside_c or None, workspace, status or None)."""
     if not x_span.is_cuda:
         raise _lib.ChartLibError('the chart path runs on the GPU only (got a CPU tensor)')
     D, dev, vl, status, tail = plan.D, x_span.device, obj_span is not None, None, ()
@@ -114,8 +118,12 @@ def _chart_forward(entry, plan, flags, x_span, obj_span, drop_mask, params, leng
             status = torch.empty(1, device=dev, dtype=torch.int32)
             tail = (_ptr(lengths), root_levels, _ptr(status))
         pst = _param_struct(ptens)
-        _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask), *map(_ptr, outs), _ptr(inside_c),
-                  _ptr(ws), nbytes, flags, *tail, _stream())
+        if selection is not None:
+            _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), *map(_ptr, outs), *map(_ptr, selection), _ptr(ws), nbytes, flags,
+                      _stream())
+        else:
+            _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask), *map(_ptr, outs), _ptr(inside_c),
+                      _ptr(ws), nbytes, flags, *tail, _stream())
     return x_span, lengths, obj_span, drop_mask, ptens, outs, inside_c, ws, status
 
 
@@ -151,7 +159,8 @@ def _chart_backward(ctx, x_span, obj_span, charts, cots, lengths=None):
 class ChartFunction(torch.autograd.Function):
     """One autograd node for the whole inside-outside chart, text-only (obj_span None) or with image regions (a plan of R > 0).
 
-    forward  -> cliora_chart_forward   (replaces diora.py:283-398 as executed by DioraBase.forward)
+    forward  -> cliora_chart_forward   (replaces diora.py:283-398 as executed by DioraBase.forward); cliora_chart_forward_hard when the
+                holder carries selection arrays (a hard chart: same workspace, same backward)
     backward -> cliora_chart_backward  (replaces what autograd replays through those lines), or cliora_chart_backward_split when a
                 bracket loss of the same forward left a cotangent on the split scores (cliora_amd.structured)
     Inputs: plan, holder (list that receives the forward workspace), run_outside, x_span, obj_span, drop_mask, then the parameter
@@ -163,8 +172,10 @@ class ChartFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, holder, run_outside, x_span, obj_span, drop_mask, *params):
         run_outside, vl = int(run_outside), obj_span is not None
-        x_span, _, obj_span, drop_mask, ptens, outs, inside_c, ws, _ = _chart_forward('cliora_chart_forward', plan, run_outside, x_span,
-                                                                                     obj_span, drop_mask, params)
+        selection = getattr(holder, 'selection', None)
+        x_span, _, obj_span, drop_mask, ptens, outs, inside_c, ws, _ = _chart_forward(
+            'cliora_chart_forward' + ('_hard' if selection is not None else ''), plan, run_outside, x_span, obj_span, drop_mask, params,
+            selection=selection)
         ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.drop_mask, ctx.vl = plan, run_outside & 1, ws, ptens, drop_mask, vl
         ctx.split_cot = getattr(holder, 'split_cot', None)      # cliora_amd.structured leaves d_split there (a plain list: no such input)
         ctx.save_for_backward(x_span, *((obj_span,) if vl else ()), *outs)
@@ -296,6 +307,11 @@ class Chart(object):
 
 class DioraBase(nn.Module):
     vision_language = False
+    # hard (S-DIORA) charts: every cell encodes its single best split.  A plain settable attribute; only the
+    # text-only cliora_amd.diora.DioraMLP takes it (forward refuses the rest).  hard_dense: the same chart through the dense compose
+    # kernels (CLIORA_FWD_HARD_DENSE: the on-device cross-check and the benchmark's baseline, not a tuning switch).
+    hard = False
+    hard_dense = False
 
     def __init__(self, size, word_mat=None, cate_mat=None, outside=True, normalize='unit', compress=False, share=True):
         super().__init__()
@@ -371,7 +387,7 @@ class DioraBase(nn.Module):
         # plain attributes, written straight into the instance dict: nn.Module.__setattr__ walks its parameter / buffer / module
         # registries for every assignment (~3.5 us each; a configs[0]-sized step is bound by the host)
         self.__dict__.update(batch_size=None, length=None, chart=None, atten_score=None, all_atten_score=None, vg_atten_score=None,
-                             _wss=None, _plan=None, _ragged_status=None)
+                             _wss=None, _plan=None, _ragged_status=None, selection=None)
 
     def _check_long(self, L, needs_grad, hooks):
         """64 < L <= 128 runs on a forward-only plan (include/cliora_chart.h): every refusal before any launch.  A padded chart of mixed
@@ -386,6 +402,21 @@ class DioraBase(nn.Module):
                                      'per-pair rows)' % (L, _lib.MAX_L))
         if self.compress:
             raise _lib.ChartLibError('L = %d > %d: compress = True is not supported' % (L, _lib.MAX_L))
+
+    def _check_hard(self, hooks):
+        """What a hard chart does not take: every refusal before any launch."""
+        if self.vision_language:
+            raise NotImplementedError('hard=True: cliora_amd.cliora.DioraMLP is not supported (the attention re-normalises an inside cell '
+                                      'between its aggregate and the scoring); a hard chart is text-only cliora_amd.diora.DioraMLP')
+        if self.plan_arch != 0:
+            raise NotImplementedError('hard=True: DioraTreeLSTM is not supported; a hard chart is text-only cliora_amd.diora.DioraMLP')
+        if self.compress:
+            raise NotImplementedError('hard=True: compress = True is not supported')
+        if hooks:
+            raise NotImplementedError('hard=True: inside_hook / outside_hook overrides get no per-pair states (a hard level composes one '
+                                      'pair per cell)')
+        if self.__dict__.get('_ragged') is not None or self.__dict__.get('_ragged_train') is not None:
+            raise NotImplementedError('hard=True: a padded chart of mixed lengths is not supported')
 
     def _check_padded(self, hooks):
         """What no padded chart of mixed lengths takes, for inference or with a backward."""
@@ -476,6 +507,8 @@ class DioraBase(nn.Module):
         needs_grad = torch.is_grad_enabled() and (x_span.requires_grad or (obj_embed_span is not None and obj_embed_span.requires_grad)
                                                   or any(t is not None and t.requires_grad for t in params))
         hooks = self._hook_overridden('inside_hook') or self._hook_overridden('outside_hook')
+        if self.hard:
+            self._check_hard(hooks)
         self._check_long(L, needs_grad, hooks)
         plan = _lib.get_plan(B, L, D, self.share, self.normalize, R, dev_index, arch=self.plan_arch)
         flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
@@ -490,11 +523,15 @@ class DioraBase(nn.Module):
             raise _lib.ChartLibError('a padded training chart of mixed lengths needs gradients enabled; cliora_amd.ragged.forward_ragged '
                                      'runs the same batch for inference')
         else:
+            if self.hard:          # the selections, -1 where the call writes none (leaves, the outside root, no outside pass)
+                sel = torch.full((2, B, plan.C), -1, dtype=torch.int32, device=x_span.device)
+                holder.selection = (sel[0], sel[1])
+                flags |= _lib.FWD_HARD_DENSE if self.hard_dense else 0
             charts = self._run_chart(plan, holder, flags, x_span, obj_embed_span, params)
         ch = Chart()
         ch.inside_h, ch.inside_s, ch.outside_h, ch.outside_s, ch.inside_c, ch.outside_c = charts      # a zero cell state: on first read (Chart)
         d = self.__dict__
-        d['chart'], d['_wss'], d['_plan'] = ch, holder, plan
+        d['chart'], d['_wss'], d['_plan'], d['selection'] = ch, holder, plan, holder.selection
         if self._hook_overridden('init_with_batch'):      # analysis/utils.py:67-76 wraps it: then it gets the reference's arguments
             self.init_with_batch(ch.inside_h[:, :L], ch.inside_c[:, :L])
         else:
@@ -578,6 +615,42 @@ class DioraBase(nn.Module):
                 for ws, sl in parts:
                     _lib.call('cliora_cky_spans', plan.handle, _ptr(ws), None, _ptr(spans[sl]), _stream())
         return spans
+
+    # ---- the tree of a hard chart: it falls out of the selections, no CKY pass
+    def _hard_selection(self):
+        if self.__dict__.get('selection') is None:
+            raise _lib.ChartLibError('the last forward was not a hard chart (DioraMLP(hard=True), or set .hard): there are no selections')
+        return self.selection
+
+    def hard_spans_device(self, out=None):
+        """The spans of the tree the hard chart's inside selections spell (cliora_hard_spans), in the layout of cky_spans_device: an
+        int32 tensor (B, L-1, 2) on the chart's GPU, written into `out` when given."""
+        sel_in, _ = self._hard_selection()
+        plan = self._plan
+        spans, _ = span_buffer(self, out)
+        if plan.L > 1:
+            with torch.cuda.device(spans.device):
+                _lib.call('cliora_hard_spans', plan.handle, _ptr(sel_in), _ptr(spans), _stream())
+        return spans
+
+    def hard_spans(self):
+        """hard_spans_device as an int32 array (B, L-1, 2): one device-to-host copy."""
+        self._hard_selection()
+        if self._plan.L < 2:
+            import numpy as np
+            return np.zeros((self._plan.B, 0, 2), dtype=np.int32)
+        return self.hard_spans_device().cpu().numpy()
+
+    def hard_tree(self):
+        """The hard chart's tree per sentence as nested tuples of word positions, as cky() returns the Viterbi tree."""
+        return self.trees_from_spans(self.hard_spans())
+
+    @property
+    def inside_tree(self):
+        """What the reference's TreesFromDiora.parse_batch reads (analysis/diora_tree.py:47-64): inside_tree[(b, 0)][(L-1, 0)] is the
+        list of the (level, pos) cells of sentence b's tree above the leaves."""
+        from .hard import inside_tree_from_spans
+        return inside_tree_from_spans(self.hard_spans())
 
     @staticmethod
     def trees_from_spans(spans):
@@ -727,6 +800,10 @@ class DioraBase(nn.Module):
 
 
 class DioraMLP(DioraBase):
+    def __init__(self, *args, hard=False, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.hard = bool(hard)
+
     def init_parameters(self):
         self.inside_score_func = Bilinear(self.size)
         self.inside_compose_func = ComposeMLP(self.size, leaf=True)

@@ -94,16 +94,21 @@ def ground_batch(diora, batch_map, spans=None, decode='viterbi'):
     on the current stream and copies every output back in one transfer.  `spans`: the (B, L-1, 2) int32 device spans of
     ``diora.cky_spans_device()``; None decodes them here, into the output buffer.  Text-only DIORA (``atten_score`` None): F1 counts
     only, the phrases are not read (the reference skips them too).  decode: which tree is decoded when `spans` is None -- 'viterbi'
-    (cky_spans_device) or 'mbr' (mbr_spans_device, cliora_amd.posterior)."""
+    (cky_spans_device), 'mbr' (mbr_spans_device, cliora_amd.posterior) or 'hard' (hard_spans_device: the tree a hard chart's own
+    selections spell, uniform batches only; refused on a module whose last forward was not hard)."""
     from . import ragged
-    ragged.decode_entry(decode)
+    if decode == 'hard':
+        if getattr(diora, 'selection', None) is None:
+            raise ValueError("decode='hard' needs a hard chart: the module's last forward ran with hard=False")
+    else:
+        ragged.decode_entry(decode)
     plan = diora._plan
     B, L = plan.B * len(diora._wss), plan.L
     atten = getattr(diora, 'atten_score', None)
     tg = Targets(batch_map.get('VG_GT') if atten is not None else None, batch_map.get('GT'), B, L)
     boxes = batch_map['boxes'] if atten is not None else None
     if spans is None:
-        spans = diora.mbr_spans_device if decode == 'mbr' else diora.cky_spans_device
+        spans = {'mbr': diora.mbr_spans_device, 'hard': diora.hard_spans_device}.get(decode, diora.cky_spans_device)
     return ground(atten, boxes, tg, spans, device=diora._wss[0].device)
 
 
@@ -308,8 +313,11 @@ def batch_records(res, trees, sentences, example_ids, idx2word, with_boxes, post
 def evaluate(net, batches, idx2word, out_path=None, postprocess=False, decode='viterbi'):
     """parse.py:run (lines 101-291) on a harness.Net: eval mode, outside pass on, batches of length <= 2 skipped; returns the eight
     numbers it prints (METRICS) and writes parse.jsonl to `out_path` when given.  decode: 'viterbi' (the reference's tree) or 'mbr'
-    (the minimum-Bayes-risk tree of cliora_amd.posterior: F1, CCRA and the records are then those of that tree)."""
+    (the minimum-Bayes-risk tree of cliora_amd.posterior: F1, CCRA and the records are then those of that tree) or 'hard' (the tree
+    a hard chart's selections spell, hard_spans_device; refused on a module that is not hard)."""
     diora = net.diora
+    if decode == 'hard' and not getattr(diora, 'hard', False):
+        raise ValueError("decode='hard' needs a hard chart module (DioraMLP(hard=True), build_net(hard=True))")
     diora.outside = True
     net.eval()
     ev = Evaluator()

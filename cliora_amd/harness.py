@@ -419,12 +419,15 @@ def select_diora(arch, obj_feats):
 
 def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=True, normalize='unit',
               vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp', bracket_loss_weight=0.0,
-              risk_loss_weight=0.0, entropy_loss_weight=0.0, full_softmax=False):
+              risk_loss_weight=0.0, entropy_loss_weight=0.0, full_softmax=False, hard=False):
     """What trainer.py:504-582 assembles, on the native chart modules.  full_softmax: the reconstruction loss is the exact one over the
-    whole table (ReconstructionSoftmaxLoss(full_vocab=True)) instead of the reference's sampled loss."""
+    whole table (ReconstructionSoftmaxLoss(full_vocab=True)) instead of the reference's sampled loss.  hard: the chart module encodes
+    every cell's single best split (S-DIORA, `--arch hard` of the reference's training script; text-only DioraMLP)."""
     embed = Embed(embeddings, embeddings.weight.shape[1], size)
     enc = ImageEncoder(img_dim, size)
     diora = select_diora(arch, obj_feats)(size, outside=True, normalize=normalize, compress=False, share=share)
+    if hard:
+        diora.hard = True            # forward refuses it on a module that is not the text-only DioraMLP
     losses = [ReconstructionSoftmaxLoss(embeddings, embeddings.weight.shape[1], size, k_neg=k_neg, full_vocab=full_softmax)]
     if vg_loss:
         losses.append(VGLoss(alpha_vg))

@@ -170,6 +170,32 @@ int cliora_chart_backward_split(cliora_plan* plan, const cliora_params* params,
                                 float* d_x_span, float* d_obj_span, const cliora_params* grads,
                                 int ran_outside, void* stream);
 
+/* Hard (single-tree, S-DIORA) chart of a text-only DioraMLP plan: every cell encodes its single best split instead of the softmax
+ * mixture.  Per cell of a level the split scores are those of cliora_chart_forward; then, with k the LOWEST split that attains their
+ * maximum: the weight row is one-hot at k, h = unit(y_k) (the compose output of pair k alone) and s = s_k.  Only the selected pair of
+ * a cell is composed (level_compose_hard: B * Lc rows per level instead of B * Lc * N).
+ *   sel_in / sel_out  (B, C) int32 each, caller-owned: k per cell of the inside / outside chart.  The leaves of sel_in and the root of
+ *                     sel_out -- and all of sel_out without an outside pass -- are not written.
+ *   flags             bit 0 = run the outside pass, CLIORA_FWD_NO_BACKWARD, CLIORA_FWD_HARD_DENSE
+ * The workspace is that of cliora_chart_forward (cliora_plan_fwd_workspace_bytes, same layout); the backward is cliora_chart_backward
+ * / _split on it, unchanged: with a one-hot weight row its softmax backward gives dS at the selected split and 0 elsewhere, its compose
+ * backward the gradient of the selected pair alone -- the gradient of "h = unit(y_k), s = s_k" with k held fixed.  The decodes that
+ * read the split scores (cliora_cky_spans, ...) work on such a workspace as on any other.
+ * Runs the per-level launch path on the caller's stream whatever cliora_set_wavefront / cliora_set_resident say.
+ * Refused before any launch: TreeLSTM plans, plans with regions (R > 0), compress (root_mat), CLIORA_FWD_PAIR_STATES, a long plan
+ * (L > 64) without CLIORA_FWD_NO_BACKWARD, NULL selection arrays.
+ * CLIORA_FWD_HARD_DENSE: the same one-hot weights through the dense compose kernels of cliora_chart_forward (every split composed and
+ * multiplied by 0 or 1) -- the on-device cross-check and the benchmark's baseline; same outputs, bit for bit. */
+#define CLIORA_FWD_HARD_DENSE 16
+int cliora_chart_forward_hard(cliora_plan* plan, const cliora_params* params, const float* x_span,
+                              float* inside_h, float* inside_s, float* outside_h, float* outside_s,
+                              int32_t* sel_in, int32_t* sel_out,
+                              void* fwd_workspace, size_t fwd_workspace_bytes, int flags, void* stream);
+/* The tree of a hard chart from its inside selections, no CKY pass: spans (B, L-1, 2) int32 device in the layout of cliora_cky_spans
+ * (children before parents, left subtree first, the root last).  One wave per sentence walks from the root with an explicit stack.
+ * Nothing is written for L < 2. */
+int cliora_hard_spans(cliora_plan* plan, const int32_t* sel_in, int32_t* spans, void* stream);
+
 /* DioraTreeLSTM (BASELINE config 5).  PARITY UNPINNED: the reference ships this composition only
  * as commented-out text (cliora/net/vg.py:28-76); what is implemented is that text on the
  * DioraBase skeleton (cliora/net/diora.py:283-398), constant = 1 inside / 0 outside (diora.py:174),
