@@ -52,6 +52,8 @@ ABI = {
     'cliora_chart_forward': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp]),
     'cliora_chart_forward_hard': (i32, [vp, pp] + [vp] * 7 + [vp, sz, i32, vp]),
     'cliora_hard_spans': (i32, [vp, vp, vp, vp]),
+    'cliora_chart_forward_ragged_hard': (i32, [vp, pp] + [vp] * 7 + [vp, sz, i32, vp, vp, vp, vp]),
+    'cliora_hard_spans_ragged': (i32, [vp] * 6),
     'cliora_chart_backward': (i32, [vp, pp] + [vp] * 11 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_backward_split': (i32, [vp, pp] + [vp] * 12 + [vp, sz, vp, sz, vp, vp, pp, i32, vp]),
     'cliora_chart_forward_ragged': (i32, [vp, pp] + [vp] * 8 + [vp, sz, i32, vp, u64, vp, vp]),

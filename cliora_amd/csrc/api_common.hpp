@@ -113,6 +113,11 @@ struct RaggedFwd {
 int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const float* x_span, const float* obj_span, const float* drop_mask,
                              float* inside_h, float* inside_s, float* outside_h, float* outside_s, float* inside_c, void* fwd_ws,
                              size_t fwd_ws_bytes, int run_outside, void* stream, const RaggedFwd* rg);
+// The body of cliora_chart_forward_hard (api_mlp.hip), and with rg that of cliora_chart_forward_ragged_hard (api_ragged.hip, which has
+// made its own refusals): hard = 1 the selected-pair compose, 2 the dense one (CLIORA_FWD_HARD_DENSE, already taken out of `flags`).
+int cliora_chart_forward_hard_run(cliora_plan* plan, const cliora_params* P, const float* x_span, float* inside_h, float* inside_s,
+                                  float* outside_h, float* outside_s, int32_t* sel_in, int32_t* sel_out, void* fwd_ws, size_t fwd_ws_bytes,
+                                  int flags, void* stream, const RaggedFwd* rg, int hard);
 
 // The ragged backward entries' extra arguments (api_ragged.hip: ragged_backward), handed to the backward's body (api_mlp.hip: BwdCall): the caller's
 // four chart cotangents (inside_h, inside_s, outside_h, outside_s; NULL = zero) and the buffers their masked copies go to

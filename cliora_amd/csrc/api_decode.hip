@@ -71,15 +71,30 @@ extern "C" int cliora_cky_spans_ragged(cliora_plan* plan, void* fwd_ws, const in
 }
 
 // The spans of a hard chart's tree from its inside selections (no workspace: the selections are the caller's)
-extern "C" int cliora_hard_spans(cliora_plan* plan, const int32_t* sel_in, int32_t* spans, void* stream) {
-    if (!plan) return fail(CLIORA_EINVAL, "cliora_hard_spans: NULL argument");
+// lengths: NULL (cliora_hard_spans: every sentence has L words, no status) or one per sentence of a padded chart (status zeroed first)
+static int launch_hard_spans(const char* who, cliora_plan* plan, const int32_t* sel_in, const int32_t* lengths, int32_t* spans,
+                             int32_t* status, void* stream) {
+    const std::string w = std::string(who) + ": ";
+    if (!plan) return fail(CLIORA_EINVAL, w + "NULL argument");
     const Plan& p = plan->p;
-    if (p.L < 2) return CLIORA_OK;                   // one word: no constituent, and no row to write
-    if (!sel_in || !spans) return fail(CLIORA_EINVAL, "cliora_hard_spans: NULL argument");
-    if (p.L > CLIORA_MAX_L_FWD) return fail(CLIORA_EINVAL, "cliora_hard_spans: L > 128");
-    hipLaunchKernelGGL(hard_spans_kernel, dim3(p.B), dim3(64), 0, (hipStream_t)stream, p.L, p.C, p.B, sel_in, spans);
+    hipStream_t st = (hipStream_t)stream;
+    if (p.L < 2 && !status) return CLIORA_OK;        // one word: no constituent, and no row to write
+    if (!sel_in || (!spans && p.L > 1)) return fail(CLIORA_EINVAL, w + "NULL argument");
+    if (p.L > CLIORA_MAX_L_FWD) return fail(CLIORA_EINVAL, w + "L > 128");
+    if (status) HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(hard_spans_kernel, dim3(p.B), dim3(64), 0, st, p.L, p.C, p.B, sel_in, spans, lengths, status);
     LAUNCHOK("hard_spans_kernel");
     return CLIORA_OK;
+}
+extern "C" int cliora_hard_spans(cliora_plan* plan, const int32_t* sel_in, int32_t* spans, void* stream) {
+    return launch_hard_spans("cliora_hard_spans", plan, sel_in, nullptr, spans, nullptr, stream);
+}
+// ... of each sentence's own triangle of a right-padded hard chart (cliora_chart_forward_ragged_hard, or the inside pass of
+// cliora_chart_forward_hard on the padded batch: prefix-closed)
+extern "C" int cliora_hard_spans_ragged(cliora_plan* plan, const int32_t* sel_in, const int32_t* lengths, int32_t* spans, int32_t* status,
+                                        void* stream) {
+    if (!lengths || !status) return fail(CLIORA_EINVAL, "cliora_hard_spans_ragged: NULL argument");
+    return launch_hard_spans("cliora_hard_spans_ragged", plan, sel_in, lengths, spans, status, stream);
 }
 
 // Every table of the kernel fits the CU's LDS up to L = 128 (posterior_kernels.hpp), so no plan needs device scratch today; the query

@@ -123,10 +123,11 @@ enum class FwdSchedule {
     InsideThenOutside,    // compress: the outside root is a projection of the inside root
     Ragged,               // mixed lengths in one padded chart: inside pass, mask, outside pass with root fix-ups (ragged_kernels.hpp)
     Hard,                 // cliora_chart_forward_hard: every cell encodes its best split alone; the wavefront's step order on the caller's stream
+    HardRagged,           // cliora_chart_forward_ragged_hard: Ragged's order built from the hard level step
 };
 
 static FwdSchedule pick_fwd_schedule(const cliora_plan* plan, bool vl, bool compress, int flags, const RaggedFwd* rg, int hard) {
-    if (hard) return FwdSchedule::Hard;      // whatever cliora_set_wavefront / cliora_set_resident say
+    if (hard) return rg ? FwdSchedule::HardRagged : FwdSchedule::Hard;      // whatever cliora_set_wavefront / cliora_set_resident say
     if (rg) return FwdSchedule::Ragged;
     if (!(flags & CLIORA_FWD_PAIR_STATES) && resident_pays(plan, vl, compress)) return FwdSchedule::Resident;
     if (compress) return FwdSchedule::InsideThenOutside;
@@ -560,6 +561,31 @@ struct FwdCall {
         return CLIORA_OK;
     }
 
+    // Mixed lengths in one padded HARD chart: forward_ragged's order from the hard level step.  The masked scores serve the hard tail as
+    // they serve the softmax (ragged_kernels.hpp); after a seed fix-up the level below is scored again by the hard tail alone, which
+    // rewrites its selections, weight rows and scores from final operands.  Last, -1 into the selection entries that mean nothing.
+    int forward_hard_ragged() const {
+        const PassOps in = pass_ops(false), out = pass_ops(true);
+        for (int k = 1; k <= L - 1; ++k) OKR(hard_level_step(in, k));
+        HIPOK(hipMemsetAsync(rg->status, 0, sizeof(int32_t), st));
+        hipLaunchKernelGGL(ragged_mask_inside_s, dim3((unsigned)(((size_t)B * C + 255) / 256)), dim3(256), 0, st, B, L, C,
+                           rg->lengths, IS, rg->status);
+        LAUNCHOK("ragged_mask_inside_s");
+        OKR(start_outside_chart());
+        for (int level = L - 2; level >= 0 && run_outside; --level) {
+            OKR(hard_level_step(out, level));
+            if (!rg->root_level(level)) continue;
+            hipLaunchKernelGGL(ragged_root_seed, dim3(B), dim3(4 * 64), 0, st, level, p.level_offset[level], C, p.Dp, rg->lengths, OH, OS,
+                               ws + f.nrmo, ws + f.po);
+            LAUNCHOK("ragged_root_seed");
+            if (level >= 1) OKR(launch_scores(st, score_args(out, level - 1, -1, 0), true));
+        }
+        hipLaunchKernelGGL(ragged_hard_mask_sel, dim3((unsigned)(((size_t)B * C + 255) / 256)), dim3(256), 0, st, B, L, C, run_outside,
+                           rg->lengths, sel_in, sel_out);
+        LAUNCHOK("ragged_hard_mask_sel");
+        return CLIORA_OK;
+    }
+
     // The shared head (packed parameters; on the launch path weight images, leaves, level-1 scores), the schedule, the un-pad copies.
     int run(ForkGuard& fork_guard) const {
         const bool resident = schedule == FwdSchedule::Resident;
@@ -579,6 +605,7 @@ struct FwdCall {
             case FwdSchedule::InsideThenOutside: OKR(forward_inside_then_outside()); break;
             case FwdSchedule::Ragged: OKR(forward_ragged()); break;
             case FwdSchedule::Hard: OKR(forward_hard()); break;
+            case FwdSchedule::HardRagged: OKR(forward_hard_ragged()); break;
         }
         if (padded && !(resident && run_outside)) {      // un-pad the charts (a resident call writes its own)
             CopyTable t; t.n = 0;
@@ -634,6 +661,12 @@ int cliora_chart_forward_run(cliora_plan* plan, const cliora_params* P, const fl
                              void* stream, const RaggedFwd* rg) {
     return chart_forward_body(plan, P, x_span, obj_span, drop_mask, inside_h, inside_s, outside_h, outside_s, inside_c, fwd_ws, fwd_ws_bytes,
                               run_outside, stream, rg, nullptr, nullptr, 0);
+}
+int cliora_chart_forward_hard_run(cliora_plan* plan, const cliora_params* P, const float* x_span, float* inside_h, float* inside_s,
+                                  float* outside_h, float* outside_s, int32_t* sel_in, int32_t* sel_out, void* fwd_ws, size_t fwd_ws_bytes,
+                                  int flags, void* stream, const RaggedFwd* rg, int hard) {
+    return chart_forward_body(plan, P, x_span, nullptr, nullptr, inside_h, inside_s, outside_h, outside_s, nullptr, fwd_ws, fwd_ws_bytes, flags,
+                              stream, rg, sel_in, sel_out, hard);
 }
 // A hard (single-tree, S-DIORA) chart: text-only DioraMLP.  Every refusal of its own before any launch, then the body's.
 extern "C" int cliora_chart_forward_hard(cliora_plan* plan, const cliora_params* P, const float* x_span, float* inside_h, float* inside_s,

@@ -5,6 +5,8 @@
 //
 // Layout: each entry is described once (RaggedEntry); ragged_refusals is what every entry refuses, under its own name and in one
 // order; ragged_forward and ragged_backward are the two bodies; the six extern "C" functions at the end are one call each.
+// cliora_chart_forward_ragged_hard (a hard padded chart, inference and training) has the argument list of cliora_chart_forward_hard and
+// states its own refusals.
 #include "api_common.hpp"
 
 // What an entry does with image regions: the text-only training pair refuses a CLIORA plan and obj_span, the _vl pair needs both
@@ -118,6 +120,33 @@ extern "C" int cliora_chart_forward_ragged_wide(RAGGED_FWD_PARAMS, const uint64_
 }
 extern "C" int cliora_chart_forward_ragged_train(RAGGED_FWD_PARAMS, uint64_t root_levels, int32_t* status, void* stream) {
     return ragged_forward(FORWARD_TRAIN, RAGGED_FWD_ARGS, MaskWords{{root_levels, 0}}.w, status, stream);
+}
+// A HARD (single-tree, S-DIORA) padded chart, for inference and for training: the refusals of
+// cliora_chart_forward_hard and of the ragged entries, each under this entry's name and before any HIP call, then the hard body with
+// the lengths.  There are no regions, so no obj_span / drop_mask / inside_c arguments: a drop_mask has nowhere to come from.
+extern "C" int cliora_chart_forward_ragged_hard(cliora_plan* plan, const cliora_params* P, const float* x_span, float* inside_h, float* inside_s,
+                                                float* outside_h, float* outside_s, int32_t* sel_in, int32_t* sel_out, void* fwd_ws,
+                                                size_t fwd_ws_bytes, int flags, const int32_t* lengths, const uint64_t* root_levels,
+                                                int32_t* status, void* stream) {
+    const std::string w = "cliora_chart_forward_ragged_hard: ";
+    if (!plan || !P || !lengths || !root_levels || !status) return fail(CLIORA_EINVAL, w + "NULL argument (plan, params, lengths, root_levels, status)");
+    const Plan& p = plan->p;
+    if (p.arch != 0) return fail(CLIORA_EINVAL, w + "TreeLSTM plans are not supported (a hard chart is text-only DioraMLP)");
+    if (p.R > 0) return fail(CLIORA_EINVAL, w + "CLIORA plans (R > 0) are not supported (the attention re-normalises an inside cell between "
+                                                "its aggregate and the scoring)");
+    if (P->root_mat) return fail(CLIORA_EINVAL, w + "compress (root_mat) is not supported");
+    if (flags & CLIORA_FWD_PAIR_STATES) return fail(CLIORA_EINVAL, w + "CLIORA_FWD_PAIR_STATES is not supported (a hard level composes one pair per cell)");
+    if (flags & ~(1 | CLIORA_FWD_NO_BACKWARD | CLIORA_FWD_HARD_DENSE)) return fail(CLIORA_EINVAL, w + "unknown flag bit");
+    if (p.is_long() && !(flags & CLIORA_FWD_NO_BACKWARD))
+        return fail(CLIORA_EINVAL, w + "L > 64 is forward only: pass CLIORA_FWD_NO_BACKWARD (the backward stops at 64 words)");
+    if (!sel_in || !sel_out) return fail(CLIORA_EINVAL, w + "NULL selection array (sel_in and sel_out are (B, C) int32 each)");
+    const int L = p.L;                  // 1 .. 128 (plan creation)
+    const uint64_t above0 = L >= 64 ? 0 : root_levels[0] >> L, above1 = L <= 64 ? root_levels[1] : (L >= 128 ? 0 : root_levels[1] >> (L - 64));
+    if (above0 || above1)
+        return fail(CLIORA_EINVAL, w + "root_levels has a bit set at or above L = " + std::to_string(L) + " (bit t stands for a sentence of t + 1 words)");
+    const RaggedFwd rg{lengths, {root_levels[0], root_levels[1]}, status};      // (the schedule zeroes status before it counts into it)
+    return cliora_chart_forward_hard_run(plan, P, x_span, inside_h, inside_s, outside_h, outside_s, sel_in, sel_out, fwd_ws, fwd_ws_bytes,
+                                         flags & ~CLIORA_FWD_HARD_DENSE, stream, &rg, (flags & CLIORA_FWD_HARD_DENSE) ? 2 : 1);
 }
 extern "C" int cliora_chart_backward_ragged(RAGGED_BWD_PARAMS) { return ragged_backward(BACKWARD, RAGGED_BWD_ARGS); }
 extern "C" int cliora_chart_forward_ragged_train_vl(RAGGED_FWD_PARAMS, uint64_t root_levels, int32_t* status, void* stream) {

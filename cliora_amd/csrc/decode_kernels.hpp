@@ -176,12 +176,22 @@ static __global__ __launch_bounds__(CKY_WAVES * 64) void cky_kernel(int L, int C
 // falls out of the selections without a CKY pass.  One wave per sentence, of which lane 0 walks from the root with walk_spans' explicit
 // stack (3 (L + 1) ints of LDS): spans (B, L-1, 2) in emit_spans' order.  sel (B, C): the split of every cell above the leaves, kept
 // inside [0, level) whatever the array holds; L >= 2.
-static __global__ __launch_bounds__(64) void hard_spans_kernel(int L, int C, int B, const int32_t* __restrict__ sel, int32_t* __restrict__ spans) {
+// lengths (B) or NULL (every sentence has L words; status is NULL then too): sentence b of a right-padded hard chart
+// (cliora_chart_forward_ragged_hard) is walked from its own root (n - 1, 0) with the padded chart's level offsets -- its n - 1 rows in
+// cliora_cky_spans_ragged's layout, (-1, -1) beyond.  A length outside [1, L]: every row -1, one count in *status, no selection read.
+static __global__ __launch_bounds__(64) void hard_spans_kernel(int L, int C, int B, const int32_t* __restrict__ sel, int32_t* __restrict__ spans,
+                                                               const int32_t* __restrict__ lengths, int32_t* __restrict__ status) {
     __shared__ int32_t stk[3 * (128 + 1)];           // walk_stack_bytes of the longest plan (128 words)
     const int b = blockIdx.x;
     if (b >= B || threadIdx.x != 0) return;
+    bool bad;
+    const int n = sentence_length(lengths, b, L, bad);
+    if (bad) atomicAdd(status, 1);                   // (without lengths n = L: never bad)
+    int32_t* out = spans + (size_t)b * (L - 1) * 2;
+    for (int i = 2 * max(n - 1, 0); i < 2 * (L - 1); ++i) out[i] = -1;
+    if (n < 2) return;
     const int32_t* s = sel + (size_t)b * C;
-    walk_spans<false>(L, 0, stk, spans + (size_t)b * (L - 1) * 2, [&](int level, int pos, int, int&, int&) {
+    walk_spans<false>(n, 0, stk, out, [&](int level, int pos, int, int&, int&) {
         const int off = level * L - level * (level - 1) / 2;         // cells of the levels below `level`
         return min(max(s[off + pos], 0), level - 1);
     });

@@ -56,6 +56,26 @@ static __global__ __launch_bounds__(256) void ragged_root_seed(int level, int of
     }
 }
 
+// A hard (S-DIORA) padded chart (cliora_chart_forward_ragged_hard): the masked scores serve the hard tail as they
+// serve the softmax -- a cell of a triangle other than its root keeps a valid pair, whose score is above every masked one, so the
+// first maximum is a valid pair and the one-hot row gives every invalid pair the weight 0.  A cell's valid outside pairs are its FIRST
+// n_b - level - 1 (plan.cpp: left siblings first, then right siblings by their end), so a selection is the exact-length chart's.
+// What is left is to say which entries of the two selection arrays mean something: after the last level, -1 goes wherever no cell of
+// a sentence selects -- one thread per (sentence, cell): beyond the triangle in both arrays; the leaves of sel_in; the sentence's root
+// (n_b - 1, 0) in sel_out, and all of sel_out without an outside pass.  (n < 1: every entry; n > L is treated as L.)
+static __global__ __launch_bounds__(256) void ragged_hard_mask_sel(int B, int L, int C, int run_outside, const int32_t* __restrict__ lengths,
+                                                                   int32_t* __restrict__ sel_in, int32_t* __restrict__ sel_out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)B * C) return;
+    const int b = (int)(i / C), cell = (int)(i - (size_t)b * C);
+    const int n = min(lengths[b], L);
+    int level = 0, off = 0;                          // the level whose cells [off, off + L - level) hold `cell`
+    while (cell >= off + (L - level)) { off += L - level; ++level; }
+    const bool own = (cell - off) + level < n;
+    if (!own || level == 0) sel_in[i] = -1;
+    if (!own || level >= n - 1 || !run_outside) sel_out[i] = -1;
+}
+
 // ---------------------------------------------------------------------------------
 // The backward of a padded chart.  The chains of cliora_chart_backward compute each sentence's own gradient
 // when (1) the cotangents of the cells beyond its triangle are zero -- those cells are unspecified outputs -- (2) every invalid pair

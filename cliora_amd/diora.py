@@ -118,9 +118,9 @@ def _chart_forward(entry, plan, flags, x_span, obj_span, drop_mask, params, leng
             status = torch.empty(1, device=dev, dtype=torch.int32)
             tail = (_ptr(lengths), root_levels, _ptr(status))
         pst = _param_struct(ptens)
-        if selection is not None:
+        if selection is not None:         # (with lengths: cliora_chart_forward_ragged_hard, root_levels as two host words)
             _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), *map(_ptr, outs), *map(_ptr, selection), _ptr(ws), nbytes, flags,
-                      _stream())
+                      *tail, _stream())
         else:
             _lib.call(entry, plan.handle, C.byref(pst), _ptr(x_span), _ptr(obj_span), _ptr(drop_mask), *map(_ptr, outs), _ptr(inside_c),
                       _ptr(ws), nbytes, flags, *tail, _stream())
@@ -199,7 +199,8 @@ class RaggedChartFunction(torch.autograd.Function):
     forward  -> cliora_chart_forward_ragged_train   (the padded chart's schedule with the backward's state written)
     backward -> cliora_chart_backward_ragged        (the split cotangent of a structured loss of the same forward included)
     With image regions (obj_span given, a plan of R > 0) the `_vl` forms of the two entries: the (B, C, R) dropout mask is taken and
-    d obj_span returned.
+    d obj_span returned.  When the holder carries selection arrays (a hard padded chart) the forward is
+    cliora_chart_forward_ragged_hard and the backward the same cliora_chart_backward_ragged.
     Inputs: plan, holder, run_outside, lengths (int32 device tensor (B,)), root_levels (the bit mask of {n - 1}), x_span, obj_span,
     drop_mask (both None for text-only DIORA), then the parameter tensors in _lib.PARAM_FIELDS order.  Outputs: the four charts --
     valid on each sentence's own triangle, unspecified beyond it, where their cotangents are ignored -- the status word (1,) int32
@@ -208,9 +209,13 @@ class RaggedChartFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan, holder, run_outside, lengths, root_levels, x_span, obj_span, drop_mask, *params):
         run_outside, vl = int(run_outside), obj_span is not None
+        selection = getattr(holder, 'selection', None)
+        if selection is not None:         # a hard padded chart (text-only): one entry for inference and training, the mask as two words
+            entry, mask = 'cliora_chart_forward_ragged_hard', split_root_levels(root_levels)
+        else:
+            entry, mask = 'cliora_chart_forward_ragged_train' + ('_vl' if vl else ''), int(root_levels)
         x_span, lengths, obj_span, drop_mask, ptens, outs, inside_c, ws, status = _chart_forward(
-            'cliora_chart_forward_ragged_train' + ('_vl' if vl else ''), plan, run_outside, x_span, obj_span, drop_mask, params, lengths,
-            int(root_levels))
+            entry, plan, run_outside, x_span, obj_span, drop_mask, params, lengths, mask, selection=selection)
         ctx.plan, ctx.run_outside, ctx.ws, ctx.ptens, ctx.root_levels = plan, run_outside & 1, ws, ptens, int(root_levels)
         ctx.drop_mask, ctx.vl = drop_mask, vl
         ctx.split_cot = getattr(holder, 'split_cot', None)
@@ -236,20 +241,24 @@ def split_root_levels(mask):
     return (C.c_uint64 * 2)(mask & 0xFFFFFFFFFFFFFFFF, (mask >> 64) & 0xFFFFFFFFFFFFFFFF)
 
 
-def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_levels):
+def ragged_chart(plan, holder, outside, x_span, obj_span, params, lengths, root_levels, hard_dense=False):
     """cliora_chart_forward_ragged (include/cliora_chart.h): both passes of a right-padded batch of mixed lengths, inference only, so no
     autograd node.  lengths: int32 device tensor (B,); root_levels: the bit mask of {n - 1}, a Python int.  A long plan (L > 64) runs
     through cliora_chart_forward_ragged_wide, which takes the mask as two 64-bit words; a short plan through the entry it always ran
-    through.  -> inside_h, inside_s, outside_h, outside_s, inside_c (None for a text-only plan), status (1,) int32 on the device,
-    which the caller must read."""
-    entry, mask = 'cliora_chart_forward_ragged', int(root_levels)
-    if plan.L > _lib.MAX_L:
+    through.  A holder that carries selection arrays (a hard chart, text-only) runs cliora_chart_forward_ragged_hard at either length
+    (hard_dense: CLIORA_FWD_HARD_DENSE).  -> inside_h, inside_s, outside_h, outside_s, inside_c (None for a text-only plan), status
+    (1,) int32 on the device, which the caller must read."""
+    entry, mask, flags = 'cliora_chart_forward_ragged', int(root_levels), int(bool(outside)) | _lib.FWD_NO_BACKWARD
+    selection = getattr(holder, 'selection', None)
+    if plan.L > _lib.MAX_L or selection is not None:
         if mask < 0 or mask >> _lib.MAX_L_FWD:
             raise ValueError('root_levels holds a bit at or above %d' % _lib.MAX_L_FWD)
         entry, mask = 'cliora_chart_forward_ragged_wide', split_root_levels(mask)
-    _, _, _, _, _, outs, inside_c, ws, status = _chart_forward(entry, plan, int(bool(outside)) | _lib.FWD_NO_BACKWARD, x_span.detach(),
+    if selection is not None:
+        entry, flags = 'cliora_chart_forward_ragged_hard', flags | (_lib.FWD_HARD_DENSE if hard_dense else 0)
+    _, _, _, _, _, outs, inside_c, ws, status = _chart_forward(entry, plan, flags, x_span.detach(),
                                                                obj_span.detach() if obj_span is not None else None, None, params, lengths,
-                                                               mask)
+                                                               mask, selection=selection)
     holder.clear()
     holder.append(ws)
     return (*outs, inside_c, status)
@@ -330,6 +339,10 @@ class DioraBase(nn.Module):
         # cliora_amd.ragged sets the same pair around a TRAINING forward over such a batch (forward_ragged_train): the chart then is a
         # RaggedChartFunction node (text-only DIORA, or CLIORA with its regions)
         self.__dict__['_ragged_train'] = None
+        # ... and, around the forward of a HARD module over such a batch, these two in their place: the chart
+        # then runs through cliora_chart_forward_ragged_hard.  A hard module keeps refusing the two slots above (_check_hard).
+        self.__dict__['_ragged_hard'] = None
+        self.__dict__['_ragged_hard_train'] = None
         self.init_parameters()
         self.reset_parameters()
         self.reset()
@@ -442,8 +455,9 @@ class DioraBase(nn.Module):
     def _run_ragged_train(self, plan, holder, x_span, obj_embed_span, params, ragged):
         """_run_chart through RaggedChartFunction (with regions, DESIGN.md section 23: the mask's rows are those of the PADDED chart);
         the status word is left in _ragged_status."""
+        flags = int(bool(self.outside)) | (_lib.FWD_HARD_DENSE if holder.selection is not None and self.hard_dense else 0)
         *charts, self.__dict__['_ragged_status'], inside_c = RaggedChartFunction.apply(
-            plan, holder, int(bool(self.outside)), *ragged, x_span, *self._chart_inputs(plan, x_span, obj_embed_span), *params)
+            plan, holder, flags, *ragged, x_span, *self._chart_inputs(plan, x_span, obj_embed_span), *params)
         return (*charts, inside_c, None)
 
     def _hook_overridden(self, name):
@@ -489,7 +503,8 @@ class DioraBase(nn.Module):
     def _run_ragged(self, plan, holder, x_span, obj_embed_span, params, ragged):
         """_run_chart through cliora_chart_forward_ragged (cliora_amd.ragged); the status word is left in _ragged_status."""
         obj_span, _ = self._chart_inputs(plan, x_span, obj_embed_span)      # eval mode (_check_ragged): no dropout mask
-        *charts, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, obj_span, params, *ragged)
+        *charts, self.__dict__['_ragged_status'] = ragged_chart(plan, holder, self.outside, x_span, obj_span, params, *ragged,
+                                                                hard_dense=self.hard_dense)
         return (*charts, None)
 
     def forward(self, x_span, x_word=None, obj_embed_span=None, obj_embed_word=None):
@@ -513,6 +528,13 @@ class DioraBase(nn.Module):
         plan = _lib.get_plan(B, L, D, self.share, self.normalize, R, dev_index, arch=self.plan_arch)
         flags = int(bool(self.outside)) | (0 if needs_grad else _lib.FWD_NO_BACKWARD) | (_lib.FWD_PAIR_STATES if hooks else 0)
         ragged, ragged_train = self.__dict__.get('_ragged'), self.__dict__.get('_ragged_train')
+        hard_slots = self.__dict__.get('_ragged_hard'), self.__dict__.get('_ragged_hard_train')
+        if hard_slots != (None, None):     # a hard padded chart: the same two routes, the selection arrays on the holder
+            if not self.hard:
+                raise NotImplementedError('_ragged_hard / _ragged_hard_train are a hard module\'s slots (hard=False: _ragged / _ragged_train)')
+            ragged, ragged_train = hard_slots
+            sel = torch.empty((2, B, plan.C), dtype=torch.int32, device=x_span.device)      # every entry is written by the call
+            holder.selection = (sel[0], sel[1])
         if ragged is not None:
             self._check_ragged(needs_grad, hooks)
             charts = self._run_ragged(plan, holder, x_span, obj_embed_span, params, ragged)
@@ -622,28 +644,47 @@ class DioraBase(nn.Module):
             raise _lib.ChartLibError('the last forward was not a hard chart (DioraMLP(hard=True), or set .hard): there are no selections')
         return self.selection
 
-    def hard_spans_device(self, out=None):
+    def hard_spans_device(self, out=None, lengths=None):
         """The spans of the tree the hard chart's inside selections spell (cliora_hard_spans), in the layout of cky_spans_device: an
-        int32 tensor (B, L-1, 2) on the chart's GPU, written into `out` when given."""
+        int32 tensor (B, L-1, 2) on the chart's GPU, written into `out` when given.  lengths (int32 tensor (B,)): the chart is a
+        right-padded batch of mixed lengths -- cliora_hard_spans_ragged walks each sentence from its own root, rows beyond its n - 1
+        are (-1, -1) -- and the result is (spans, status): status (1,) int32 on the device counts the lengths outside [1, L], which
+        the caller must check."""
         sel_in, _ = self._hard_selection()
         plan = self._plan
         spans, _ = span_buffer(self, out)
-        if plan.L > 1:
-            with torch.cuda.device(spans.device):
+        with torch.cuda.device(spans.device):
+            if lengths is not None:
+                lengths = check_lengths(lengths.to(spans.device), plan.B, spans.device)
+                status = torch.empty(1, dtype=torch.int32, device=spans.device)
+                _lib.call('cliora_hard_spans_ragged', plan.handle, _ptr(sel_in), _ptr(lengths), _ptr(spans) if plan.L > 1 else None,
+                          _ptr(status), _stream())
+                return spans, status
+            if plan.L > 1:
                 _lib.call('cliora_hard_spans', plan.handle, _ptr(sel_in), _ptr(spans), _stream())
         return spans
 
-    def hard_spans(self):
-        """hard_spans_device as an int32 array (B, L-1, 2): one device-to-host copy."""
+    def hard_spans(self, lengths=None):
+        """hard_spans_device as an int32 array (B, L-1, 2): one device-to-host copy.  With lengths (a padded chart of mixed lengths)
+        a length outside [1, L] raises."""
         self._hard_selection()
+        if lengths is not None:
+            spans, status = host_copy(*self.hard_spans_device(lengths=lengths))
+            if status.any():
+                raise _lib.ChartLibError('cliora_hard_spans_ragged rejected %d sentence length(s)' % int(status.sum()))
+            return spans
         if self._plan.L < 2:
             import numpy as np
             return np.zeros((self._plan.B, 0, 2), dtype=np.int32)
         return self.hard_spans_device().cpu().numpy()
 
-    def hard_tree(self):
-        """The hard chart's tree per sentence as nested tuples of word positions, as cky() returns the Viterbi tree."""
-        return self.trees_from_spans(self.hard_spans())
+    def hard_tree(self, lengths=None):
+        """The hard chart's tree per sentence as nested tuples of word positions, as cky() returns the Viterbi tree.  With lengths:
+        of each sentence's own triangle of a padded chart."""
+        if lengths is None:
+            return self.trees_from_spans(self.hard_spans())
+        spans = self.hard_spans(lengths)
+        return [self.trees_from_spans(spans[b:b + 1, :int(n) - 1])[0] for b, n in enumerate(lengths.tolist())]
 
     @property
     def inside_tree(self):

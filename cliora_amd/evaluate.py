@@ -358,12 +358,18 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
     the eval losses per uniform-length batch (the reconstruction loss reads every leaf of the batch and shares its negatives, the
     contrastive and VG losses compare the sentences of a batch with each other), and their ops take no per-sentence lengths.  return_details: also a list with, per
     example, None (skipped) or a dict of spans (n-1, 2), sent (3,), hit / ccr / word / box per phrase and span_xyxy (n-1, 4).
-    decode: 'viterbi' or 'mbr', as ``evaluate``.  max_len: the longest sentence taken, 64 or up to 128 (an unfiltered test set); a
+    decode: 'viterbi' or 'mbr', as ``evaluate``, or 'hard' on a hard net (the packs then run cliora_chart_forward_ragged_hard and the
+    trees are those of cliora_hard_spans_ragged; refused on a net that is not hard).  max_len: the longest sentence taken, 64 or up to 128 (an unfiltered test set); a
     pack topped by a sentence of more than 64 words then holds at most `max_long_batch` sentences (``ragged.forward_ragged``)."""
     from . import ragged
-    entry = ragged.decode_entry(decode)
     diora = net.diora
-    keep = [i for i, ex in enumerate(examples) if len(ex['sentence']) > 2]
+    if decode == 'hard':                # before decode_entry, which keeps refusing the name: a hard net's own padded chart and walk
+        if not getattr(diora, 'hard', False):
+            raise ValueError("decode='hard' needs a hard chart module (DioraMLP(hard=True), build_net(hard=True))")
+        entry, forward_entry = 'cliora_hard_spans_ragged', 'cliora_chart_forward_ragged_hard'
+    else:
+        entry, forward_entry = ragged.decode_entry(decode), 'cliora_chart_forward_ragged'
+    keep =[i for i, ex in enumerate(examples) if len(ex['sentence']) > 2]
     sents = [list(examples[i]['sentence']) for i in keep]
     vl = bool(net.obj_feats)
     feats = torch.stack([torch.as_tensor(examples[i]['obj_feats']) for i in keep]) if vl and keep else None
@@ -380,10 +386,13 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
         cky_status = []
 
         def decode_into(out):
-            cky_status.append(ragged.decode_spans_ragged(d, lens, decode, out=out)[1])
+            if decode == 'hard':
+                cky_status.append(ragged.hard_spans_ragged(d, lens, out=out)[1])
+            else:
+                cky_status.append(ragged.decode_spans_ragged(d, lens, decode, out=out)[1])
 
         res = ground(atten, boxes, tg, decode_into, device=d._wss[0].device, lengths=lens,
-                     extra_status=[('cliora_chart_forward_ragged', d._ragged_status), (entry, lambda: cky_status[0])])
+                     extra_status=[(forward_entry, d._ragged_status), (entry, lambda: cky_status[0])])
         off = tg.phr_off
         for b, j in enumerate(idx):
             n = ns[b]

@@ -5,6 +5,9 @@ cell's splits replaced by a detached one-hot weight row, so ``torch.autograd`` t
 its selected split" -- what the library's unchanged backward computes on a hard workspace.  The splits of a cell are walked in the
 LIBRARY's order (the plan's pair tables, read on the host: no GPU needed), so a selection means the same split here and on the device.
 
+``hard_forward_ragged_torch`` is the yardstick of ``cliora_chart_forward_ragged_hard``: the same restatement on
+every sentence of a right-padded batch alone at its exact length, scattered into padded charts.
+
 Nothing here runs on the product path.
 """
 import functools
@@ -130,16 +133,73 @@ def level_offsets(L):
     return [level * L - level * (level - 1) // 2 for level in range(L)]
 
 
-def hard_spans_numpy(sel_in, L):
+def own_rows(L, n):
+    """The rows of a chart of length L that hold sentence n's own triangle, in the order of the cells of a chart of length n: row
+    level_offset_L[level] + pos for pos < n - level, level by level -- int64 (n (n + 1) / 2,).  Only a cell's row moves between the
+    exact-length and the padded chart; its selection does not."""
+    off = level_offsets(L)
+    return torch.tensor([off[level] + pos for level in range(n) for pos in range(n - level)], dtype=torch.int64)
+
+
+def hard_forward_ragged_torch(params, x_span_padded, lengths, share, normalize, selection=None, dtype=torch.float64):
+    """The yardstick of cliora_chart_forward_ragged_hard: ``hard_forward_torch`` on every sentence ALONE at its exact length (both
+    passes), scattered into padded charts -- NaN beyond each sentence's triangle, so nothing there can be read by accident.
+
+    x_span_padded (B, L, D), lengths: n_b in 1..L.  selection: None, or the PADDED (sel_in, sel_out) (B, C_L) arrays as the device
+    writes them: sentence b is then teacher-forced by its own triangle's entries, re-rowed to the chart of length n_b (own_rows).
+    Everything stays in the autograd graph of `params` and `x_span_padded`: a loss that reads own cells only (index them; a product
+    with 0 would keep the NaN) is the sum of the per-sentence losses, and its gradients are theirs summed.
+
+    -> dict: inside_h / outside_h (B, C_L, D), inside_s / outside_s (B, C_L); sel_in / sel_out (B, C_L) int64, -1 where a sentence
+    selects nothing (leaves, its outside root, beyond its triangle); margin_in / margin_out (B, C_L), inf there; margin_rel: per
+    sentence the smallest margin of both passes over max |inside_s| of that sentence (hard_cases.min_margin_rel's quantity);
+    relu_margin / relu_margin_all: the smallest over the sentences, over the selected pairs / over every pair."""
+    B, L, D = x_span_padded.shape
+    C = L * (L + 1) // 2
+    IH, OH = (torch.full((B, C, D), float('nan'), dtype=dtype) for _ in range(2))
+    IS, OS = (torch.full((B, C), float('nan'), dtype=dtype) for _ in range(2))
+    sel = [torch.full((B, C), -1, dtype=torch.int64) for _ in range(2)]
+    margin = [torch.full((B, C), float('inf'), dtype=dtype) for _ in range(2)]
+    margin_rel, relu, relu_all = [], float('inf'), float('inf')
+    for b, n in enumerate(int(v) for v in lengths):
+        rows = own_rows(L, n)
+        given = None
+        if selection is not None:
+            given = tuple(s.detach().cpu().long()[b:b + 1, rows].clone() for s in selection)
+            given[1][:, -1] = -1                                               # the sentence's own outside root selects nothing
+        o = hard_forward_torch(params, x_span_padded[b:b + 1, :n], share, normalize, outside=True, selection=given, dtype=dtype)
+        IH[b, rows], IS[b, rows], OH[b, rows], OS[b, rows] = o['inside_h'][0], o['inside_s'][0], o['outside_h'][0], o['outside_s'][0]
+        sel[0][b, rows], sel[1][b, rows] = o['sel_in'][0], o['sel_out'][0]
+        margin[0][b, rows], margin[1][b, rows] = o['margin_in'][0], o['margin_out'][0]
+        scale = max(1e-30, float(o['inside_s'].detach().abs().max()))
+        margin_rel.append(min(float(o['margin_in'].min()), float(o['margin_out'].min())) / scale)
+        relu, relu_all = min(relu, o['relu_margin']), min(relu_all, o['relu_margin_all'])
+    return dict(inside_h=IH, inside_s=IS, outside_h=OH, outside_s=OS, sel_in=sel[0], sel_out=sel[1], margin_in=margin[0],
+                margin_out=margin[1], margin_rel=margin_rel, relu_margin=relu, relu_margin_all=relu_all)
+
+
+def hard_spans_ragged_numpy(sel_in, lengths, L):
+    """``hard_spans_numpy`` for a right-padded chart of length L, as cliora_hard_spans_ragged emits it: sentence b is walked from its own
+    root (n_b - 1, 0) with the padded chart's level offsets -- n_b - 1 rows, the root last, (-1, -1) beyond; a length outside [1, L]
+    gets -1 in every row."""
+    return hard_spans_numpy(sel_in, L, lengths)
+
+
+def hard_spans_numpy(sel_in, L, lengths=None):
     """The tree of a hard chart from its inside selections, as cliora_hard_spans emits it: int32 (B, L-1, 2) of (start, end) word
     positions, children before parents, left subtree first, the root last.  sel_in: (B, C) integers, the split of every cell above
-    the leaves (cell (level, pos) with split k has the children (k, pos) and (level - k - 1, pos + k + 1))."""
+    the leaves (cell (level, pos) with split k has the children (k, pos) and (level - k - 1, pos + k + 1)).  lengths: see
+    hard_spans_ragged_numpy."""
     sel = np.asarray(sel_in.cpu() if torch.is_tensor(sel_in) else sel_in)
     B = sel.shape[0]
     off = level_offsets(L)
     out = np.zeros((B, max(L - 1, 0), 2), dtype=np.int32)
     for b in range(B):
-        cnt, stack = 0, [(L - 1, 0, 0)]                                       # (level, pos, phase): an explicit stack, as on the device
+        n = L if lengths is None else int(lengths[b])
+        out[b, max(n - 1, 0) if 1 <= n <= L else 0:] = -1
+        if not 1 <= n <= L:
+            continue
+        cnt, stack = 0, [(n - 1, 0, 0)]                                       # (level, pos, phase): an explicit stack, as on the device
         while stack:
             level, pos, phase = stack.pop()
             if level == 0:

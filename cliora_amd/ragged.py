@@ -25,6 +25,12 @@ sentence's own gradient), ``reconstruction_loss_ragged`` is the reconstruction l
 features of every sentence (``obj_feats=``): the ``_vl`` forms of the two entries, and the VG and contrastive losses over each
 sentence's own words and triangle (``harness.VGLoss`` / ``ContrastiveLoss`` with ``lengths``).
 
+A HARD (S-DIORA) net -- ``build_net(hard=True)``, or a trained net whose ``diora.hard`` is set -- runs the same entries (DESIGN.md
+section 29): ``forward_ragged``, ``forward_ragged_train`` and ``Trainer.step_ragged`` route its packs through
+``cliora_chart_forward_ragged_hard`` (the module's ``_ragged_hard`` / ``_ragged_hard_train`` slots; ``diora.selection`` then holds the
+pack's padded selection arrays, -1 wherever no cell of a sentence selects), ``parse_ragged_hard`` reads each sentence's tree off its
+own inside selections (``cliora_hard_spans_ragged``), and ``evaluate.evaluate_ragged(decode='hard')`` scores those trees.
+
     from cliora_amd.ragged import parse_ragged, encode_ragged, forward_ragged
     trees = parse_ragged(net, sentences)        # net: harness.Net; sentences: lists of token ids, any lengths 1..64
     trees = parse_ragged(net, sentences, max_len=128)            # ... 1..128: the inside pass alone needs no root-level mask
@@ -242,10 +248,13 @@ def _check_batch(net, sentences, obj_feats, max_len, kind):
 
 def _forward_packs(net, sentences, lengths, packs, pad_id, obj_feats, slot, max_len=MAX_L):
     """The one loop over the packs, a generator: per pack pad, embed, encode the pack's regions (obj_feats, else None) and run the
-    chart module's forward -- with (lengths on the device, root-level mask) in the module's slot `slot` ('_ragged', '_ragged_train')
-    around it, cleared whatever happens; slot None: the module's ordinary forward -- then yield (indices, lengths on the device)."""
+    chart module's forward -- with (lengths on the device, root-level mask) in the module's slot `slot` ('_ragged', '_ragged_train';
+    for a hard module '_ragged_hard', '_ragged_hard_train' in their place) around it, cleared whatever happens; slot None: the
+    module's ordinary forward -- then yield (indices, lengths on the device)."""
     diora = net.diora
     dev = next(net.parameters()).device
+    if slot is not None and getattr(diora, 'hard', False):      # a hard module's own slots: cliora_chart_forward_ragged_hard
+        slot = {'_ragged': '_ragged_hard', '_ragged_train': '_ragged_hard_train'}[slot]
     for idx in packs:
         tokens, lens = pad_batch([sentences[i] for i in idx], pad_id)
         x_span, x_word = net.embed(tokens.to(dev))
@@ -323,7 +332,8 @@ def forward_ragged_train(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WAS
     for idx, lens in _forward_packs(net, sentences, lengths, pack(lengths, max_batch, max_waste), pad_id, obj_feats, '_ragged_train'):
         bad = int(diora._ragged_status.item())
         if bad:
-            raise _lib.ChartLibError('cliora_chart_forward_ragged_train%s rejected %d sentence length(s)' % ('_vl' if vl else '', bad))
+            raise _lib.ChartLibError('cliora_chart_forward_ragged_%s rejected %d sentence length(s)'
+                                     % ('hard' if getattr(diora, 'hard', False) else 'train_vl' if vl else 'train', bad))
         yield idx, lens, diora
 
 
@@ -392,6 +402,35 @@ def parse_ragged(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_
             trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
 
     _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, obj_feats=obj_feats, max_len=max_len, max_long_batch=max_long_batch)
+    return trees
+
+
+def hard_spans_ragged(diora, lengths, out=None):
+    """cliora_hard_spans_ragged on a hard chart module after its forward over a right-padded batch: the tree each sentence's own
+    inside selections spell.  lengths: int32 tensor (B,).  -> (spans (B, L-1, 2) int32 with (-1, -1) beyond each sentence's n - 1 rows,
+    status (1,) int32 counting the lengths outside [1, L], which the caller must check).  Device tensors; nothing is synchronised."""
+    return diora.hard_spans_device(out=out, lengths=lengths)
+
+
+def parse_ragged_hard(net, sentences, max_batch=64, max_waste=DEFAULT_MAX_WASTE, pad_id=0, max_len=MAX_L_INSIDE, max_long_batch=None):
+    """The hard (S-DIORA) tree of every sentence -- the one its own inside selections spell, no CKY pass -- in the caller's order, as
+    ``parse_ragged`` returns trees.  net: a harness.Net whose chart module is hard (build_net(hard=True), or .hard set).  Packs like
+    ``parse_ragged`` and runs the inside pass alone through the module's ordinary hard forward on the padded batch (the inside pass
+    is prefix-closed, hard or soft: DESIGN.md section 29), then cliora_hard_spans_ragged; sentences of up to 128 words.  One
+    device-to-host copy per pack."""
+    diora = net.diora
+    if not getattr(diora, 'hard', False):
+        raise ValueError('parse_ragged_hard needs a hard chart module (DioraMLP(hard=True), build_net(hard=True)); parse_ragged decodes a soft one')
+    trees = [None] * len(sentences)
+
+    def decode_pack(idx, lens):
+        rows, status = host_copy(*hard_spans_ragged(diora, lens))                # the pack's one device-to-host copy
+        if status.any():
+            raise _lib.ChartLibError('cliora_hard_spans_ragged rejected %d sentence length(s)' % int(status.sum()))
+        for b, i in enumerate(idx):
+            trees[i] = diora.trees_from_spans(rows[b:b + 1, :len(sentences[i]) - 1])[0]
+
+    _run_packs(net, sentences, max_batch, max_waste, pad_id, decode_pack, max_len=max_len, max_long_batch=max_long_batch)
     return trees
 
 

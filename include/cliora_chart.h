@@ -196,6 +196,40 @@ int cliora_chart_forward_hard(cliora_plan* plan, const cliora_params* params, co
  * Nothing is written for L < 2. */
 int cliora_hard_spans(cliora_plan* plan, const int32_t* sel_in, int32_t* spans, void* stream);
 
+/* The hard chart of sentences of DIFFERENT lengths that share one right-padded chart of length L: what
+ * cliora_chart_forward_ragged (lengths, status: as there; root_levels: two words in host memory, as cliora_chart_forward_ragged_wide
+ * takes them) is to cliora_chart_forward, for cliora_chart_forward_hard.  ONE entry for inference and training:
+ *   with CLIORA_FWD_NO_BACKWARD   plans of L <= 128 (a long plan runs the long instances of the hard score / projection kernels)
+ *   without it                    plans of L <= 64; the state the backward reads is written, ReLU bits included, and the backward is
+ *                                 cliora_chart_backward_ragged on that workspace, unchanged
+ *   CLIORA_FWD_HARD_DENSE         as in cliora_chart_forward_hard: same outputs, bit for bit
+ * On every cell of sentence b's own triangle (pos + level < lengths[b]) the four charts hold what cliora_chart_forward_hard computes for
+ * that sentence alone at its exact length, to rounding, and the selections are that chart's with its numbering: the valid outside
+ * pairs of a cell are its first lengths[b] - level - 1, so an index means the same pair at either length and the lowest-maximum tie
+ * rule carries over.  Cells beyond a triangle are unspecified in the four charts (inside_s holds -1e30 there).  EVERY entry of the two
+ * selection arrays is written: the split on the cells of a triangle above the leaves (sel_in) / other than the sentence's root
+ * (lengths[b] - 1, 0) (sel_out), -1 everywhere else -- leaves, outside roots, beyond the triangles, all of sel_out without an outside
+ * pass.  Schedule: hard inside levels, mask, root, hard outside levels with the seed fix-up and a re-scoring of the level below after
+ * each level that holds some sentence's root, then the -1 fill; all on the caller's stream.  With every length equal to L the charts
+ * and the selections are bitwise those of cliora_chart_forward_hard.
+ * Refused with CLIORA_EINVAL and a message that starts with the entry's name, each before any HIP call: a NULL plan, params, lengths,
+ * root_levels or status; NULL selection arrays; TreeLSTM plans; plans with regions (R > 0); params->root_mat (compress);
+ * CLIORA_FWD_PAIR_STATES; unknown flag bits; a long plan without CLIORA_FWD_NO_BACKWARD; a bit of root_levels set at or above L (bit
+ * L - 1 is legal and ignored).  There is no drop_mask argument (text-only DIORA has no attention dropout).  status counts the lengths
+ * outside [1, L]; the cells and selections of such a sentence are unspecified (nothing is read or written out of bounds). */
+int cliora_chart_forward_ragged_hard(cliora_plan* plan, const cliora_params* params, const float* x_span,
+                                     float* inside_h, float* inside_s, float* outside_h, float* outside_s,
+                                     int32_t* sel_in, int32_t* sel_out,
+                                     void* fwd_workspace, size_t fwd_workspace_bytes, int flags,
+                                     const int32_t* lengths, const uint64_t* root_levels, int32_t* status, void* stream);
+/* cliora_hard_spans with a length per sentence: sentence b is walked from its own root (lengths[b] - 1, 0) with the padded chart's cell
+ * ids -- lengths[b] - 1 rows in cliora_cky_spans_ragged's layout (the root last), (-1, -1) beyond.  sel_in: of
+ * cliora_chart_forward_ragged_hard, or of cliora_chart_forward_hard on the padded batch (the inside pass is prefix-closed).  status (an
+ * int32 on the device, zeroed by the call) counts the lengths outside [1, L]; such a sentence gets -1 in every row.  With every length
+ * equal to L the spans are bitwise those of cliora_hard_spans (the same kernel, given lengths). */
+int cliora_hard_spans_ragged(cliora_plan* plan, const int32_t* sel_in, const int32_t* lengths, int32_t* spans, int32_t* status,
+                             void* stream);
+
 /* DioraTreeLSTM (BASELINE config 5).  PARITY UNPINNED: the reference ships this composition only
  * as commented-out text (cliora/net/vg.py:28-76); what is implemented is that text on the
  * DioraBase skeleton (cliora/net/diora.py:283-398), constant = 1 inside / 0 outside (diora.py:174),
