@@ -3,8 +3,8 @@
 // each sentence's own triangle of a right-padded chart.  See include/cliora_chart.h for the contract, decode_kernels.hpp for the CKY
 // kernel, kbest_kernels.hpp for the k-best lists, posterior_kernels.hpp for the sum-product model, sample_kernels.hpp for the draws
 // from it, constrained_kernels.hpp for the bracket mask over both, constrained_tree_kernels.hpp for the k-best lists and the draws
-// under that mask, bracket_grad_kernels.hpp for the gradient of its log-probability
-// and expectation_kernels.hpp for the expected cost, the entropy and their gradient.
+// under that mask, bracket_grad_kernels.hpp for the gradient of its log-probability,
+// expectation_kernels.hpp for the expected cost, the entropy and their gradient, and margin_kernels.hpp for the max-margin losses.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
 #include <cmath>
 
@@ -15,6 +15,7 @@
 #include "decode_kernels.hpp"
 #include "expectation_kernels.hpp"
 #include "kbest_kernels.hpp"
+#include "margin_kernels.hpp"
 #include "posterior_kernels.hpp"
 #include "sample_kernels.hpp"
 
@@ -257,5 +258,25 @@ extern "C" int cliora_tree_expectation(cliora_plan* plan, void* fwd_ws, const in
                          [&](auto, auto&& go) {
                              return go("tree_expectation_kernel", tree_expectation_kernel, cost, w_cost, w_entropy, d_split, risk_out,
                                        entropy_out, log_z_out);
+                         });
+}
+
+// The two value tables, the two split tables and the mask fit the CU's LDS up to L = 64 (margin_kernels.hpp: 41 KiB there at M 256):
+// no scratch, no query.  A long plan has no backward to hand the gradient to, so there is no LONG instance.
+extern "C" int cliora_bracket_margin(cliora_plan* plan, void* fwd_ws, const int32_t* lengths, const int32_t* brackets, int M, float margin,
+                                     float penalty, const float* weights, float* d_split, float* loss_out, float* aug_score_out,
+                                     float* ref_score_out, int32_t* violations_out, int32_t* feasible_out, int32_t* spans_aug,
+                                     int32_t* spans_ref, int32_t* status, void* stream) {
+    if (M < 0 || M > CON_MAX_M) return fail(CLIORA_EINVAL, "cliora_bracket_margin: M outside 0..256");
+    if (!(margin >= 0.f) || !std::isfinite(margin)) return fail(CLIORA_EINVAL, "cliora_bracket_margin: margin negative or not finite");
+    if (!(penalty >= 0.f)) return fail(CLIORA_EINVAL, "cliora_bracket_margin: penalty negative or NaN");
+    if (!plan || !fwd_ws || !d_split || !loss_out || !aug_score_out || !ref_score_out || !violations_out || !feasible_out || !status)
+        return fail(CLIORA_EINVAL, "cliora_bracket_margin: NULL argument");
+    if (!brackets && M > 0) return fail(CLIORA_EINVAL, "cliora_bracket_margin: NULL brackets");
+    if (plan->p.is_long()) return fail(CLIORA_EINVAL, "cliora_bracket_margin: L > 64 is forward only (the backward stops at 64 words, so nothing could take the gradient)");
+    return launch_decode(plan, fwd_ws, "cliora_bracket_margin", POST_WAVES, [M](int L, int C) { return MarginLds{L, C, M}; }, lengths, nullptr,
+                         nullptr, status, stream, [&](auto, auto&& go) {
+                             return go("bracket_margin_kernel", bracket_margin_kernel, brackets, M, margin, penalty, weights, d_split, loss_out,
+                                       aug_score_out, ref_score_out, violations_out, feasible_out, spans_aug, spans_ref);
                          });
 }

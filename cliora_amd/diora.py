@@ -821,6 +821,21 @@ class DioraBase(nn.Module):
                     raise ValueError('bracket (%d, %d) is not 0 <= start <= end < %d' % (s, e, L))
         return structured.bracket_nll(self, constrained.pack_brackets(required, forbidden), reduction=reduction)
 
+    def bracket_hinge(self, required, forbidden=None, margin=1.0, penalty=float('inf'), reduction='mean'):
+        """The max-margin loss of the brackets, in the autograd graph of the last forward (cliora_amd.structured.bracket_hinge;
+        DESIGN.md section 30): the score of the best cost-augmented tree minus that of the best tree that respects the brackets.
+        required / forbidden as bracket_nll takes them.  margin > 0, penalty inf: structured hinge; margin 0: perceptron; a finite
+        penalty: ramp, which takes crossing brackets too.  A span outside its sentence raises here, on the host; nothing is
+        synchronised."""
+        from . import constrained, structured
+        L = self._plan.L
+        for lst in list(required) + list(forbidden or ()):
+            for s, e in lst:
+                if not 0 <= int(s) <= int(e) < L:
+                    raise ValueError('bracket (%d, %d) is not 0 <= start <= end < %d' % (s, e, L))
+        return structured.bracket_hinge(self, constrained.pack_brackets(required, forbidden), margin=margin, penalty=penalty,
+                                        reduction=reduction)
+
     def tree_objective(self, cost=None):
         """(risk, entropy) of the distribution over parses of the last forward, two (B,) tensors in its autograd graph
         (cliora_amd.structured.tree_objective): the expected value of the per-cell cost -- fp32 (B, C) in the cell

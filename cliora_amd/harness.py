@@ -306,7 +306,7 @@ class LossDict(dict):
 
 class Net(nn.Module):
     def __init__(self, embed, image_encoder, diora, obj_feats, loss_funcs=(), bracket_loss_weight=0.0, risk_loss_weight=0.0,
-                 entropy_loss_weight=0.0):
+                 entropy_loss_weight=0.0, hinge_loss_weight=0.0, hinge_margin=1.0, hinge_penalty=float('inf')):
         super().__init__()
         self.obj_feats = obj_feats
         # > 0: a batch that carries entity_labels adds weight * bracket_nll of its annotated phrases (cliora_amd.structured) to the total
@@ -314,6 +314,9 @@ class Net(nn.Module):
         # > 0: such a batch adds weight * the mean expected cost under span_costs of ALL its phrases, crossing ones included (minus the
         # expected number of them recovered); != 0, either sign: a training step adds weight * the mean entropy of the parse distribution
         self.risk_loss_weight, self.entropy_loss_weight = float(risk_loss_weight), float(entropy_loss_weight)
+        # > 0: such a batch adds weight * bracket_hinge of its phrases: the structured hinge (perceptron at margin
+        # 0) with an infinite penalty, over the laminar subset of the phrases; the ramp loss with a finite one, crossing phrases kept
+        self.hinge_loss_weight, self.hinge_margin, self.hinge_penalty = float(hinge_loss_weight), float(hinge_margin), float(hinge_penalty)
         self.overlap_word_branch = True      # vision-language training steps: the word branch on the library's caller lane (forward())
         if obj_feats:
             self.img_encoder = image_encoder
@@ -381,11 +384,15 @@ class Net(nn.Module):
 
     def structured_losses(self, entity_labels, L, device):
         """The weighted structured terms of the chart self.diora holds (cliora_amd.structured), as (name, 0-d tensor) in the order they
-        join the total: bracket_nll and risk for a batch that carries entity_labels, entropy for a training step.  L: the chart's length."""
+        join the total: bracket_nll, hinge and risk for a batch that carries entity_labels, entropy for a training step.  L: the chart's length."""
         out = []
         if entity_labels is not None and self.bracket_loss_weight > 0:
             from .constrained import brackets_from_entity_labels
             out.append(('bracket_nll', self.bracket_loss_weight * self.diora.bracket_nll(brackets_from_entity_labels(entity_labels))))
+        if entity_labels is not None and self.hinge_loss_weight > 0:
+            from .constrained import brackets_from_entity_labels
+            req = brackets_from_entity_labels(entity_labels, drop_crossing=self.hinge_penalty == float('inf'))
+            out.append(('hinge', self.hinge_loss_weight * self.diora.bracket_hinge(req, margin=self.hinge_margin, penalty=self.hinge_penalty)))
         use_risk = entity_labels is not None and self.risk_loss_weight > 0
         use_entropy = self.entropy_loss_weight != 0 and self.training and torch.is_grad_enabled()
         if use_risk or use_entropy:                             # one node for both: one kernel launch each way
@@ -419,7 +426,8 @@ def select_diora(arch, obj_feats):
 
 def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=True, normalize='unit',
               vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp', bracket_loss_weight=0.0,
-              risk_loss_weight=0.0, entropy_loss_weight=0.0, full_softmax=False, hard=False):
+              risk_loss_weight=0.0, entropy_loss_weight=0.0, full_softmax=False, hard=False, hinge_loss_weight=0.0, hinge_margin=1.0,
+              hinge_penalty=float('inf')):
     """What trainer.py:504-582 assembles, on the native chart modules.  full_softmax: the reconstruction loss is the exact one over the
     whole table (ReconstructionSoftmaxLoss(full_vocab=True)) instead of the reference's sampled loss.  hard: the chart module encodes
     every cell's single best split (S-DIORA, `--arch hard` of the reference's training script; text-only DioraMLP)."""
@@ -436,7 +444,8 @@ def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=
     if obj_feats:
         embeddings.weight.requires_grad = False              # trainer.py:541
     return Net(embed, enc, diora, obj_feats, losses, bracket_loss_weight=bracket_loss_weight, risk_loss_weight=risk_loss_weight,
-               entropy_loss_weight=entropy_loss_weight)
+               entropy_loss_weight=entropy_loss_weight, hinge_loss_weight=hinge_loss_weight, hinge_margin=hinge_margin,
+               hinge_penalty=hinge_penalty)
 
 
 class Trainer(object):
@@ -463,7 +472,8 @@ class Trainer(object):
         if neg_samples is None and self.negative_sampler is not None:       # drawn on the current stream, ahead of the forward
             neg_samples = self.negative_sampler.sample(self.k_neg)
         with torch.set_grad_enabled(train):
-            if ((getattr(self.net, 'bracket_loss_weight', 0.0) > 0 or getattr(self.net, 'risk_loss_weight', 0.0) > 0) and train and compute_loss
+            if ((getattr(self.net, 'bracket_loss_weight', 0.0) > 0 or getattr(self.net, 'risk_loss_weight', 0.0) > 0
+                 or getattr(self.net, 'hinge_loss_weight', 0.0) > 0) and train and compute_loss
                     and batch_map.get('entity_labels') is not None):
                 out = self.net(batch_map['sentences'], batch_map.get('obj_feats'), neg_samples, compute_loss,
                                entity_labels=batch_map['entity_labels'])

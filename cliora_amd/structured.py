@@ -29,6 +29,9 @@ L > 64 (the backward stops at 64 words), a TreeLSTM module (its backward takes n
 
 The second half of the module reads the same distribution as an expectation (cliora_tree_expectation): the
 expected value of a per-cell cost and the entropy of the distribution over trees, ``tree_objective``, with the same hand-off.
+
+The third part is the max-margin family over the same potentials (cliora_bracket_margin): structured hinge,
+perceptron and ramp losses, ``bracket_hinge``, whose subgradient -- a difference of two trees -- takes the same hand-off.
 """
 import collections
 import ctypes as C
@@ -426,3 +429,238 @@ def tree_expectation_numpy(pair_s, lengths, cost, w_cost=None, w_entropy=None):
             G[level][b, :n - level] = d
         entropy[b] = log_z[b] - mean_r
     return G, risk, entropy, log_z
+
+
+# ---- max-margin losses: structured hinge, perceptron and ramp (cliora_bracket_margin) -------------------------
+# The third way to train on brackets: the score of the best cost-augmented tree minus the score of the best tree that respects the
+# brackets.  dis[cell] = 1 on a cell of levels 1 .. n - 2 that the brackets disallow, F(t) the sum of r over a tree's internal cells,
+# D(t) the sum of dis over them:
+#
+#     A = max_t F(t) + margin D(t),   Bv = max_t F(t) - penalty D(t),   loss = A - Bv >= 0
+#
+# margin > 0 and penalty inf: the structured hinge with margin rescaling; margin 0: the perceptron loss; a finite penalty: the ramp
+# loss, which stays defined on a bracket set that no tree satisfies.  The subgradient is a difference of two trees -- sparse, made of
+# integers -- and reaches the chart through the bracket loss's slot, into which it ADDS; a hard chart, whose score
+# matrix gets an exactly zero gradient from the reconstruction loss, is moved by it.
+#
+#     loss = recon + 0.5 * net.diora.bracket_hinge(req)                   # or bracket_hinge(net.diora, pack_brackets(req))
+#
+# d_split as BracketGrad's; loss, aug_score, ref_score (B,) fp32; violations, feasible (B,) int32; spans_aug, spans_ref (B, L-1, 2)
+# int32 or None; status (number of workspaces,) int32.  Device tensors; nothing is synchronised.  (bracket_margin_numpy: the same fields
+# as numpy arrays, d_split {level: (B, L - level, level)} and the scalars in fp64, status an int.)
+BracketMargin = collections.namedtuple('BracketMargin', 'd_split loss aug_score ref_score violations feasible spans_aug spans_ref status')
+
+
+def _check_margin(margin, penalty):
+    margin, penalty = float(margin), float(penalty)
+    if not (margin >= 0 and np.isfinite(margin)):
+        raise ValueError('margin must be finite and >= 0')
+    if not penalty >= 0:
+        raise ValueError('penalty must be >= 0 (inf: the reference tree keeps every bracket)')
+    return margin, penalty
+
+
+def bracket_margin(diora, brackets, margin=1.0, penalty=float('inf'), weights=None, lengths=None, spans=False):
+    """cliora_bracket_margin on a chart module after its forward (any forward: this call needs no backward state).  brackets, weights,
+    lengths: as ``bracket_grad`` takes them; spans: also give the two trees.  One d_split buffer per workspace of
+    ``workspace_slices``, back to back.  -> BracketMargin of device tensors; nothing is synchronised."""
+    if diora._plan is None:
+        raise _lib.ChartLibError('bracket_margin: the module has run no forward')
+    margin, penalty = _check_margin(margin, penalty)
+    plan, parts = diora._plan, workspace_slices(diora)
+    nws, B = len(parts), plan.B
+    dev = parts[0][0].device
+    M = _check_brackets(brackets, B * nws)
+    if lengths is None:
+        lengths = getattr(diora._wss, 'lengths', None)         # a padded training chart of mixed lengths: each sentence's own triangle
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
+        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
+    if weights is not None and weights.numel() != B * nws:
+        raise ValueError('weights must hold one value per sentence of the chart (%d)' % (B * nws))
+    with torch.cuda.device(dev):
+        count = split_score_count(plan)
+        lengths = lengths.to(dev).contiguous() if lengths is not None else None
+        brackets = brackets.to(dev).contiguous() if brackets is not None else None
+        weights = weights.to(dev).contiguous().float().reshape(-1) if weights is not None else None
+        buf = torch.empty(max(count * nws, 1), dtype=torch.float32, device=dev)      # (one word: no row, but the library wants an address)
+        loss, aug, ref = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(3))
+        viol, feasible = (torch.empty(B * nws, dtype=torch.int32, device=dev) for _ in range(2))
+        sp_a, sp_r = (torch.empty((B * nws, plan.L - 1, 2), dtype=torch.int32, device=dev) for _ in range(2)) if spans else (None, None)
+        status = torch.zeros(nws, dtype=torch.int32, device=dev)
+        sub = lambda t, sl: _p(t[sl]) if t is not None else None
+        for i, (ws, sl) in enumerate(parts):
+            _lib.call('cliora_bracket_margin', plan.handle, C.c_void_p(ws.data_ptr()), sub(lengths, sl), _p(brackets[sl]) if M else None, M,
+                      margin, penalty, sub(weights, sl), C.c_void_p(buf.data_ptr() + 4 * i * count), _p(loss[sl]), _p(aug[sl]), _p(ref[sl]),
+                      _p(viol[sl]), _p(feasible[sl]), sub(sp_a, sl), sub(sp_r, sl), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    return BracketMargin(buf[:count * nws], loss, aug, ref, viol, feasible, sp_a, sp_r, status)
+
+
+class _BracketMarginLoss(torch.autograd.Function):
+    """(loss, feasible) of the brackets as functions of the chart (formally: of its inside_s, as _BracketLogProb)."""
+
+    @staticmethod
+    def forward(ctx, inside_s, diora, brackets, margin, penalty):
+        res = bracket_margin(diora, brackets, margin, penalty)
+        ctx.chart = _ChartView(diora._plan, diora._wss)            # the plan and the forward's holder (workspace + slot)
+        ctx.brackets, ctx.shape, ctx.scalars = brackets, inside_s.shape, (margin, penalty)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(res.feasible)
+        return res.loss, res.feasible
+
+    @staticmethod
+    def backward(ctx, g, _):
+        if g is None:
+            return None, None, None, None, None
+        holder = ctx.chart._wss
+        d = bracket_margin(ctx.chart, ctx.brackets, ctx.scalars[0], ctx.scalars[1], weights=g).d_split
+        slot = holder.split_cot
+        slot[0] = d if slot[0] is None else slot[0] + d
+        return torch.zeros(ctx.shape, dtype=torch.float32, device=d.device), None, None, None, None
+
+
+def _margin_node(diora, brackets, margin, penalty, who):
+    plan = diora._plan
+    if plan is None:
+        raise _lib.ChartLibError('%s: the module has run no forward' % who)
+    margin, penalty = _check_margin(margin, penalty)
+    if plan.L > _lib.MAX_L:
+        raise _lib.ChartLibError('%s: L = %d > %d is inference only (the backward stops at %d words), so the loss has nothing to train '
+                                 'through' % (who, plan.L, _lib.MAX_L, _lib.MAX_L))
+    if getattr(diora, 'plan_arch', 0) != 0:
+        raise _lib.ChartLibError('%s: a TreeLSTM chart takes no cotangent on its split scores (cliora_lstm_backward has no such input)' % who)
+    holder = diora._wss
+    if len(holder) != 1 or getattr(holder, 'split_cot', None) is None:
+        raise _lib.ChartLibError('%s: the module holds %d workspaces that no single chart node owns; call it after each forward of its '
+                                 'own' % (who, len(holder)))
+    inside_s = diora.chart.inside_s
+    if not inside_s.requires_grad:
+        raise _lib.ChartLibError('%s: the forward kept no backward state (it ran under torch.no_grad(), in eval mode without gradients, '
+                                 'or on a padded chart); bracket_margin gives the value alone' % who)
+    return _BracketMarginLoss.apply(inside_s, diora, brackets, margin, penalty)
+
+
+def bracket_margin_loss(diora, brackets, margin=1.0, penalty=float('inf')):
+    """loss (B,) fp32 of the brackets (int32 (B, M, 3), ``constrained.pack_brackets``; None: no bracket) under the last forward of
+    `diora`, in its autograd graph: A - Bv of the module comment above; 0, with a zero gradient, for a sentence no tree qualifies for
+    under an infinite penalty (or with a bad row).  The mechanism and the refusals are ``bracket_log_prob``'s."""
+    return _margin_node(diora, brackets, margin, penalty, 'bracket_margin_loss')[0]
+
+
+def bracket_hinge(diora, brackets, margin=1.0, penalty=float('inf'), reduction='mean'):
+    """The max-margin loss over the feasible sentences -- under an infinite penalty those some tree qualifies for, under a finite one
+    those without a bad row: their mean ('mean') or sum ('sum'), a 0-d tensor in the graph; 0 (with a graph) when there is none.
+    Nothing is synchronised."""
+    if reduction not in ('mean', 'sum'):
+        raise ValueError("reduction must be 'mean' or 'sum'")
+    loss, feasible = _margin_node(diora, brackets, margin, penalty, 'bracket_hinge')
+    total = loss.sum()                                     # an infeasible or rejected sentence holds 0
+    return total / feasible.sum().clamp(min=1).to(loss.dtype) if reduction == 'mean' else total
+
+
+def bracket_violations(diora, brackets, lengths=None):
+    """Per sentence, the number of constituents of the best (CKY) tree that cross a required bracket or equal a forbidden one -- against
+    a full gold tree, its spans that are not in the gold tree: the margin = 0 call's violations.  -> (B,) int32 numpy array; one
+    device-to-host copy; a rejected sentence raises."""
+    from .constrained import refuse_rejected
+    from .diora import host_copy
+    res = bracket_margin(diora, brackets, margin=0.0, penalty=0.0, lengths=lengths)
+    viol, status = host_copy(res.violations, res.status)
+    refuse_rejected(int(status.sum()), 'cliora_bracket_margin')
+    return viol
+
+
+def _best_tree(n, rel, leaf, bonus):
+    """The fp32 recurrence of the kernel over one sentence: val[leaf] = leaf, candidate (val_l + val_r) + rel in fp32, first maximum
+    wins, then val[cell] = best + bonus[level][pos] (fp32; 0 where the cell has none).  -> (root value, [(start, end, split)] in the
+    walk's order)."""
+    val, bp = np.zeros((n, n), dtype=np.float32), {}
+    val[0, :n] = leaf
+    for level in range(1, n):
+        k, pos = np.arange(level)[None, :], np.arange(n - level)[:, None]
+        cand = (val[k, pos] + val[level - k - 1, pos + k + 1]) + rel[level]        # (cells of the level, splits), fp32
+        bp[level] = np.argmax(cand, axis=1)
+        val[level, :n - level] = cand[np.arange(n - level), bp[level]] + bonus[level]
+    rows, stack = [], [(n - 1, 0, 0)] if n > 1 else []
+    while stack:                                      # the kernel's walk: left subtree, right subtree, then the node
+        level, pos, phase = stack.pop()
+        if level == 0:
+            continue
+        k = int(bp[level][pos])
+        if phase == 0:
+            stack += [(level, pos, 1), (k, pos, 0)]
+        elif phase == 1:
+            stack += [(level, pos, 2), (level - k - 1, pos + k + 1, 0)]
+        else:
+            rows.append((pos, pos + level, k))
+    return val[n - 1, 0], rows
+
+
+def bracket_margin_numpy(pair_s, lengths, brackets, margin, penalty, weights=None):
+    """cliora_bracket_margin restated (tests): `pair_s[level]` (B, L - level, level[, 1]) the per-split inside scores of the (padded)
+    chart, sentence b its first lengths[b] words; brackets (B, M, 3) or None; weights (B,) or None.  The two trees in float32 in the
+    kernel's operation order, as ``constrained_numpy`` does its best tree; scores, loss and gradient in fp64 from those trees.
+    -> BracketMargin of numpy arrays as the kernel writes them."""
+    margin, penalty = _check_margin(margin, penalty)
+    m32, p32, hard = np.float32(margin), np.float32(penalty), penalty == float('inf')
+    lengths = [int(x) for x in lengths]
+    Bn = len(lengths)
+    levels = sorted(int(lv) for lv in pair_s)
+    L = (max(levels) + 1) if levels else 1
+    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
+    weights = np.ones(Bn) if weights is None else np.asarray(weights, dtype=np.float32).astype(np.float64)
+    G = {level: np.zeros((Bn, L - level, level)) for level in range(1, L)}
+    loss, aug, ref = np.zeros(Bn), np.zeros(Bn), np.zeros(Bn)
+    viol, feasible, status = np.zeros(Bn, dtype=np.int32), np.zeros(Bn, dtype=np.int32), 0
+    sp_a, sp_r = (np.full((Bn, max(L - 1, 0), 2), -1, dtype=np.int32) for _ in range(2))
+    ninf32 = np.float32(-np.inf)
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= L or any(bad_row(row, n) for row in brackets[b]):
+            status += 1
+            continue
+        allowed, _ = allowed_cells(n, brackets[b])
+        dis = ~allowed
+        dis[0, :] = False
+        dis[max(n - 1, 0):, :] = False                # leaves and the root are in every tree: no cost
+        s, rel, r = {}, {}, {}
+        for level in range(1, n):
+            s[level] = np.asarray(pair_s[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
+            s32 = np.asarray(pair_s[level][b], dtype=np.float32).reshape(-1, level)[:n - level]
+            rel[level] = s32 - s32.max(axis=1, keepdims=True)
+            r[level] = s[level] - s[level].max(axis=1, keepdims=True)
+        ones = np.ones(n, dtype=np.float32)
+        zero = np.float32(0.0)
+        bonus_a = {level: np.where(dis[level, :n - level], m32, zero) for level in range(1, n)}
+        if hard:
+            leaf_b = np.where(allowed[0, :n], np.float32(1.0), ninf32)
+            bonus_b = {level: np.where(allowed[level, :n - level], zero, ninf32) for level in range(1, n)}
+        else:
+            leaf_b = ones
+            bonus_b = {level: np.where(dis[level, :n - level], -p32, zero) for level in range(1, n)}
+        with np.errstate(invalid='ignore'):
+            _, tree_a = _best_tree(n, rel, ones, bonus_a)
+            root_b, tree_b = _best_tree(n, rel, leaf_b, bonus_b)
+        score = lambda tree: sum(r[e - st][st, k] for st, e, k in tree)
+        count = lambda tree: sum(int(dis[e - st, st]) for st, e, _ in tree)
+        viol[b] = count(tree_a)
+        aug[b] = score(tree_a) + float(m32) * viol[b]
+        sp_a[b, :len(tree_a)] = np.asarray([t[:2] for t in tree_a], dtype=np.int32).reshape(-1, 2)
+        if not root_b > ninf32:                       # no qualifying tree
+            ref[b] = -np.inf
+            continue
+        feasible[b] = 1
+        sp_r[b, :len(tree_b)] = np.asarray([t[:2] for t in tree_b], dtype=np.int32).reshape(-1, 2)
+        ref[b] = score(tree_b) - (float(p32) * count(tree_b) if count(tree_b) else 0.0)
+        diff = aug[b] - ref[b]
+        if diff < 0:                                  # the two fp32 maxima within rounding of each other
+            continue
+        loss[b] = diff
+        for tree, sign in ((tree_a, 1.0), (tree_b, -1.0)):
+            for st, e, k in tree:
+                level = e - st
+                kstar = int(np.argmax(s[level][st]))
+                G[level][b, st, k] += sign
+                G[level][b, st, kstar] -= sign
+        for level in range(1, n):
+            G[level][b] *= weights[b]
+            G[level][b][G[level][b] == 0] = 0.0       # +0 whatever the weight
+    return BracketMargin(G, loss, aug, ref, viol, feasible, sp_a, sp_r, status)

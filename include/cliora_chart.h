@@ -619,6 +619,45 @@ int cliora_bracket_grad(cliora_plan* plan, void* fwd_workspace, const int32_t* l
 int cliora_tree_expectation(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const float* cost, const float* w_cost,
                             const float* w_entropy, float* d_split, float* risk_out, float* entropy_out, float* log_z_out,
                             int32_t* status, void* stream);
+/* Max-margin bracket losses over the same potentials: structured hinge, perceptron and ramp.  With dis[cell] = 1
+ * on a cell of levels 1 .. n - 2 that the brackets disallow (it crosses a required bracket or equals a forbidden one; leaves and the
+ * root are in every tree and carry no cost), F(t) the sum of r over the n - 1 internal cells of a tree t and D(t) the sum of dis:
+ *   A    = max_t F(t) + margin * D(t)       its argmax: the cost-augmented tree
+ *   Bv   = max_t F(t) - penalty * D(t)      its argmax: the reference tree
+ *   loss = A - Bv >= 0
+ *   d_split[cell, k] = w[b] * (c[cell, k] - [k == k*] * sum_k c[cell, .]),  c = [(cell, k) in the augmented tree] - [.. in the reference tree]
+ * k* is the first maximum of the cell's scores, as cliora_bracket_grad has it: every row sums to zero.  margin >= 0 (finite); penalty in
+ * [0, +inf].  penalty = +inf: the second maximum runs over the qualifying trees of cliora_constrained_parse -- a disallowed cell holds
+ * -inf, a forbidden leaf or root makes the sentence infeasible -- and the reference tree and feasible are that entry's, bit for bit.
+ * margin > 0, penalty = +inf: structured hinge with margin rescaling; margin = 0, penalty = +inf: perceptron; a finite penalty: ramp,
+ * defined for a bracket set that no tree satisfies too.
+ * Both maxima are cliora_cky_spans' recurrence in fp32 (val[leaf] = 1, candidate (val_l + val_r) + (s_k - smax), first maximum wins)
+ * in one level loop, with val[cell] = best + bonus[cell] after the cell's own argmax: + margin * dis in the first pass, - penalty * dis
+ * (or -inf on a disallowed cell) in the second.  With margin = 0 the augmented tree is cliora_cky_spans' (cliora_cky_spans_ragged's).
+ *   d_split: cliora_plan_split_score_count floats in the layout cliora_bracket_grad writes.  EVERY element is written, once (no memset
+ *     is needed); cells beyond a sentence's triangle get zeros.  The integer in the bracket lies in -2 .. 2 and meets w[b] once:
+ *     d_split is exact in fp32 given the two trees; a zero is +0 whatever the weight.
+ *   weights (B) fp32 device, or NULL = 1: in a backward, the cotangent of the loss.
+ *   loss_out, aug_score_out, ref_score_out (B) fp32: A - Bv, A and Bv formed in fp64 from the terms of the two emitted trees (r in fp64
+ *     from the fp32 scores, plus the bonuses), rounded once.  A difference below 0 -- the two fp32 maxima within rounding of each
+ *     other -- is stored as +0 with a zero gradient.  Equal trees give a loss of exactly +0 under an infinite penalty.
+ *   violations_out (B) int32: D of the augmented tree; with margin = 0, the bracket violations of the best tree.  feasible_out (B) int32.
+ *   spans_aug, spans_ref (B, L-1, 2) int32, either NULL: the two trees in cliora_cky_spans' layout, (-1, -1) beyond.
+ *   brackets, M, lengths, status: as cliora_bracket_grad takes them.  With every length equal to L the outputs are bitwise those of the
+ *     lengths == NULL call.
+ *   A bad length or a bad row: zero gradient, loss 0, both scores 0, violations 0, feasible 0, rows -1, one count in *status; the weight
+ *     is not read.  penalty = +inf and no qualifying tree: zero gradient, loss 0, ref_score -inf, feasible 0, spans_ref rows -1 (the
+ *     augmented tree, its score and its violations are still given; nothing is counted); the weight is not read.  No disallowed cell:
+ *     both trees are cliora_cky_spans', loss +0, zero gradient, one pass.
+ * One workgroup per sentence, a wavefront per cell, each element written by one lane, no floating-point atomics: two calls give equal
+ * bits.  The tables fit the LDS (17 C + 52 L + 12 M + 248 bytes: 41 KiB at L 64 and M 256): no scratch.  TreeLSTM plans are taken (the
+ * entry only reads the split scores).  Refused with CLIORA_EINVAL and a message that starts with the entry's name, before any launch: a
+ * long plan (L > 64: the backward stops at 64 words); M outside 0 .. 256; margin negative, NaN or infinite; penalty negative or NaN; a
+ * NULL plan, workspace, d_split, scalar output, feasible_out or status; NULL brackets with M > 0; a plan that has not run a forward. */
+int cliora_bracket_margin(cliora_plan* plan, void* fwd_workspace, const int32_t* lengths, const int32_t* brackets, int M, float margin,
+                          float penalty, const float* weights, float* d_split, float* loss_out, float* aug_score_out,
+                          float* ref_score_out, int32_t* violations_out, int32_t* feasible_out, int32_t* spans_aug, int32_t* spans_ref,
+                          int32_t* status, void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
