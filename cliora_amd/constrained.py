@@ -23,15 +23,13 @@ section 25): its K best trees and draws from it, with their restatements ``const
     ts = constrained_samples(net.diora, pack_brackets(req), 64, seed=7) # every draw keeps the brackets; log_prob given them
 """
 import collections
-import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib, kbest as _kbest, sample as _sample
-from ._lib import ptr_or_null as _p, stream as _stream
-from .diora import span_buffer, workspace_slices
 from .posterior import cell_id, cell_uses, inside_numpy
+from .query import ChartQuery, host_copy, per_sentence, sentences_of, walk, walk_spans
 
 MAX_M = 256              # csrc/constrained_kernels.hpp CON_MAX_M: bracket rows per sentence
 REQUIRED, FORBIDDEN = 1, 0
@@ -98,42 +96,25 @@ def constrained_parse(diora, brackets, lengths=None, marginals=False, out=None):
     (``pack_brackets``), or None for no bracket at all.  lengths: None (every sentence has L words) or an int32 tensor (B,) for a
     right-padded batch.  marginals: also run the outside pass.  out: a contiguous int32 tensor (B, L-1, 2) on the chart's device to
     decode the spans into.  -> ConstrainedParse."""
-    plan = diora._plan
-    B, L, Cc = plan.B, plan.L, plan.C
-    spans, parts = span_buffer(diora, out)
-    nws = len(parts)
-    dev = spans.device
-    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
-        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
-    M = 0
-    if brackets is not None:
-        if brackets.dtype != torch.int32 or brackets.dim() != 3 or brackets.shape[0] != B * nws or brackets.shape[2] != 3:
-            raise ValueError('brackets must be int32 (%d, M, 3)' % (B * nws))
-        M = int(brackets.shape[1])                         # a bad M is the library's to refuse, with its message
-    with torch.cuda.device(dev):
-        if lengths is not None:
-            lengths = lengths.to(dev).contiguous()
-        if brackets is not None:
-            brackets = brackets.to(dev).contiguous()
-        score, log_z, log_zc, log_prob = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(4))
-        feasible = torch.empty(B * nws, dtype=torch.int32, device=dev)
-        marg = torch.empty((B * nws, Cc), dtype=torch.float32, device=dev) if marginals else None
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        for i, (ws, sl) in enumerate(parts):
-            _lib.call('cliora_constrained_parse', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
-                      _p(brackets[sl]) if M else None, M, _p(spans[sl]), _p(score[sl]), _p(log_z[sl]), _p(log_zc[sl]),
-                      _p(log_prob[sl]), _p(feasible[sl]), _p(marg[sl]) if marginals else None,
-                      C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    q = ChartQuery(diora)
+    spans = q.spans(out)
+    q.check_int32('lengths', lengths)
+    M = q.check_brackets(brackets)
+    score, log_z, log_zc, log_prob = (q.empty(torch.float32) for _ in range(4))
+    feasible = q.empty(torch.int32)
+    marg = q.empty(torch.float32, q.plan.C) if marginals else None
+    status = q.status()
+    q.launch('cliora_constrained_parse', per_sentence(q.moved(lengths)), per_sentence(q.moved(brackets)), M, per_sentence(spans),
+             per_sentence(score), per_sentence(log_z), per_sentence(log_zc), per_sentence(log_prob), per_sentence(feasible),
+             per_sentence(marg), status=status)
     return ConstrainedParse(spans, score, log_z, log_zc, log_prob, feasible, marg, status)
 
 
 def host_results(cp):
     """A ConstrainedParse's spans, feasible, log_prob and status in ONE device-to-host copy: -> (spans (B, L-1, 2) int32, feasible (B,)
     int32, log_prob (B,) float32, the number of rejected sentences)."""
-    nsp, nb = cp.spans.numel(), cp.feasible.numel()
-    host = torch.cat([cp.spans.reshape(-1), cp.feasible, cp.log_prob.view(torch.int32), cp.status]).cpu().numpy()
-    return (host[:nsp].reshape(cp.spans.shape), host[nsp:nsp + nb], host[nsp + nb:nsp + 2 * nb].view(np.float32),
-            int(host[nsp + 2 * nb:].sum()))
+    spans, feasible, log_prob, status = host_copy(cp.spans, cp.feasible, cp.log_prob, cp.status)
+    return spans, feasible, log_prob, int(status.sum())
 
 
 def refuse_rejected(count, entry='cliora_constrained_parse'):
@@ -177,11 +158,8 @@ def constrained_numpy(pair_s, lengths, brackets, L=None):
     brackets (B, M, 3) or None.  The best tree in fp32 in the kernel's operation order (cky_kernel's candidate, first maximum wins, a
     disallowed cell at -inf); log_z_c, log_z, log_prob and the marginals in fp64 from the definitions, with the mask by one test per
     (cell, row).  -> ConstrainedParse of numpy arrays as the kernel writes them; status: the number of rejected sentences."""
-    lengths = [int(x) for x in lengths]
-    if L is None:
-        L = np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)
+    lengths, L, brackets = sentences_of(pair_s, lengths, L, brackets)
     Bn, Cc = len(lengths), L * (L + 1) // 2
-    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
     spans = np.full((Bn, max(L - 1, 0), 2), -1, dtype=np.int32)
     score = np.full(Bn, -np.inf, dtype=np.float32)
     log_z = np.zeros(Bn, dtype=np.float64)
@@ -227,18 +205,7 @@ def constrained_numpy(pair_s, lengths, brackets, L=None):
             continue
         feasible[b] = 1
         score[b] = val[n - 1, 0] - np.float32(n)
-        rows, stack = [], [(n - 1, 0, 0)] if n > 1 else []
-        while stack:                                  # the kernel's walk: left subtree, right subtree, then the node
-            level, pos, phase = stack.pop()
-            if level == 0:
-                continue
-            k = bp[(level, pos)]
-            if phase == 0:
-                stack += [(level, pos, 1), (k, pos, 0)]
-            elif phase == 1:
-                stack += [(level, pos, 2), (level - k - 1, pos + k + 1, 0)]
-            else:
-                rows.append((pos, pos + level))
+        rows = walk_spans(n, lambda level, pos: bp[(level, pos)])
         spans[b, :len(rows)] = np.asarray(rows, dtype=np.int32).reshape(-1, 2)
         be = np.full((n, n), -np.inf)
         be[n - 1, 0] = 0.0
@@ -270,45 +237,23 @@ class ConstrainedKBest(_kbest.KBest):
 ConstrainedTreeSamples = collections.namedtuple('ConstrainedTreeSamples', _sample.TreeSamples._fields + ('log_z_c', 'feasible'))
 
 
-def _bracket_args(diora, brackets, lengths, ids=None):
-    """The checks constrained_parse makes of brackets / lengths (and ids), on the chart's device: -> (dev, nws, M, lengths, brackets, ids)."""
-    plan, wss = diora._plan, diora._wss
-    nws, dev, rows = len(wss), wss[0].device, plan.B * len(wss)
-    for name, t in (('lengths', lengths), ('ids', ids)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != rows):
-            raise ValueError('%s must be int32, one per sentence of the chart (%d)' % (name, rows))
-    M = 0
-    if brackets is not None:
-        if brackets.dtype != torch.int32 or brackets.dim() != 3 or brackets.shape[0] != rows or brackets.shape[2] != 3:
-            raise ValueError('brackets must be int32 (%d, M, 3)' % rows)
-        M = int(brackets.shape[1])                         # a bad M is the library's to refuse, with its message
-    with torch.cuda.device(dev):
-        lengths, brackets, ids = (None if t is None else t.to(dev).contiguous() for t in (lengths, brackets, ids))
-    return dev, nws, M, lengths, brackets, ids
-
-
 def constrained_kbest(diora, brackets, k, lengths=None):
     """cliora_kbest_spans_constrained on a chart module after its forward: the k best trees (1 .. 16) among those that keep the
     brackets -- an int32 tensor (B, M, 3) of rows (start, end, kind) (``pack_brackets``), or None for no bracket at all, which gives
     ``kbest.kbest_spans``' tensors bit for bit.  Rank 0 is ``constrained_parse``'s tree and score.  lengths: None or an int32 tensor (B,)
     for a right-padded batch.  Allocates the scratch the library asks for.  -> ConstrainedKBest."""
-    plan = diora._plan
-    B, L = plan.B, plan.L
-    k = int(k)
-    dev, nws, M, lengths, brackets, _ = _bracket_args(diora, brackets, lengths)
-    with torch.cuda.device(dev):
-        width = max(k, 0)                                  # a bad k is the library's to refuse, with its message
-        spans = torch.empty((B * nws, width, L - 1, 2), dtype=torch.int32, device=dev)
-        scores = torch.empty((B * nws, width), dtype=torch.float32, device=dev)
-        count, feasible = (torch.empty(B * nws, dtype=torch.int32, device=dev) for _ in range(2))
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        need = _lib.fn('cliora_kbest_constrained_scratch_bytes')(plan.handle, k, M)
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        for i, (ws, sl) in enumerate(workspace_slices(diora)):
-            _lib.call('cliora_kbest_spans_constrained', plan.handle, C.c_void_p(ws.data_ptr()),
-                      _p(lengths[sl]) if lengths is not None else None, _p(brackets[sl]) if M else None, M, k, _p(spans[sl]),
-                      C.c_void_p(scores[sl].data_ptr()), C.c_void_p(count[sl].data_ptr()), C.c_void_p(feasible[sl].data_ptr()),
-                      _p(scratch), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    q = ChartQuery(diora)
+    plan, k = q.plan, int(k)
+    q.check_int32('lengths', lengths)
+    M = q.check_brackets(brackets)
+    width = max(k, 0)                                      # a bad k is the library's to refuse, with its message
+    spans, scores = q.empty(torch.int32, width, plan.L - 1, 2), q.empty(torch.float32, width)
+    count, feasible = q.empty(torch.int32), q.empty(torch.int32)
+    status = q.status()
+    need = _lib.fn('cliora_kbest_constrained_scratch_bytes')(plan.handle, k, M)
+    scratch = torch.empty(need, dtype=torch.uint8, device=q.dev) if need else None
+    q.launch('cliora_kbest_spans_constrained', per_sentence(q.moved(lengths)), per_sentence(q.moved(brackets)), M, k, per_sentence(spans),
+             per_sentence(scores), per_sentence(count), per_sentence(feasible), scratch, status=status)
     return ConstrainedKBest(spans, scores, count, status, feasible)
 
 
@@ -317,36 +262,25 @@ def constrained_samples(diora, brackets, S, seed, lengths=None, ids=None, first_
     first_sample + S - 1) drawn from the posterior over parses given the brackets, at inverse temperature beta.  brackets: as
     ``constrained_kbest`` takes them; None gives ``sample.sample_spans``' spans, log_prob and log_z bit for bit.  lengths, ids: as
     ``sample.sample_spans`` takes them.  -> ConstrainedTreeSamples."""
-    plan = diora._plan
-    B, L = plan.B, plan.L
-    S = int(S)
-    dev, nws, M, lengths, brackets, ids = _bracket_args(diora, brackets, lengths, ids)
-    with torch.cuda.device(dev):
-        if ids is None and nws > 1:
-            ids = torch.arange(B * nws, dtype=torch.int32, device=dev)
-        width = min(max(S, 0), _sample.MAX_S)              # a bad S is the library's to refuse, with its message
-        spans = torch.empty((B * nws, width, L - 1, 2), dtype=torch.int32, device=dev)
-        log_prob = torch.empty((B * nws, width), dtype=torch.float32, device=dev)
-        log_z, log_zc = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(2))
-        feasible = torch.empty(B * nws, dtype=torch.int32, device=dev)
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        for i, (ws, sl) in enumerate(workspace_slices(diora)):
-            _lib.call('cliora_sample_trees_constrained', plan.handle, C.c_void_p(ws.data_ptr()),
-                      _p(lengths[sl]) if lengths is not None else None, _p(ids[sl]) if ids is not None else None,
-                      _p(brackets[sl]) if M else None, M, S, int(seed) & (2 ** 64 - 1), int(first_sample) & (2 ** 64 - 1), float(beta),
-                      _p(spans[sl]), C.c_void_p(log_prob[sl].data_ptr()), C.c_void_p(log_zc[sl].data_ptr()),
-                      C.c_void_p(log_z[sl].data_ptr()), C.c_void_p(feasible[sl].data_ptr()), C.c_void_p(status[i:i + 1].data_ptr()),
-                      _stream())
+    q = ChartQuery(diora)
+    plan, S = q.plan, int(S)
+    q.check_int32('lengths', lengths)
+    q.check_int32('ids', ids)
+    M = q.check_brackets(brackets)
+    ids = q.default_ids(ids)
+    width = min(max(S, 0), _sample.MAX_S)                  # a bad S is the library's to refuse, with its message
+    spans, log_prob = q.empty(torch.int32, width, plan.L - 1, 2), q.empty(torch.float32, width)
+    log_z, log_zc, feasible = q.empty(torch.float32), q.empty(torch.float32), q.empty(torch.int32)
+    status = q.status()
+    q.launch('cliora_sample_trees_constrained', per_sentence(q.moved(lengths)), per_sentence(ids), per_sentence(q.moved(brackets)), M, S,
+             int(seed) & (2 ** 64 - 1), int(first_sample) & (2 ** 64 - 1), float(beta), per_sentence(spans), per_sentence(log_prob),
+             per_sentence(log_zc), per_sentence(log_z), per_sentence(feasible), status=status)
     return ConstrainedTreeSamples(spans, log_prob, log_z, status, log_zc, feasible)
 
 
 # ---- their restatements ---------------------------------------------------------------------------------------------------------------
 ConstrainedKBestNumpy = collections.namedtuple('ConstrainedKBestNumpy', 'spans scores count feasible status')
 ConstrainedSamplesNumpy = collections.namedtuple('ConstrainedSamplesNumpy', 'spans log_prob log_z log_z_c feasible margin status')
-
-
-def _chart_length(pair_s, lengths, L):
-    return (np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)) if L is None else L
 
 
 def constrained_kbest_numpy(pair_s, lengths, brackets, k, L=None):
@@ -357,10 +291,8 @@ def constrained_kbest_numpy(pair_s, lengths, brackets, k, L=None):
     k = int(k)
     if not 1 <= k <= _kbest.MAX_K:
         raise ValueError('k must be in 1..%d' % _kbest.MAX_K)
-    lengths = [int(x) for x in lengths]
-    L = _chart_length(pair_s, lengths, L)
+    lengths, L, brackets = sentences_of(pair_s, lengths, L, brackets)
     Bn = len(lengths)
-    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
     spans = np.full((Bn, k, max(L - 1, 0), 2), -1, dtype=np.int32)
     scores = np.full((Bn, k), -np.inf, dtype=np.float32)
     count, feasible, status = np.zeros(Bn, dtype=np.int32), np.zeros(Bn, dtype=np.int32), 0
@@ -423,10 +355,8 @@ def constrained_sample_numpy(pair_s, lengths, brackets, S, seed, ids=None, first
     beta = float(beta)
     if not (beta >= 0 and np.isfinite(beta)):
         raise ValueError('beta must be finite and >= 0')
-    lengths = [int(x) for x in lengths]
-    L = _chart_length(pair_s, lengths, L)
+    lengths, L, brackets = sentences_of(pair_s, lengths, L, brackets)
     Bn = len(lengths)
-    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
     ids = list(range(Bn)) if ids is None else [int(x) for x in ids]
     spans = np.full((Bn, S, max(L - 1, 0), 2), -1, dtype=np.int32)
     log_prob = np.full((Bn, S), -np.inf, dtype=np.float64)
@@ -455,25 +385,19 @@ def constrained_sample_numpy(pair_s, lengths, brackets, S, seed, ids=None, first
         u = _sample.draw_uniform(lv[None], ps[None], samples[:, None, None], ids[b], seed)  # [sample, level, pos]
         weights = {}                                  # of the cells a walk can reach: the finite ones
         for s in range(S):
-            rows, acc, stack = [], 0.0, [(n - 1, 0, 0, 0)]
-            while stack:                              # the kernel's walk: draw, left subtree, right subtree, then the node
-                level, pos, phase, k = stack.pop()
-                if level == 0:
-                    continue
-                if phase == 0:
-                    if (level, pos) not in weights:
-                        ks = np.arange(level)
-                        weights[(level, pos)] = (_sample.split_weights(r, al, level, pos, beta),
-                                                 (al[ks, pos] + al[level - ks - 1, pos + ks + 1]) > -np.inf)
-                    w, finite = weights[(level, pos)]
-                    k, m = choose_split(w, u[s, level, pos], finite)
-                    margin[b, s] = min(margin[b, s], m)
-                    acc += beta * r[level, pos, k]
-                    stack += [(level, pos, 1, k), (k, pos, 0, 0)]
-                elif phase == 1:
-                    stack += [(level, pos, 2, k), (level - k - 1, pos + k + 1, 0, 0)]
-                else:
-                    rows.append((pos, pos + level))
+            acc = [0.0]
+
+            def choose(level, pos, _):
+                if (level, pos) not in weights:
+                    ks = np.arange(level)
+                    weights[(level, pos)] = (_sample.split_weights(r, al, level, pos, beta),
+                                             (al[ks, pos] + al[level - ks - 1, pos + ks + 1]) > -np.inf)
+                w, finite = weights[(level, pos)]
+                k, m = choose_split(w, u[s, level, pos], finite)
+                margin[b, s] = min(margin[b, s], m)
+                acc[0] += beta * r[level, pos, k]
+                return k, None, None
+            rows = [row[:2] for row in walk(n, choose)]
             spans[b, s, :len(rows)] = np.asarray(rows, dtype=np.int32).reshape(-1, 2)
-            log_prob[b, s] = acc - log_zc[b]
+            log_prob[b, s] = acc[0] - log_zc[b]
     return ConstrainedSamplesNumpy(spans, log_prob, log_z, log_zc, feasible, margin, status)

@@ -18,6 +18,7 @@ from .index import Index
 
 
 from ._lib import ptr as _ptr, stream as _stream, param_struct as _param_struct      # noqa: F401  (re-exports: the tests import them from here)
+from .query import ChartQuery, host_copy, per_sentence, span_buffer, workspace_slices      # noqa: F401  (re-exports, as above)
 
 
 def _grad_out(t):
@@ -42,36 +43,8 @@ def chart_buffers(plan, dev, flags, *widths):
     return outs, torch.empty(nbytes, device=dev, dtype=torch.uint8), nbytes
 
 
-def workspace_slices(diora):
-    """Per forward workspace of a chart module: (workspace, the slice of its B sentences in the module's outputs)."""
-    B = diora._plan.B
-    return [(ws, slice(i * B, (i + 1) * B)) for i, ws in enumerate(diora._wss)]
-
-
-def span_buffer(diora, out=None):
-    """The span output of a decode over a chart module's workspaces: an int32 tensor (B * workspaces, L-1, 2) on the chart's device --
-    `out`, checked, when given, else a fresh one.  -> (spans, workspace_slices(diora))."""
-    plan, dev = diora._plan, diora._wss[0].device
-    L, shape = plan.L, (plan.B * len(diora._wss), plan.L - 1, 2)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int32, device=dev)
-    elif out.shape != shape or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError('out must be a contiguous int32 tensor (%d, %d, 2) on %s' % (shape[0], L - 1, dev))
-    return out, workspace_slices(diora)
-
-
 def _cont(g):
     return g.contiguous().float() if g is not None else None
-
-
-def host_copy(*tensors):
-    """The int32 / fp32 tensors of one device as numpy arrays of their own dtypes and shapes, after ONE device-to-host copy: they
-    travel concatenated, as 32-bit words."""
-    host = torch.cat([t.reshape(-1).view(torch.int32) for t in tensors]).cpu().numpy()
-    ends = [0]
-    for t in tensors:
-        ends.append(ends[-1] + t.numel())
-    return [host[a:b].view(str(t.dtype)[len('torch.'):]).reshape(t.shape) for t, a, b in zip(tensors, ends, ends[1:])]
 
 
 class ChartWorkspaces(list):
@@ -630,12 +603,10 @@ class DioraBase(nn.Module):
     def cky_spans_device(self, out=None):
         """cky_spans left on the device: an int32 tensor (B, L-1, 2) on the chart's GPU, written into `out` when given (a contiguous
         int32 tensor of that shape; cliora_amd.evaluate decodes into its batch's output buffer)."""
-        plan = self._plan
-        spans, parts = span_buffer(self, out)
-        if plan.L > 1:
-            with torch.cuda.device(spans.device):
-                for ws, sl in parts:
-                    _lib.call('cliora_cky_spans', plan.handle, _ptr(ws), None, _ptr(spans[sl]), _stream())
+        q = ChartQuery(self)
+        spans = q.spans(out)
+        if q.plan.L > 1:
+            q.launch('cliora_cky_spans', None, per_sentence(spans))
         return spans
 
     # ---- the tree of a hard chart: it falls out of the selections, no CKY pass (DESIGN.md section 28)
@@ -808,17 +779,20 @@ class DioraBase(nn.Module):
         constrained.refuse_rejected(int(status.sum()), 'cliora_sample_trees_constrained')
         return [list(zip(self.trees_from_spans(spans[b]), log_prob[b].tolist())) if feasible[b] else [] for b in range(len(feasible))]
 
+    def _check_spans(self, required, forbidden):
+        L = self._plan.L
+        for lst in list(required) + list(forbidden or ()):
+            for s, e in lst:
+                if not 0 <= int(s) <= int(e) < L:
+                    raise ValueError('bracket (%d, %d) is not 0 <= start <= end < %d' % (s, e, L))
+
     def bracket_nll(self, required, forbidden=None, reduction='mean'):
         """The loss -log_prob of the brackets, in the autograd graph of the last forward (cliora_amd.structured.bracket_nll; DESIGN.md
         section 20): required / forbidden as cky_constrained takes them -- per-sentence lists of (start, end); a gold tree is its inner
         brackets.  The mean (or 'sum') over the sentences some tree qualifies for.  A span outside its sentence raises here, on the
         host; nothing is synchronised."""
         from . import constrained, structured
-        L = self._plan.L
-        for lst in list(required) + list(forbidden or ()):
-            for s, e in lst:
-                if not 0 <= int(s) <= int(e) < L:
-                    raise ValueError('bracket (%d, %d) is not 0 <= start <= end < %d' % (s, e, L))
+        self._check_spans(required, forbidden)
         return structured.bracket_nll(self, constrained.pack_brackets(required, forbidden), reduction=reduction)
 
     def bracket_hinge(self, required, forbidden=None, margin=1.0, penalty=float('inf'), reduction='mean'):
@@ -828,11 +802,7 @@ class DioraBase(nn.Module):
         penalty: ramp, which takes crossing brackets too.  A span outside its sentence raises here, on the host; nothing is
         synchronised."""
         from . import constrained, structured
-        L = self._plan.L
-        for lst in list(required) + list(forbidden or ()):
-            for s, e in lst:
-                if not 0 <= int(s) <= int(e) < L:
-                    raise ValueError('bracket (%d, %d) is not 0 <= start <= end < %d' % (s, e, L))
+        self._check_spans(required, forbidden)
         return structured.bracket_hinge(self, constrained.pack_brackets(required, forbidden), margin=margin, penalty=penalty,
                                         reduction=reduction)
 

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from .query import walk_spans
 
 EPS = 1e-8      # cliora/net/utils.py:10
 
@@ -199,19 +200,8 @@ def hard_spans_numpy(sel_in, L, lengths=None):
         out[b, max(n - 1, 0) if 1 <= n <= L else 0:] = -1
         if not 1 <= n <= L:
             continue
-        cnt, stack = 0, [(n - 1, 0, 0)]                                       # (level, pos, phase): an explicit stack, as on the device
-        while stack:
-            level, pos, phase = stack.pop()
-            if level == 0:
-                continue
-            k = min(max(int(sel[b, off[level] + pos]), 0), level - 1)
-            if phase == 0:
-                stack += [(level, pos, 1), (k, pos, 0)]
-            elif phase == 1:
-                stack += [(level, pos, 2), (level - k - 1, pos + k + 1, 0)]
-            else:
-                out[b, cnt] = (pos, pos + level)
-                cnt += 1
+        rows = walk_spans(n, lambda level, pos: min(max(int(sel[b, off[level] + pos]), 0), level - 1))     # (the device's clamp)
+        out[b, :len(rows)] = np.asarray(rows, dtype=np.int32).reshape(-1, 2)
     return out
 
 

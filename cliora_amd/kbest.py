@@ -14,14 +14,11 @@ value 1.0; a candidate is (val_left[i] + val_right[j]) + (s_k - smax) in fp32, i
 value descending, then split, left rank, right rank ascending.  ``kbest_numpy`` restates it in fp32 for tests, bit for bit.
 The same lists among the trees that keep required and forbidden brackets: ``constrained.constrained_kbest``.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ptr_or_null as _p, stream as _stream
-from .diora import workspace_slices
+from .query import ChartQuery, per_sentence, sentences_of, walk
 
 MAX_K = 16               # csrc/kbest_kernels.hpp KBEST_MAX_K: 4 bits per rank in a derivation's packed key
 
@@ -47,46 +44,25 @@ class KBest(object):
 def kbest_spans(diora, k, lengths=None):
     """cliora_kbest_spans on a chart module after its forward.  k: 1 .. 16.  lengths: None (every sentence has L words) or an int32
     tensor (B,) for a right-padded batch.  Allocates the scratch the library asks for.  -> KBest."""
-    plan, wss = diora._plan, diora._wss
-    B, L = plan.B, plan.L
-    nws = len(wss)
-    dev = wss[0].device
-    k = int(k)
-    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
-        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
-    with torch.cuda.device(dev):
-        if lengths is not None:
-            lengths = lengths.to(dev).contiguous()
-        width = max(k, 0)                                  # a bad k is the library's to refuse, with its message
-        spans = torch.empty((B * nws, width, L - 1, 2), dtype=torch.int32, device=dev)
-        scores = torch.empty((B * nws, width), dtype=torch.float32, device=dev)
-        count = torch.empty(B * nws, dtype=torch.int32, device=dev)
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        need = _lib.fn('cliora_kbest_scratch_bytes')(plan.handle, k)
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        for i, (ws, sl) in enumerate(workspace_slices(diora)):
-            _lib.call('cliora_kbest_spans', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None, k,
-                      _p(spans[sl]), C.c_void_p(scores[sl].data_ptr()), C.c_void_p(count[sl].data_ptr()), _p(scratch),
-                      C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    q = ChartQuery(diora)
+    plan, k = q.plan, int(k)
+    q.check_int32('lengths', lengths)
+    width = max(k, 0)                                      # a bad k is the library's to refuse, with its message
+    spans, scores, count = q.empty(torch.int32, width, plan.L - 1, 2), q.empty(torch.float32, width), q.empty(torch.int32)
+    status = q.status()
+    need = _lib.fn('cliora_kbest_scratch_bytes')(plan.handle, k)
+    scratch = torch.empty(need, dtype=torch.uint8, device=q.dev) if need else None
+    q.launch('cliora_kbest_spans', per_sentence(q.moved(lengths)), k, per_sentence(spans), per_sentence(scores), per_sentence(count),
+             scratch, status=status)
     return KBest(spans, scores, count, status)
 
 
 def _walk(key, n, rank):
     """The kernel's walk over the derivations key[level][pos, rank] = (split, left rank, right rank): left subtree, right subtree,
     then the node.  -> [(start, end)], children before parents."""
-    spans, stack = [], [(n - 1, 0, rank, 0)] if n > 1 else []
-    while stack:
-        level, pos, r, phase = stack.pop()
-        if level == 0:
-            continue
-        k, i, j = (int(v) for v in key[level][pos, r])
-        if phase == 0:
-            stack += [(level, pos, r, 1), (k, pos, i, 0)]
-        elif phase == 1:
-            stack += [(level, pos, r, 2), (level - k - 1, pos + k + 1, j, 0)]
-        else:
-            spans.append((pos, pos + level))
-    return spans
+    def choose(level, pos, r):
+        return key[level][pos, r]
+    return [row[:2] for row in walk(n, choose, rank)]
 
 
 def kbest_numpy(pair_s, lengths, k, L=None):
@@ -98,9 +74,7 @@ def kbest_numpy(pair_s, lengths, k, L=None):
     k = int(k)
     if not 1 <= k <= MAX_K:
         raise ValueError('k must be in 1..%d' % MAX_K)
-    lengths = [int(x) for x in lengths]
-    if L is None:
-        L = np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)
+    lengths, L = sentences_of(pair_s, lengths, L)
     spans = np.full((len(lengths), k, max(L - 1, 0), 2), -1, dtype=np.int32)
     scores = np.full((len(lengths), k), -np.inf, dtype=np.float32)
     count = np.zeros(len(lengths), dtype=np.int32)

@@ -13,14 +13,11 @@ counterpart; the distribution is the one whose mode its parser returns.
 ``posterior_numpy`` (fp64, from the definitions) and ``mbr_numpy`` (fp32, the kernel's operation order) restate the kernel for
 tests, as ``ragged.decode_ragged_numpy`` restates the ragged decode.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ptr_or_null as _p, stream as _stream
-from .diora import span_buffer, workspace_slices
+from .query import ChartQuery, per_sentence, sentences_of, walk_spans
 
 
 def cell_id(L, level, pos):
@@ -54,30 +51,18 @@ def span_posteriors(diora, lengths=None, mbr=False, out=None):
     """cliora_span_posteriors on a chart module after its forward.  lengths: None (every sentence has L words) or an int32 tensor
     (B,) for a right-padded batch; mbr: also decode the MBR tree.  out: a contiguous int32 tensor (B, L-1, 2) on the chart's device
     to decode the MBR spans into (cliora_amd.evaluate: its output buffer).  -> SpanPosteriors."""
-    plan, wss = diora._plan, diora._wss
-    B, L, Cc = plan.B, plan.L, plan.C
-    nws = len(wss)
-    dev = wss[0].device
-    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
-        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
-    with torch.cuda.device(dev):
-        if lengths is not None:
-            lengths = lengths.to(dev).contiguous()
-        marg = torch.empty((B * nws, Cc), dtype=torch.float32, device=dev)
-        log_z = torch.empty(B * nws, dtype=torch.float32, device=dev)
-        status = torch.empty(nws, dtype=torch.int32, device=dev)
-        spans = split = None
-        if mbr:
-            spans = span_buffer(diora, out)[0]
-            split = torch.empty((B * nws, Cc), dtype=torch.int32, device=dev)
-        need = _lib.fn('cliora_span_posteriors_scratch_bytes')(plan.handle)
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        for i, (ws, sl) in enumerate(workspace_slices(diora)):
-            _lib.call('cliora_span_posteriors', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
-                      _p(marg[sl]), _p(log_z[sl]), _p(split[sl]) if mbr else None,
-                      _p(spans[sl]) if mbr else None, _p(scratch), C.c_void_p(status[i:i + 1].data_ptr()),
-                      _stream())
-    return SpanPosteriors(marg, log_z, spans, split, status, L)
+    q = ChartQuery(diora)
+    plan = q.plan
+    q.check_int32('lengths', lengths)
+    spans = q.spans(out) if mbr else None
+    marg, log_z = q.empty(torch.float32, plan.C), q.empty(torch.float32)
+    split = q.empty(torch.int32, plan.C) if mbr else None
+    status = q.status(zeroed=False)
+    need = _lib.fn('cliora_span_posteriors_scratch_bytes')(plan.handle)
+    scratch = torch.empty(need, dtype=torch.uint8, device=q.dev) if need else None
+    q.launch('cliora_span_posteriors', per_sentence(q.moved(lengths)), per_sentence(marg), per_sentence(log_z), per_sentence(split),
+             per_sentence(spans), scratch, status=status)
+    return SpanPosteriors(marg, log_z, spans, split, status, plan.L)
 
 
 def marginal_table(marginals, L):
@@ -119,9 +104,7 @@ def posterior_numpy(pair_s, lengths, L=None):
     inside scores of the (padded) chart of length L (inferred from level 1 when not given), sentence b its first lengths[b] words.
     -> (marginals (B, C) float64, 0 outside each triangle; log_z (B,) float64).  Tables indexed [level, pos]; the uses of a cell are
     those of ``cell_uses``, taken a sibling level j at a time."""
-    lengths = [int(x) for x in lengths]
-    if L is None:
-        L = np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)
+    lengths, L = sentences_of(pair_s, lengths, L)
     Cc = L * (L + 1) // 2
     mu = np.zeros((len(lengths), Cc), dtype=np.float64)
     log_z = np.zeros(len(lengths), dtype=np.float64)
@@ -159,17 +142,5 @@ def mbr_numpy(marginals, lengths, L):
                 val[(level, pos)] = np.float32(cand[k] + marginals[b, cell_id(L, level, pos)])
                 bp[(level, pos)] = k
                 split[b, cell_id(L, level, pos)] = k
-        spans, stack = [], [(n - 1, 0, 0)] if n > 1 else []
-        while stack:                                  # the kernel's walk: left subtree, right subtree, then the node
-            level, pos, phase = stack.pop()
-            if level == 0:
-                continue
-            k = bp[(level, pos)]
-            if phase == 0:
-                stack += [(level, pos, 1), (k, pos, 0)]
-            elif phase == 1:
-                stack += [(level, pos, 2), (level - k - 1, pos + k + 1, 0)]
-            else:
-                spans.append((pos, pos + level))
-        out.append(spans)
+        out.append(walk_spans(n, lambda level, pos: bp[(level, pos)]))
     return out, split

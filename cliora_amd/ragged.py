@@ -41,14 +41,12 @@ own inside selections (``cliora_hard_spans_ragged``), and ``evaluate.evaluate_ra
     for idx, lens, diora in forward_ragged_train(net, sentences): ...        # the same, one pack at a time, with autograd live
     for idx, lens, diora in forward_ragged_train(vl_net, sentences, obj_feats=feats): ...      # a CLIORA net with its images
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import ptr_or_null as _p, stream as _stream
-from .diora import host_copy, span_buffer
+from .query import ChartQuery, host_copy, per_sentence, walk_spans
 
 MAX_L = 64                # csrc/plan.hpp: CLIORA_MAX_L -- the default of max_len, the training charts, one word of the root-level mask
 MAX_L_INSIDE = _lib.MAX_L_FWD    # csrc/plan.hpp: CLIORA_MAX_L_FWD -- what max_len may be raised to, for the inside-only and the both-pass entries
@@ -131,17 +129,7 @@ def decode_ragged_numpy(pair_s, lengths, L=None):
                 val[(level, pos)], bp[(level, pos)] = cand[k], k
                 if split is not None:
                     split[b, L * (L + 1) // 2 - (L - level) * (L - level + 1) // 2 + pos] = k
-        spans = []
-
-        def walk(level, pos):
-            if level == 0:
-                return
-            k = bp[(level, pos)]
-            walk(k, pos)
-            walk(level - k - 1, pos + k + 1)
-            spans.append((pos, pos + level))
-        walk(n - 1, 0)
-        out.append(spans)
+        out.append(walk_spans(n, lambda level, pos: bp[(level, pos)]))
     return out if split is None else (out, split)
 
 
@@ -152,19 +140,11 @@ def cky_spans_ragged(diora, lengths, split_out=False, out=None):
     with (-1, -1) beyond each sentence's n - 1 rows; status (number of workspaces,) int32 counting the lengths outside [1, L], which
     the caller must check; split (B, C) int32, -1 at the leaves and outside each triangle.  Device tensors; nothing is synchronised.
     out: a contiguous int32 tensor (B, L-1, 2) on the chart's device to decode into (cliora_amd.evaluate: its output buffer)."""
-    plan, wss = diora._plan, diora._wss
-    B, nws = plan.B, len(wss)
-    if lengths.dtype != torch.int32 or lengths.numel() != B * nws:
-        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
-    dev = wss[0].device
-    with torch.cuda.device(dev):
-        lengths = lengths.to(dev).contiguous()
-        spans, parts = span_buffer(diora, out)
-        status = torch.empty(nws, dtype=torch.int32, device=dev)
-        split = torch.empty((B * nws, plan.C), dtype=torch.int32, device=dev) if split_out else None
-        for i, (ws, sl) in enumerate(parts):
-            _lib.call('cliora_cky_spans_ragged', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]),
-                      _p(split[sl]) if split_out else C.c_void_p(0), _p(spans[sl]), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    q = ChartQuery(diora)
+    q.check_int32('lengths', lengths)
+    spans, status = q.spans(out), q.status(zeroed=False)
+    split = q.empty(torch.int32, q.plan.C) if split_out else None
+    q.launch('cliora_cky_spans_ragged', per_sentence(q.moved(lengths)), per_sentence(split), per_sentence(spans), status=status)
     return (spans, status, split) if split_out else (spans, status)
 
 

@@ -16,15 +16,11 @@ depends on (seed, sentence id, sample index, cell) and the sentence's scores alo
 The same draws from the distribution given required and forbidden brackets: ``constrained.constrained_samples``.
 """
 import collections
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr_or_null as _p, stream as _stream
-from .diora import workspace_slices
 from .posterior import inside_numpy
+from .query import ChartQuery, per_sentence, sentences_of, walk
 
 MAX_S = 1 << 20          # csrc/sample_kernels.hpp SAMPLE_MAX_S
 
@@ -39,31 +35,16 @@ def sample_spans(diora, S, seed, lengths=None, ids=None, first_sample=0, beta=1.
     first_sample + S - 1; seed: 64 bits.  lengths: None (every sentence has L words) or an int32 tensor (B,) for a right-padded batch.
     ids: None or an int32 tensor (B,) of the caller's sentence numbers (None: the row in the chart, over every workspace).
     -> TreeSamples."""
-    plan, wss = diora._plan, diora._wss
-    B, L = plan.B, plan.L
-    nws = len(wss)
-    dev = wss[0].device
-    S = int(S)
-    for name, t in (('lengths', lengths), ('ids', ids)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != B * nws):
-            raise ValueError('%s must be int32, one per sentence of the chart (%d)' % (name, B * nws))
-    with torch.cuda.device(dev):
-        if lengths is not None:
-            lengths = lengths.to(dev).contiguous()
-        if ids is not None:
-            ids = ids.to(dev).contiguous()
-        elif nws > 1:
-            ids = torch.arange(B * nws, dtype=torch.int32, device=dev)
-        width = min(max(S, 0), MAX_S)                      # a bad S is the library's to refuse, with its message
-        spans = torch.empty((B * nws, width, L - 1, 2), dtype=torch.int32, device=dev)
-        log_prob = torch.empty((B * nws, width), dtype=torch.float32, device=dev)
-        log_z = torch.empty(B * nws, dtype=torch.float32, device=dev)
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        for i, (ws, sl) in enumerate(workspace_slices(diora)):
-            _lib.call('cliora_sample_trees', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
-                      _p(ids[sl]) if ids is not None else None, S, int(seed) & (2 ** 64 - 1), int(first_sample) & (2 ** 64 - 1),
-                      float(beta), _p(spans[sl]), C.c_void_p(log_prob[sl].data_ptr()), C.c_void_p(log_z[sl].data_ptr()),
-                      C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    q = ChartQuery(diora)
+    plan, S = q.plan, int(S)
+    q.check_int32('lengths', lengths)
+    q.check_int32('ids', ids)
+    ids = q.default_ids(ids)
+    width = min(max(S, 0), MAX_S)                          # a bad S is the library's to refuse, with its message
+    spans, log_prob, log_z = q.empty(torch.int32, width, plan.L - 1, 2), q.empty(torch.float32, width), q.empty(torch.float32)
+    status = q.status()
+    q.launch('cliora_sample_trees', per_sentence(q.moved(lengths)), per_sentence(ids), S, int(seed) & (2 ** 64 - 1),
+             int(first_sample) & (2 ** 64 - 1), float(beta), per_sentence(spans), per_sentence(log_prob), per_sentence(log_z), status=status)
     return TreeSamples(spans, log_prob, log_z, status)
 
 
@@ -128,9 +109,7 @@ def sample_numpy(pair_s, lengths, S, seed, ids=None, first_sample=0, beta=1.0, L
     beta = float(beta)
     if not (beta >= 0 and np.isfinite(beta)):
         raise ValueError('beta must be finite and >= 0')
-    lengths = [int(x) for x in lengths]
-    if L is None:
-        L = np.asarray(pair_s[1]).shape[1] + 1 if max(lengths) > 1 else max(lengths)
+    lengths, L = sentences_of(pair_s, lengths, L)
     ids = list(range(len(lengths))) if ids is None else [int(x) for x in ids]
     spans = np.full((len(lengths), S, max(L - 1, 0), 2), -1, dtype=np.int32)
     log_prob = np.zeros((len(lengths), S), dtype=np.float64)
@@ -146,22 +125,16 @@ def sample_numpy(pair_s, lengths, S, seed, ids=None, first_sample=0, beta=1.0, L
         lv, ps = np.meshgrid(np.arange(n), np.arange(n), indexing='ij')
         u = draw_uniform(lv[None], ps[None], samples[:, None, None], ids[b], seed)          # [sample, level, pos]
         for s in range(S):
-            rows, acc, stack = [], 0.0, [(n - 1, 0, 0, 0)]
-            while stack:                              # the kernel's walk: draw, left subtree, right subtree, then the node
-                level, pos, phase, k = stack.pop()
-                if level == 0:
-                    continue
-                if phase == 0:
-                    c = cum[(level, pos)]
-                    thr = u[s, level, pos] * c[-1]
-                    k = min(int((c <= thr).sum()), level - 1)
-                    margin[b, s] = min(margin[b, s], float(np.abs(thr - c).min() / c[-1]))
-                    acc += beta * r[level, pos, k]
-                    stack += [(level, pos, 1, k), (k, pos, 0, 0)]
-                elif phase == 1:
-                    stack += [(level, pos, 2, k), (level - k - 1, pos + k + 1, 0, 0)]
-                else:
-                    rows.append((pos, pos + level))
-            spans[b, s, :len(rows)] = np.asarray(rows, dtype=np.int32).reshape(-1, 2)
-            log_prob[b, s] = acc - log_z[b]
+            acc = [0.0]
+
+            def choose(level, pos, _):
+                c = cum[(level, pos)]
+                thr = u[s, level, pos] * c[-1]
+                k = min(int((c <= thr).sum()), level - 1)
+                margin[b, s] = min(margin[b, s], float(np.abs(thr - c).min() / c[-1]))
+                acc[0] += beta * r[level, pos, k]
+                return k, None, None
+            tree = [row[:2] for row in walk(n, choose)]
+            spans[b, s, :len(tree)] = np.asarray(tree, dtype=np.int32).reshape(-1, 2)
+            log_prob[b, s] = acc[0] - log_z[b]
     return spans, log_prob, log_z, margin

@@ -34,16 +34,14 @@ The third part is the max-margin family over the same potentials (cliora_bracket
 perceptron and ramp losses, ``bracket_hinge``, whose subgradient -- a difference of two trees -- takes the same hand-off.
 """
 import collections
-import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ptr_or_null as _p, stream as _stream
-from .constrained import allowed_cells, bad_row
-from .diora import workspace_slices
+from .constrained import allowed_cells, bad_row, refuse_rejected
 from .posterior import cell_id
+from .query import ChartQuery, host_copy, per_sentence, walk
 
 # d_split (cliora_plan_split_score_count * workspaces,) fp32 -- G in the layout of the inside split-score rows; log_prob (B,) fp32;
 # feasible (B,) int32; status (number of workspaces,) int32.  Device tensors; nothing is synchronised.
@@ -72,46 +70,72 @@ def split_rows_by_level(plan, d_split):
     return out
 
 
-def _check_brackets(brackets, nsent):
-    if brackets is None:
-        return 0
-    if brackets.dtype != torch.int32 or brackets.dim() != 3 or brackets.shape[0] != nsent or brackets.shape[2] != 3:
-        raise ValueError('brackets must be int32 (%d, M, 3)' % nsent)
-    return int(brackets.shape[1])                          # a bad M is the library's to refuse, with its message
+def _refuse_no_forward(diora, who):
+    if diora._plan is None:
+        raise _lib.ChartLibError('%s: the module has run no forward' % who)
 
 
 def bracket_grad(diora, brackets, weights=None, lengths=None):
     """cliora_bracket_grad on a chart module after its forward (any forward: this call needs no backward state).  brackets: int32
     (B, M, 3) (``constrained.pack_brackets``) or None; weights: fp32 (B,) or None = 1; lengths: int32 (B,) or None.  One d_split buffer
     per workspace of ``workspace_slices``, back to back.  -> BracketGrad of device tensors; nothing is synchronised."""
-    if diora._plan is None:
-        raise _lib.ChartLibError('bracket_grad: the module has run no forward')
-    plan, parts = diora._plan, workspace_slices(diora)
-    nws, B = len(parts), plan.B
-    dev = parts[0][0].device
-    M = _check_brackets(brackets, B * nws)
-    if lengths is None:
-        lengths = getattr(diora._wss, 'lengths', None)         # a padded training chart of mixed lengths: each sentence's own triangle
-    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
-        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
-    if weights is not None and weights.numel() != B * nws:
-        raise ValueError('weights must hold one value per sentence of the chart (%d)' % (B * nws))
-    with torch.cuda.device(dev):
-        count = split_score_count(plan)
-        lengths = lengths.to(dev).contiguous() if lengths is not None else None
-        brackets = brackets.to(dev).contiguous() if brackets is not None else None
-        weights = weights.to(dev).contiguous().float().reshape(-1) if weights is not None else None
-        buf = torch.empty(max(count * nws, 1), dtype=torch.float32, device=dev)      # (one word: no row, but the library wants an address)
-        d_split = buf[:count * nws]
-        log_prob = torch.empty(B * nws, dtype=torch.float32, device=dev)
-        feasible = torch.empty(B * nws, dtype=torch.int32, device=dev)
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        for i, (ws, sl) in enumerate(parts):
-            _lib.call('cliora_bracket_grad', plan.handle, C.c_void_p(ws.data_ptr()), _p(lengths[sl]) if lengths is not None else None,
-                      _p(brackets[sl]) if M else None, M, _p(weights[sl]) if weights is not None else None,
-                      C.c_void_p(buf.data_ptr() + 4 * i * count), _p(log_prob[sl]), _p(feasible[sl]),
-                      C.c_void_p(status[i:i + 1].data_ptr()), _stream())
+    _refuse_no_forward(diora, 'bracket_grad')
+    q = ChartQuery(diora)
+    M = q.check_brackets(brackets)
+    lengths = q.lengths_or_holders(lengths)
+    q.check_int32('lengths', lengths)
+    q.check_weights('weights', weights)
+    d_arg, d_split = q.split_buffer()
+    log_prob, feasible, status = q.empty(torch.float32), q.empty(torch.int32), q.status()
+    q.launch('cliora_bracket_grad', per_sentence(q.moved(lengths)), per_sentence(q.moved(brackets)), M, per_sentence(q.moved_weights(weights)),
+             d_arg, per_sentence(log_prob), per_sentence(feasible), status=status)
     return BracketGrad(d_split, log_prob, feasible, status)
+
+
+# ---- the loss node: what the three autograd Functions of this module share ----------------------------------------------------------
+def _trainable(diora, who, noun, instead, long_instead=''):
+    """Whether a structured loss can train through the last forward of `diora`: the refusals of the module docstring, in their order.
+    noun: what `who` computes, instead / long_instead: where its value alone comes from (the words that differ between the callers).
+    -> the chart's inside_s, the formal input of the loss's node."""
+    _refuse_no_forward(diora, who)
+    plan = diora._plan
+    if plan.L > _lib.MAX_L:
+        raise _lib.ChartLibError('%s: L = %d > %d is inference only (the backward stops at %d words), so the %s has nothing to train '
+                                 'through%s' % (who, plan.L, _lib.MAX_L, _lib.MAX_L, noun, long_instead))
+    if getattr(diora, 'plan_arch', 0) != 0:
+        raise _lib.ChartLibError('%s: a TreeLSTM chart takes no cotangent on its split scores (cliora_lstm_backward has no such input)' % who)
+    holder = diora._wss
+    if len(holder) != 1 or getattr(holder, 'split_cot', None) is None:
+        raise _lib.ChartLibError('%s: the module holds %d workspaces that no single chart node owns; call it after each forward of its '
+                                 'own' % (who, len(holder)))
+    inside_s = diora.chart.inside_s
+    if not inside_s.requires_grad:
+        raise _lib.ChartLibError('%s: the forward kept no backward state (it ran under torch.no_grad(), in eval mode without gradients, '
+                                 'or on a padded chart); %s' % (who, instead))
+    return inside_s
+
+
+def _keep(ctx, inside_s, diora, *args):
+    """The forward side of the hand-off: the plan and the forward's holder (workspace + slot), inside_s's shape, the query's own
+    arguments."""
+    ctx.chart, ctx.args, ctx.shape = _ChartView(diora._plan, diora._wss), args, inside_s.shape
+    ctx.set_materialize_grads(False)
+
+
+def _hand_off(ctx, query, **weights):
+    """The backward side: `query` again with the cotangents as its weights, its d_split ADDED into the slot of the forward's holder
+    (the module docstring).  -> the node's gradients: zeros for inside_s, None for the rest; all None without a cotangent."""
+    if all(w is None for w in weights.values()):
+        return (None,) * (2 + len(ctx.args))
+    d = query(ctx.chart, *ctx.args, **weights).d_split
+    slot = ctx.chart._wss.split_cot
+    slot[0] = d if slot[0] is None else slot[0] + d
+    return (torch.zeros(ctx.shape, dtype=torch.float32, device=d.device),) + (None,) * (1 + len(ctx.args))
+
+
+def _check_reduction(reduction):
+    if reduction not in ('mean', 'sum'):
+        raise ValueError("reduction must be 'mean' or 'sum'")
 
 
 class _BracketLogProb(torch.autograd.Function):
@@ -119,51 +143,27 @@ class _BracketLogProb(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inside_s, diora, brackets):
-        res = bracket_grad(diora, brackets)
-        ctx.chart = _ChartView(diora._plan, diora._wss)            # the plan and the forward's holder (workspace + slot)
-        ctx.brackets, ctx.shape = brackets, inside_s.shape
-        ctx.set_materialize_grads(False)
-        return res.log_prob
+        _keep(ctx, inside_s, diora, brackets)
+        return bracket_grad(diora, brackets).log_prob
 
     @staticmethod
     def backward(ctx, g):
-        if g is None:
-            return None, None, None
-        holder = ctx.chart._wss
-        d = bracket_grad(ctx.chart, ctx.brackets, weights=g).d_split
-        slot = holder.split_cot
-        slot[0] = d if slot[0] is None else slot[0] + d
-        return torch.zeros(ctx.shape, dtype=torch.float32, device=d.device), None, None
+        return _hand_off(ctx, bracket_grad, weights=g)
 
 
 def bracket_log_prob(diora, brackets):
     """log_prob (B,) fp32 of the brackets (int32 (B, M, 3), ``constrained.pack_brackets``; None: no bracket) under the last forward of
     `diora`, in its autograd graph: -inf, with a zero gradient, for a sentence no tree qualifies for (or with a bad row).  The
     mechanism and the refusals: the module docstring."""
-    plan = diora._plan
-    if plan is None:
-        raise _lib.ChartLibError('bracket_log_prob: the module has run no forward')
-    if plan.L > _lib.MAX_L:
-        raise _lib.ChartLibError('bracket_log_prob: L = %d > %d is inference only (the backward stops at %d words), so the loss has '
-                                 'nothing to train through; cliora_amd.constrained gives its value' % (plan.L, _lib.MAX_L, _lib.MAX_L))
-    if getattr(diora, 'plan_arch', 0) != 0:
-        raise _lib.ChartLibError('bracket_log_prob: a TreeLSTM chart takes no cotangent on its split scores (cliora_lstm_backward has no such input)')
-    holder = diora._wss
-    if len(holder) != 1 or getattr(holder, 'split_cot', None) is None:
-        raise _lib.ChartLibError('bracket_log_prob: the module holds %d workspaces that no single chart node owns; call it after each '
-                                 'forward of its own' % len(holder))
-    inside_s = diora.chart.inside_s
-    if not inside_s.requires_grad:
-        raise _lib.ChartLibError('bracket_log_prob: the forward kept no backward state (it ran under torch.no_grad(), in eval mode '
-                                 'without gradients, or on a padded chart); cliora_amd.constrained gives the value alone')
+    inside_s = _trainable(diora, 'bracket_log_prob', 'loss', 'cliora_amd.constrained gives the value alone',
+                          '; cliora_amd.constrained gives its value')
     return _BracketLogProb.apply(inside_s, diora, brackets)
 
 
 def bracket_nll(diora, brackets, reduction='mean'):
     """-log_prob of the brackets over the sentences some tree qualifies for: their mean ('mean') or sum ('sum'), a 0-d tensor in the
     graph; 0 (with a graph) when no sentence is feasible.  Nothing is synchronised."""
-    if reduction not in ('mean', 'sum'):
-        raise ValueError("reduction must be 'mean' or 'sum'")
+    _check_reduction(reduction)
     lp = bracket_log_prob(diora, brackets)
     ok = torch.isfinite(lp)
     total = -torch.where(ok, lp, torch.zeros_like(lp)).sum()
@@ -198,16 +198,20 @@ def _tables(n, r, allowed):
     return a, b
 
 
+def _sentences(pair_s, lengths, brackets=None):
+    """What the restatements below start with: -> (lengths as ints, their number, the chart's length from the levels of `pair_s`, the
+    brackets as an array, (B, 0, 3) for None)."""
+    lengths = [int(x) for x in lengths]
+    L = (max(int(lv) for lv in pair_s) + 1) if len(pair_s) else 1
+    return lengths, len(lengths), L, np.zeros((len(lengths), 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
+
+
 def bracket_grad_numpy(pair_s, lengths, brackets, weights=None):
     """cliora_bracket_grad restated in fp64 from the formulas (tests): `pair_s[level]` (B, L - level, level[, 1]) the per-split inside
     scores of the (padded) chart, sentence b its first lengths[b] words; brackets (B, M, 3) or None; weights (B,) or None.
     -> {level: (B, L - level, level)} fp64, G = w d log_prob / d s; zero beyond a triangle, for a bad length or row, for an infeasible
     set and where no cell is disallowed."""
-    lengths = [int(x) for x in lengths]
-    Bn = len(lengths)
-    levels = sorted(int(lv) for lv in pair_s)
-    L = (max(levels) + 1) if levels else 1
-    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
+    lengths, Bn, L, brackets = _sentences(pair_s, lengths, brackets)
     weights = np.ones(Bn) if weights is None else np.asarray(weights, dtype=np.float64)
     out = {level: np.zeros((Bn, L - level, level)) for level in range(1, L)}
     for b, n in enumerate(lengths):
@@ -252,35 +256,20 @@ def tree_expectation(diora, cost=None, w_cost=None, w_entropy=None, lengths=None
     (B, C) in the cell order of inside_s or None = 0; w_cost: fp32 (B,) or None = 1; w_entropy: fp32 (B,) or None = 0; lengths: int32
     (B,) or None.  d_split = d (w_cost risk + w_entropy entropy) / d s, one buffer per workspace of ``workspace_slices``, back to
     back.  -> TreeExpectation of device tensors; nothing is synchronised."""
-    if diora._plan is None:
-        raise _lib.ChartLibError('tree_expectation: the module has run no forward')
-    plan, parts = diora._plan, workspace_slices(diora)
-    nws, B = len(parts), plan.B
-    dev = parts[0][0].device
-    if lengths is None:
-        lengths = getattr(diora._wss, 'lengths', None)         # a padded training chart of mixed lengths: each sentence's own triangle
-    if cost is not None and (cost.dim() != 2 or tuple(cost.shape) != (B * nws, plan.C)):
-        raise ValueError('cost must be (%d, %d): one value per cell of the chart' % (B * nws, plan.C))
-    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
-        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
-    for name, w in (('w_cost', w_cost), ('w_entropy', w_entropy)):
-        if w is not None and w.numel() != B * nws:
-            raise ValueError('%s must hold one value per sentence of the chart (%d)' % (name, B * nws))
-    with torch.cuda.device(dev):
-        count = split_score_count(plan)
-        lengths = lengths.to(dev).contiguous() if lengths is not None else None
-        cost = cost.to(dev).float().contiguous() if cost is not None else None
-        w_cost = w_cost.to(dev).contiguous().float().reshape(-1) if w_cost is not None else None
-        w_entropy = w_entropy.to(dev).contiguous().float().reshape(-1) if w_entropy is not None else None
-        buf = torch.empty(max(count * nws, 1), dtype=torch.float32, device=dev)      # (one word: no row, but the library wants an address)
-        risk, entropy, log_z = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(3))
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        sub = lambda t, sl: _p(t[sl]) if t is not None else None
-        for i, (ws, sl) in enumerate(parts):
-            _lib.call('cliora_tree_expectation', plan.handle, C.c_void_p(ws.data_ptr()), sub(lengths, sl), sub(cost, sl), sub(w_cost, sl),
-                      sub(w_entropy, sl), C.c_void_p(buf.data_ptr() + 4 * i * count), _p(risk[sl]), _p(entropy[sl]), _p(log_z[sl]),
-                      C.c_void_p(status[i:i + 1].data_ptr()), _stream())
-    return TreeExpectation(buf[:count * nws], risk, entropy, log_z, status)
+    _refuse_no_forward(diora, 'tree_expectation')
+    q = ChartQuery(diora)
+    lengths = q.lengths_or_holders(lengths)
+    q.check_cost(cost)
+    q.check_int32('lengths', lengths)
+    q.check_weights('w_cost', w_cost)
+    q.check_weights('w_entropy', w_entropy)
+    cost = cost.to(q.dev).float().contiguous() if cost is not None else None
+    d_arg, d_split = q.split_buffer()
+    risk, entropy, log_z = (q.empty(torch.float32) for _ in range(3))
+    status = q.status()
+    q.launch('cliora_tree_expectation', per_sentence(q.moved(lengths)), per_sentence(cost), per_sentence(q.moved_weights(w_cost)),
+             per_sentence(q.moved_weights(w_entropy)), d_arg, per_sentence(risk), per_sentence(entropy), per_sentence(log_z), status=status)
+    return TreeExpectation(d_split, risk, entropy, log_z, status)
 
 
 class _TreeObjective(torch.autograd.Function):
@@ -288,24 +277,15 @@ class _TreeObjective(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inside_s, diora, cost):
+        _keep(ctx, inside_s, diora, cost)
         res = tree_expectation(diora, cost)
-        ctx.chart = _ChartView(diora._plan, diora._wss)            # the plan and the forward's holder (workspace + slot)
-        ctx.cost, ctx.shape = cost, inside_s.shape
-        ctx.set_materialize_grads(False)
         return res.risk, res.entropy
 
     @staticmethod
     def backward(ctx, g_risk, g_entropy):
-        if g_risk is None and g_entropy is None:
-            return None, None, None
-        holder = ctx.chart._wss
         some = g_risk if g_risk is not None else g_entropy
-        zeros = torch.zeros_like(some)
-        d = tree_expectation(ctx.chart, ctx.cost, w_cost=zeros if g_risk is None else g_risk,
-                             w_entropy=zeros if g_entropy is None else g_entropy).d_split
-        slot = holder.split_cot
-        slot[0] = d if slot[0] is None else slot[0] + d
-        return torch.zeros(ctx.shape, dtype=torch.float32, device=d.device), None, None
+        zeros = torch.zeros_like(some) if some is not None else None
+        return _hand_off(ctx, tree_expectation, w_cost=zeros if g_risk is None else g_risk, w_entropy=zeros if g_entropy is None else g_entropy)
 
 
 def tree_objective(diora, cost=None):
@@ -313,28 +293,11 @@ def tree_objective(diora, cost=None):
     per-cell cost (fp32 (B, C) in the cell order of inside_s, ``span_costs``; None = 0) over the trees, and the entropy of the
     distribution over trees.  Their cotangents reach the chart through the bracket loss's slot, into which they add: the objective
     sums with ``bracket_log_prob`` and with a second call on the same forward.  The refusals are ``bracket_log_prob``'s."""
-    plan = diora._plan
-    if plan is None:
-        raise _lib.ChartLibError('tree_objective: the module has run no forward')
-    if plan.L > _lib.MAX_L:
-        raise _lib.ChartLibError('tree_objective: L = %d > %d is inference only (the backward stops at %d words), so the objective has '
-                                 'nothing to train through' % (plan.L, _lib.MAX_L, _lib.MAX_L))
-    if getattr(diora, 'plan_arch', 0) != 0:
-        raise _lib.ChartLibError('tree_objective: a TreeLSTM chart takes no cotangent on its split scores (cliora_lstm_backward has no such input)')
-    holder = diora._wss
-    if len(holder) != 1 or getattr(holder, 'split_cot', None) is None:
-        raise _lib.ChartLibError('tree_objective: the module holds %d workspaces that no single chart node owns; call it after each '
-                                 'forward of its own' % len(holder))
-    inside_s = diora.chart.inside_s
-    if not inside_s.requires_grad:
-        raise _lib.ChartLibError('tree_objective: the forward kept no backward state (it ran under torch.no_grad(), in eval mode '
-                                 'without gradients, or on a padded chart); tree_expectation gives the values alone')
-    return _TreeObjective.apply(inside_s, diora, cost)
+    return _TreeObjective.apply(_trainable(diora, 'tree_objective', 'objective', 'tree_expectation gives the values alone'), diora, cost)
 
 
 def _reduce(v, reduction):
-    if reduction not in ('mean', 'sum'):
-        raise ValueError("reduction must be 'mean' or 'sum'")
+    _check_reduction(reduction)
     return v.mean() if reduction == 'mean' else v.sum()
 
 
@@ -373,10 +336,7 @@ def tree_expectation_numpy(pair_s, lengths, cost, w_cost=None, w_entropy=None):
     The expectation semiring in the linear domain, with no logarithm but log_z: a cell carries the pair (Z, Zv) = (sum of the weights
     of its subtrees, sum of weight x value), a product of pairs is (a b, a bv + av b); the outside pair (O, Ov) is pushed from every
     parent to its two children.  Then sum over the trees through edge e of weight x V(T) is Ov Z_l Z_r w + O (Z_l Z_r w)v."""
-    lengths = [int(x) for x in lengths]
-    Bn = len(lengths)
-    levels = sorted(int(lv) for lv in pair_s)
-    L = (max(levels) + 1) if levels else 1
+    lengths, Bn, L, _ = _sentences(pair_s, lengths)
     cost = np.zeros((Bn, L * (L + 1) // 2)) if cost is None else np.asarray(cost, dtype=np.float64)
     w_cost = np.ones(Bn) if w_cost is None else np.asarray(w_cost, dtype=np.float64)
     w_entropy = np.zeros(Bn) if w_entropy is None else np.asarray(w_entropy, dtype=np.float64)
@@ -464,35 +424,22 @@ def bracket_margin(diora, brackets, margin=1.0, penalty=float('inf'), weights=No
     """cliora_bracket_margin on a chart module after its forward (any forward: this call needs no backward state).  brackets, weights,
     lengths: as ``bracket_grad`` takes them; spans: also give the two trees.  One d_split buffer per workspace of
     ``workspace_slices``, back to back.  -> BracketMargin of device tensors; nothing is synchronised."""
-    if diora._plan is None:
-        raise _lib.ChartLibError('bracket_margin: the module has run no forward')
+    _refuse_no_forward(diora, 'bracket_margin')
     margin, penalty = _check_margin(margin, penalty)
-    plan, parts = diora._plan, workspace_slices(diora)
-    nws, B = len(parts), plan.B
-    dev = parts[0][0].device
-    M = _check_brackets(brackets, B * nws)
-    if lengths is None:
-        lengths = getattr(diora._wss, 'lengths', None)         # a padded training chart of mixed lengths: each sentence's own triangle
-    if lengths is not None and (lengths.dtype != torch.int32 or lengths.numel() != B * nws):
-        raise ValueError('lengths must be int32, one per sentence of the chart (%d)' % (B * nws))
-    if weights is not None and weights.numel() != B * nws:
-        raise ValueError('weights must hold one value per sentence of the chart (%d)' % (B * nws))
-    with torch.cuda.device(dev):
-        count = split_score_count(plan)
-        lengths = lengths.to(dev).contiguous() if lengths is not None else None
-        brackets = brackets.to(dev).contiguous() if brackets is not None else None
-        weights = weights.to(dev).contiguous().float().reshape(-1) if weights is not None else None
-        buf = torch.empty(max(count * nws, 1), dtype=torch.float32, device=dev)      # (one word: no row, but the library wants an address)
-        loss, aug, ref = (torch.empty(B * nws, dtype=torch.float32, device=dev) for _ in range(3))
-        viol, feasible = (torch.empty(B * nws, dtype=torch.int32, device=dev) for _ in range(2))
-        sp_a, sp_r = (torch.empty((B * nws, plan.L - 1, 2), dtype=torch.int32, device=dev) for _ in range(2)) if spans else (None, None)
-        status = torch.zeros(nws, dtype=torch.int32, device=dev)
-        sub = lambda t, sl: _p(t[sl]) if t is not None else None
-        for i, (ws, sl) in enumerate(parts):
-            _lib.call('cliora_bracket_margin', plan.handle, C.c_void_p(ws.data_ptr()), sub(lengths, sl), _p(brackets[sl]) if M else None, M,
-                      margin, penalty, sub(weights, sl), C.c_void_p(buf.data_ptr() + 4 * i * count), _p(loss[sl]), _p(aug[sl]), _p(ref[sl]),
-                      _p(viol[sl]), _p(feasible[sl]), sub(sp_a, sl), sub(sp_r, sl), C.c_void_p(status[i:i + 1].data_ptr()), _stream())
-    return BracketMargin(buf[:count * nws], loss, aug, ref, viol, feasible, sp_a, sp_r, status)
+    q = ChartQuery(diora)
+    M = q.check_brackets(brackets)
+    lengths = q.lengths_or_holders(lengths)
+    q.check_int32('lengths', lengths)
+    q.check_weights('weights', weights)
+    d_arg, d_split = q.split_buffer()
+    loss, aug, ref = (q.empty(torch.float32) for _ in range(3))
+    viol, feasible = q.empty(torch.int32), q.empty(torch.int32)
+    sp_a, sp_r = (q.empty(torch.int32, q.plan.L - 1, 2) for _ in range(2)) if spans else (None, None)
+    status = q.status()
+    q.launch('cliora_bracket_margin', per_sentence(q.moved(lengths)), per_sentence(q.moved(brackets)), M, margin, penalty,
+             per_sentence(q.moved_weights(weights)), d_arg, per_sentence(loss), per_sentence(aug), per_sentence(ref), per_sentence(viol),
+             per_sentence(feasible), per_sentence(sp_a), per_sentence(sp_r), status=status)
+    return BracketMargin(d_split, loss, aug, ref, viol, feasible, sp_a, sp_r, status)
 
 
 class _BracketMarginLoss(torch.autograd.Function):
@@ -500,43 +447,20 @@ class _BracketMarginLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inside_s, diora, brackets, margin, penalty):
+        _keep(ctx, inside_s, diora, brackets, margin, penalty)
         res = bracket_margin(diora, brackets, margin, penalty)
-        ctx.chart = _ChartView(diora._plan, diora._wss)            # the plan and the forward's holder (workspace + slot)
-        ctx.brackets, ctx.shape, ctx.scalars = brackets, inside_s.shape, (margin, penalty)
-        ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(res.feasible)
         return res.loss, res.feasible
 
     @staticmethod
     def backward(ctx, g, _):
-        if g is None:
-            return None, None, None, None, None
-        holder = ctx.chart._wss
-        d = bracket_margin(ctx.chart, ctx.brackets, ctx.scalars[0], ctx.scalars[1], weights=g).d_split
-        slot = holder.split_cot
-        slot[0] = d if slot[0] is None else slot[0] + d
-        return torch.zeros(ctx.shape, dtype=torch.float32, device=d.device), None, None, None, None
+        return _hand_off(ctx, bracket_margin, weights=g)
 
 
 def _margin_node(diora, brackets, margin, penalty, who):
-    plan = diora._plan
-    if plan is None:
-        raise _lib.ChartLibError('%s: the module has run no forward' % who)
+    _refuse_no_forward(diora, who)
     margin, penalty = _check_margin(margin, penalty)
-    if plan.L > _lib.MAX_L:
-        raise _lib.ChartLibError('%s: L = %d > %d is inference only (the backward stops at %d words), so the loss has nothing to train '
-                                 'through' % (who, plan.L, _lib.MAX_L, _lib.MAX_L))
-    if getattr(diora, 'plan_arch', 0) != 0:
-        raise _lib.ChartLibError('%s: a TreeLSTM chart takes no cotangent on its split scores (cliora_lstm_backward has no such input)' % who)
-    holder = diora._wss
-    if len(holder) != 1 or getattr(holder, 'split_cot', None) is None:
-        raise _lib.ChartLibError('%s: the module holds %d workspaces that no single chart node owns; call it after each forward of its '
-                                 'own' % (who, len(holder)))
-    inside_s = diora.chart.inside_s
-    if not inside_s.requires_grad:
-        raise _lib.ChartLibError('%s: the forward kept no backward state (it ran under torch.no_grad(), in eval mode without gradients, '
-                                 'or on a padded chart); bracket_margin gives the value alone' % who)
-    return _BracketMarginLoss.apply(inside_s, diora, brackets, margin, penalty)
+    return _BracketMarginLoss.apply(_trainable(diora, who, 'loss', 'bracket_margin gives the value alone'), diora, brackets, margin, penalty)
 
 
 def bracket_margin_loss(diora, brackets, margin=1.0, penalty=float('inf')):
@@ -550,8 +474,7 @@ def bracket_hinge(diora, brackets, margin=1.0, penalty=float('inf'), reduction='
     """The max-margin loss over the feasible sentences -- under an infinite penalty those some tree qualifies for, under a finite one
     those without a bad row: their mean ('mean') or sum ('sum'), a 0-d tensor in the graph; 0 (with a graph) when there is none.
     Nothing is synchronised."""
-    if reduction not in ('mean', 'sum'):
-        raise ValueError("reduction must be 'mean' or 'sum'")
+    _check_reduction(reduction)
     loss, feasible = _margin_node(diora, brackets, margin, penalty, 'bracket_hinge')
     total = loss.sum()                                     # an infeasible or rejected sentence holds 0
     return total / feasible.sum().clamp(min=1).to(loss.dtype) if reduction == 'mean' else total
@@ -561,8 +484,6 @@ def bracket_violations(diora, brackets, lengths=None):
     """Per sentence, the number of constituents of the best (CKY) tree that cross a required bracket or equal a forbidden one -- against
     a full gold tree, its spans that are not in the gold tree: the margin = 0 call's violations.  -> (B,) int32 numpy array; one
     device-to-host copy; a rejected sentence raises."""
-    from .constrained import refuse_rejected
-    from .diora import host_copy
     res = bracket_margin(diora, brackets, margin=0.0, penalty=0.0, lengths=lengths)
     viol, status = host_copy(res.violations, res.status)
     refuse_rejected(int(status.sum()), 'cliora_bracket_margin')
@@ -580,19 +501,7 @@ def _best_tree(n, rel, leaf, bonus):
         cand = (val[k, pos] + val[level - k - 1, pos + k + 1]) + rel[level]        # (cells of the level, splits), fp32
         bp[level] = np.argmax(cand, axis=1)
         val[level, :n - level] = cand[np.arange(n - level), bp[level]] + bonus[level]
-    rows, stack = [], [(n - 1, 0, 0)] if n > 1 else []
-    while stack:                                      # the kernel's walk: left subtree, right subtree, then the node
-        level, pos, phase = stack.pop()
-        if level == 0:
-            continue
-        k = int(bp[level][pos])
-        if phase == 0:
-            stack += [(level, pos, 1), (k, pos, 0)]
-        elif phase == 1:
-            stack += [(level, pos, 2), (level - k - 1, pos + k + 1, 0)]
-        else:
-            rows.append((pos, pos + level, k))
-    return val[n - 1, 0], rows
+    return val[n - 1, 0], [row[:3] for row in walk(n, lambda level, pos, _: (bp[level][pos], None, None))]
 
 
 def bracket_margin_numpy(pair_s, lengths, brackets, margin, penalty, weights=None):
@@ -602,11 +511,7 @@ def bracket_margin_numpy(pair_s, lengths, brackets, margin, penalty, weights=Non
     -> BracketMargin of numpy arrays as the kernel writes them."""
     margin, penalty = _check_margin(margin, penalty)
     m32, p32, hard = np.float32(margin), np.float32(penalty), penalty == float('inf')
-    lengths = [int(x) for x in lengths]
-    Bn = len(lengths)
-    levels = sorted(int(lv) for lv in pair_s)
-    L = (max(levels) + 1) if levels else 1
-    brackets = np.zeros((Bn, 0, 3), dtype=np.int32) if brackets is None else np.asarray(brackets)
+    lengths, Bn, L, brackets = _sentences(pair_s, lengths, brackets)
     weights = np.ones(Bn) if weights is None else np.asarray(weights, dtype=np.float32).astype(np.float64)
     G = {level: np.zeros((Bn, L - level, level)) for level in range(1, L)}
     loss, aug, ref = np.zeros(Bn), np.zeros(Bn), np.zeros(Bn)
