@@ -103,6 +103,7 @@ ABI = {
     'cliora_bracket_grad': (i32, [vp, vp, vp, vp, i32] + [vp] * 6),
     'cliora_tree_expectation': (i32, [vp] * 12),
     'cliora_bracket_margin': (i32, [vp, vp, vp, vp, i32, f32, f32] + [vp] * 11),
+    'cliora_tree_kl': (i32, [vp] * 16),
     'cliora_ground_eval': (i32, [i32, i32, i32, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_ground_eval_ragged': (i32, [i32, i32, i32, vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8),
     'cliora_phrase_gather': (i32, [i32, i32, i32, vp, i64, i64, vp, i64, i64, i32, vp, i32, vp, i64, i64, vp, vp]),

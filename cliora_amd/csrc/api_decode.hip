@@ -4,7 +4,8 @@
 // kernel, kbest_kernels.hpp for the k-best lists, posterior_kernels.hpp for the sum-product model, sample_kernels.hpp for the draws
 // from it, constrained_kernels.hpp for the bracket mask over both, constrained_tree_kernels.hpp for the k-best lists and the draws
 // under that mask, bracket_grad_kernels.hpp for the gradient of its log-probability,
-// expectation_kernels.hpp for the expected cost, the entropy and their gradient, and margin_kernels.hpp for the max-margin losses.
+// expectation_kernels.hpp for the expected cost, the entropy and their gradient, margin_kernels.hpp for the max-margin losses, and
+// kl_kernels.hpp for the divergence between two charts' distributions.
 // TreeLSTM plans: their Sp rows are written by pair_scores_fwd in the same level geometry (api_lstm.hip), which every entry relies on.
 #include <cmath>
 
@@ -15,6 +16,7 @@
 #include "decode_kernels.hpp"
 #include "expectation_kernels.hpp"
 #include "kbest_kernels.hpp"
+#include "kl_kernels.hpp"
 #include "margin_kernels.hpp"
 #include "posterior_kernels.hpp"
 #include "sample_kernels.hpp"
@@ -279,4 +281,39 @@ extern "C" int cliora_bracket_margin(cliora_plan* plan, void* fwd_ws, const int3
                              return go("bracket_margin_kernel", bracket_margin_kernel, brackets, M, margin, penalty, weights, d_split, loss_out,
                                        aug_score_out, ref_score_out, violations_out, feasible_out, spans_aug, spans_ref);
                          });
+}
+
+// The one entry over TWO charts (kl_kernels.hpp), so it does not go through launch_decode: the teacher's and the student's plan, of
+// the same B and L, each with its forward workspace.  With d_split_p the tables take 114.1 KiB at L 64, without it 81.6 KiB: no
+// scratch, no query.  A long plan has no backward to hand the gradient to, so there is no LONG instance.
+extern "C" int cliora_tree_kl(cliora_plan* plan_p, void* fwd_ws_p, cliora_plan* plan_q, void* fwd_ws_q, const int32_t* lengths,
+                              const float* w_kl, const float* w_ce, float* d_split_p, float* d_split_q, float* kl_out,
+                              float* cross_entropy_out, float* entropy_p_out, float* log_z_p_out, float* log_z_q_out, int32_t* status,
+                              void* stream) {
+    if (!plan_p || !fwd_ws_p || !plan_q || !fwd_ws_q || !kl_out || !cross_entropy_out || !entropy_p_out || !log_z_p_out || !log_z_q_out ||
+        !status)
+        return fail(CLIORA_EINVAL, "cliora_tree_kl: NULL argument");
+    const Plan& p = plan_p->p;
+    const Plan& q = plan_q->p;
+    if (p.is_long() || q.is_long())
+        return fail(CLIORA_EINVAL, "cliora_tree_kl: L > 64 is forward only (the backward stops at 64 words, so nothing could take the gradient)");
+    if (p.B != q.B || p.L != q.L)
+        return fail(CLIORA_EINVAL, "cliora_tree_kl: the two plans differ in B or L (teacher B " + std::to_string(p.B) + " L " + std::to_string(p.L) +
+                                       ", student B " + std::to_string(q.B) + " L " + std::to_string(q.L) + ")");
+    if (!plan_p->uploaded || !plan_q->uploaded) return fail(CLIORA_EINVAL, "cliora_tree_kl: called before forward");
+    hipStream_t st = (hipStream_t)stream;
+    OKR(cliora_plan_ready(plan_p, st));
+    OKR(cliora_plan_ready(plan_q, st));
+    HIPOK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    const float* sp_p = (const float*)fwd_ws_p + p.fwd.sp;
+    const float* sp_q = (const float*)fwd_ws_q + q.fwd.sp;
+    auto go = [&](auto* kernel, bool tg) -> int {
+        const size_t lds = KlLds{p.L, p.C, tg}.total;
+        if (lds > 64 * 1024) OKR(cliora_ensure_max_lds((const void*)kernel));
+        hipLaunchKernelGGL(kernel, dim3(p.B), dim3(POST_WAVES * 64), lds, st, p.L, p.C, p.d_tables + p.dev.lvl_base_in, p.B, sp_p, sp_q, lengths,
+                           status, w_kl, w_ce, d_split_p, d_split_q, kl_out, cross_entropy_out, entropy_p_out, log_z_p_out, log_z_q_out);
+        LAUNCHOK("tree_kl_kernel");
+        return CLIORA_OK;
+    };
+    return d_split_p ? go(tree_kl_kernel<true>, true) : go(tree_kl_kernel<false>, false);
 }

@@ -824,6 +824,20 @@ class DioraBase(nn.Module):
         from . import structured
         return structured.expected_cost(self, cost, reduction=reduction)
 
+    def parse_kl(self, teacher):
+        """(kl, cross_entropy) of this chart's distribution over parses against the one of `teacher` -- any chart module after a
+        forward on the same sentences (same B and L) --, two (B,) tensors in the autograd graph of the last forward
+        (cliora_amd.structured.parse_kl): KL(teacher || self) and -sum_T p_teacher(T) log p_self(T).  A teacher
+        whose forward kept backward state gets its gradient too.  Nothing is synchronised."""
+        from . import structured
+        return structured.parse_kl(teacher, self)
+
+    def parse_divergence(self, teacher, direction='forward', reduction='mean'):
+        """The divergence from `teacher`'s distribution over parses, its mean (or 'sum') over the batch: a 0-d tensor in the graph.
+        direction 'forward': KL(teacher || self); 'reverse': KL(self || teacher); 'symmetric': their sum."""
+        from . import structured
+        return structured.parse_divergence(teacher, self, direction=direction, reduction=reduction)
+
 
 class DioraMLP(DioraBase):
     def __init__(self, *args, hard=False, **kwargs):

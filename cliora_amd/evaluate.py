@@ -421,3 +421,79 @@ def evaluate_ragged(net, examples, idx2word, out_path=None, postprocess=False, m
                     f.write(line + '\n')
     m = {k: v for k, v in ev.result().items() if k in METRICS[:4]}
     return (m, details) if return_details else m
+
+
+def _inside_only(nets):
+    """Context of chart_divergence: every net in eval mode with its outside pass off; modes and flags restored on exit."""
+    import contextlib
+
+    @contextlib.contextmanager
+    def cm():
+        was = [(n.training, n.diora.outside) for n in nets]
+        try:
+            for n in nets:
+                n.eval()
+                n.diora.outside = False
+            with torch.no_grad():
+                yield
+        finally:
+            for n, (training, outside) in zip(nets, was):
+                n.diora.outside = outside
+                n.train(training)
+    return cm()
+
+
+def _divergence_result(ab, ba):
+    ab, ba = (np.concatenate(v) if v else np.zeros(0, dtype=np.float32) for v in (ab, ba))
+    return dict(kl_ab=float(ab.mean()) if ab.size else 0.0, kl_ba=float(ba.mean()) if ba.size else 0.0, per_sentence_ab=ab, per_sentence_ba=ba)
+
+
+def _pair_divergence(a, b, ab, ba, lengths=None):
+    """KL(a || b) and KL(b || a) of two chart modules after their forwards, appended per sentence; one device-to-host copy."""
+    from .query import host_copy
+    from .structured import tree_kl
+    r1 = tree_kl(a, b, lengths=lengths, student_grad=False)
+    r2 = tree_kl(b, a, lengths=lengths, student_grad=False)
+    k1, k2, s1, s2 = host_copy(r1.kl, r2.kl, r1.status, r2.status)
+    if int(s1.sum()) or int(s2.sum()):
+        raise _lib.ChartLibError('cliora_tree_kl rejected %d sentence length(s)' % max(int(s1.sum()), int(s2.sum())))
+    ab.append(k1.copy())
+    ba.append(k2.copy())
+
+
+def chart_divergence(net_a, net_b, batches):
+    """How far two nets' parse distributions lie apart on the same batches (cliora_amd.structured.tree_kl):
+    both nets run their inside pass in eval mode under no_grad on each batch_map ('sentences', and 'obj_feats' for a net with
+    regions), then KL(a || b) and KL(b || a) per sentence -- two launches and ONE device-to-host copy per batch.  The nets may differ
+    in width, regions, weight sharing, soft or hard; batches of one length each, up to 64 words.
+    -> dict(kl_ab, kl_ba: the means over all sentences; per_sentence_ab, per_sentence_ba: fp32 arrays in the batches' order)."""
+    ab, ba = [], []
+    with _inside_only((net_a, net_b)):
+        for bm in batches:
+            for net in (net_a, net_b):
+                dev = next(net.parameters()).device
+                obj = bm.get('obj_feats') if net.obj_feats else None
+                net(bm['sentences'].to(dev), obj.to(dev) if obj is not None else None, None, compute_loss=False)
+            _pair_divergence(net_a.diora, net_b.diora, ab, ba)
+    return _divergence_result(ab, ba)
+
+
+def chart_divergence_ragged(net_a, net_b, sentences, obj_feats=None, max_batch=64, max_waste=None, pad_id=0):
+    """``chart_divergence`` for sentences of any lengths in 1..64, given in any order: they are packed into right-padded charts
+    (cliora_amd.ragged.pack), both nets run the inside pass of each pack -- prefix-closed, so each sentence's own triangle holds its
+    own scores -- and the divergence reads each triangle through the pack's lengths.  obj_feats: (N, R, img_dim) for the nets that
+    have regions.  The per-sentence arrays come back in the caller's order."""
+    from . import ragged
+    lengths = ragged._check_batch(net_a, sentences, obj_feats if net_a.obj_feats else None, ragged.MAX_L, 'inside')[1]
+    ragged._check_batch(net_b, sentences, obj_feats if net_b.obj_feats else None, ragged.MAX_L, 'inside')
+    ab, ba, order = [], [], []
+    with _inside_only((net_a, net_b)):
+        for idx in (ragged.pack(lengths, max_batch, ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste) if lengths else ()):
+            for net in (net_a, net_b):
+                _, lens = next(ragged._forward_packs(net, sentences, lengths, [idx], pad_id, obj_feats if net.obj_feats else None, None))
+            _pair_divergence(net_a.diora, net_b.diora, ab, ba, lengths=lens)
+            order += list(idx)
+    res = _divergence_result(ab, ba)
+    back = np.argsort(np.asarray(order, dtype=np.int64), kind='stable')
+    res['per_sentence_ab'], res['per_sentence_ba'] = res['per_sentence_ab'][back], res['per_sentence_ba'][back]
+    return res

@@ -306,9 +306,18 @@ class LossDict(dict):
 
 class Net(nn.Module):
     def __init__(self, embed, image_encoder, diora, obj_feats, loss_funcs=(), bracket_loss_weight=0.0, risk_loss_weight=0.0,
-                 entropy_loss_weight=0.0, hinge_loss_weight=0.0, hinge_margin=1.0, hinge_penalty=float('inf')):
+                 entropy_loss_weight=0.0, hinge_loss_weight=0.0, hinge_margin=1.0, hinge_penalty=float('inf'), teacher=None,
+                 kl_loss_weight=0.0, kl_direction='forward'):
         super().__init__()
         self.obj_feats = obj_feats
+        # != 0 with a teacher: a training step adds weight * parse_divergence(teacher, self.diora, kl_direction).
+        # The teacher is a chart module of this net's width (a CLIORA one needs a net with regions) that is NOT a submodule: its
+        # parameters are in no optimizer and no state_dict of the net, and net.train() never reaches it.  Each step runs its inside
+        # pass alone on the net's own x_span, under no_grad.
+        if kl_direction not in ('forward', 'reverse', 'symmetric'):
+            raise ValueError("kl_direction must be 'forward', 'reverse' or 'symmetric'")
+        self.__dict__['teacher'] = teacher
+        self.kl_loss_weight, self.kl_direction = float(kl_loss_weight), kl_direction
         # > 0: a batch that carries entity_labels adds weight * bracket_nll of its annotated phrases (cliora_amd.structured) to the total
         self.bracket_loss_weight = float(bracket_loss_weight)
         # > 0: such a batch adds weight * the mean expected cost under span_costs of ALL its phrases, crossing ones included (minus the
@@ -363,6 +372,8 @@ class Net(nn.Module):
         finally:                        # per call: a later direct call of the chart module must not inherit them
             if flags:
                 self.diora.word_lane, self.diora.word_inputs_on_lane = None, False
+        if compute_loss and self.uses_teacher():
+            self.run_teacher(x_span, x_word, o_span, o_word)
         if not compute_loss:
             return {'total_loss': torch.ones(1, 1, device=x_span.device)}
         ret, parts = LossDict(), []
@@ -382,9 +393,31 @@ class Net(nn.Module):
         ret.parts = parts
         return ret
 
+    def uses_teacher(self):
+        """Whether this step adds the divergence from the teacher: a training step of a net with a teacher and a weight."""
+        return self.kl_loss_weight != 0 and self.teacher is not None and self.training and torch.is_grad_enabled()
+
+    def run_teacher(self, x_span, x_word=None, o_span=None, o_word=None):
+        """The teacher's inside pass alone on the chart inputs of this net's own forward (detached), under no_grad, in the mode the
+        teacher is in; regions only for a teacher that takes them.  A padded pack runs the same way: the inside pass is prefix-closed."""
+        from .cliora import DioraMLP as VLDiora
+        teacher = self.teacher
+        vl = isinstance(teacher, VLDiora)
+        if vl and o_span is None:
+            raise ValueError('a CLIORA teacher needs a net with regions (obj_feats)')
+        det = lambda t: t.detach() if t is not None else None
+        had_outside = teacher.outside
+        teacher.outside = False
+        try:
+            with torch.no_grad():
+                teacher(det(x_span), det(x_word), *((det(o_span), det(o_word)) if vl else ()))
+        finally:
+            teacher.outside = had_outside
+
     def structured_losses(self, entity_labels, L, device):
         """The weighted structured terms of the chart self.diora holds (cliora_amd.structured), as (name, 0-d tensor) in the order they
-        join the total: bracket_nll, hinge and risk for a batch that carries entity_labels, entropy for a training step.  L: the chart's length."""
+        join the total: bracket_nll, hinge and risk for a batch that carries entity_labels, entropy for a training step, kl for a
+        training step of a net with a teacher (whose forward on the same inputs has run: ``run_teacher``).  L: the chart's length."""
         out = []
         if entity_labels is not None and self.bracket_loss_weight > 0:
             from .constrained import brackets_from_entity_labels
@@ -406,6 +439,8 @@ class Net(nn.Module):
                 out.append(('risk', self.risk_loss_weight * risk.mean()))
             if use_entropy:
                 out.append(('entropy', self.entropy_loss_weight * entropy.mean()))
+        if self.uses_teacher():
+            out.append(('kl', self.kl_loss_weight * self.diora.parse_divergence(self.teacher, direction=self.kl_direction)))
         return out
 
 
@@ -427,10 +462,11 @@ def select_diora(arch, obj_feats):
 def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=True, normalize='unit',
               vg_loss=False, use_contr=False, vl_margin=0.2, alpha_contr=1.0, alpha_vg=1.0, arch='mlp', bracket_loss_weight=0.0,
               risk_loss_weight=0.0, entropy_loss_weight=0.0, full_softmax=False, hard=False, hinge_loss_weight=0.0, hinge_margin=1.0,
-              hinge_penalty=float('inf')):
+              hinge_penalty=float('inf'), teacher=None, kl_loss_weight=0.0, kl_direction='forward'):
     """What trainer.py:504-582 assembles, on the native chart modules.  full_softmax: the reconstruction loss is the exact one over the
     whole table (ReconstructionSoftmaxLoss(full_vocab=True)) instead of the reference's sampled loss.  hard: the chart module encodes
-    every cell's single best split (S-DIORA, `--arch hard` of the reference's training script; text-only DioraMLP)."""
+    every cell's single best split (S-DIORA, `--arch hard` of the reference's training script; text-only DioraMLP).  teacher,
+    kl_loss_weight, kl_direction: Net's -- a frozen chart module whose parse distribution each training step is pulled towards."""
     embed = Embed(embeddings, embeddings.weight.shape[1], size)
     enc = ImageEncoder(img_dim, size)
     diora = select_diora(arch, obj_feats)(size, outside=True, normalize=normalize, compress=False, share=share)
@@ -445,7 +481,7 @@ def build_net(size, embeddings, obj_feats=False, img_dim=2048, k_neg=100, share=
         embeddings.weight.requires_grad = False              # trainer.py:541
     return Net(embed, enc, diora, obj_feats, losses, bracket_loss_weight=bracket_loss_weight, risk_loss_weight=risk_loss_weight,
                entropy_loss_weight=entropy_loss_weight, hinge_loss_weight=hinge_loss_weight, hinge_margin=hinge_margin,
-               hinge_penalty=hinge_penalty)
+               hinge_penalty=hinge_penalty, teacher=teacher, kl_loss_weight=kl_loss_weight, kl_direction=kl_direction)
 
 
 class Trainer(object):
@@ -545,21 +581,32 @@ class Trainer(object):
             neg_samples = self.negative_sampler.sample(self.k_neg)
         n_tokens, n_sentences = float(sum(len(s) for s in sentences)), float(len(sentences))
         total = None
-        with torch.enable_grad():
-            for idx, lens, diora in ragged.forward_ragged_train(net, sentences, max_batch=max_batch, pad_id=pad_id, obj_feats=obj_feats,
-                                                                max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste):
-                group = [sentences[i] for i in idx]
-                labels = [entity_labels[i] for i in idx] if entity_labels is not None else None
-                part = ragged.reconstruction_loss_ragged(net, group, neg_samples, diora)
-                for _, v in net.structured_losses(labels, diora._plan.L, part.device):      # each sentence's own triangle (the holder's lengths)
-                    part = part + v
-                part = part * (sum(len(s) for s in group) / n_tokens)
-                for name in net.loss_func_names:
-                    if 'contrastive' in name:
-                        part = part + getattr(net, name)(diora, lens) * (len(idx) / n_sentences)
-                    elif 'reconstruct' not in name:
-                        part = part + getattr(net, name)(diora.vg_atten_score, lens) * (len(idx) / n_sentences)
-                total = part if total is None else total + part
+        # a net with a teacher: the teacher runs on each pack's own chart inputs, taken as the pack's forward receives them
+        seen, hook = [], None
+        if net.kl_loss_weight != 0 and net.teacher is not None:
+            hook = net.diora.register_forward_pre_hook(lambda _, args: seen.append(args))
+        try:
+            with torch.enable_grad():
+                for idx, lens, diora in ragged.forward_ragged_train(net, sentences, max_batch=max_batch, pad_id=pad_id, obj_feats=obj_feats,
+                                                                    max_waste=ragged.DEFAULT_MAX_WASTE if max_waste is None else max_waste):
+                    group = [sentences[i] for i in idx]
+                    labels = [entity_labels[i] for i in idx] if entity_labels is not None else None
+                    part = ragged.reconstruction_loss_ragged(net, group, neg_samples, diora)
+                    if hook is not None:                  # inside pass alone on the padded pack; the student's holder has the lengths
+                        net.run_teacher(*seen[-1])
+                        del seen[:]
+                    for _, v in net.structured_losses(labels, diora._plan.L, part.device):      # each sentence's own triangle (the holder's lengths)
+                        part = part + v
+                    part = part * (sum(len(s) for s in group) / n_tokens)
+                    for name in net.loss_func_names:
+                        if 'contrastive' in name:
+                            part = part + getattr(net, name)(diora, lens) * (len(idx) / n_sentences)
+                        elif 'reconstruct' not in name:
+                            part = part + getattr(net, name)(diora.vg_atten_score, lens) * (len(idx) / n_sentences)
+                    total = part if total is None else total + part
+        finally:
+            if hook is not None:
+                hook.remove()
         if total is None:
             raise ValueError('step_ragged: no sentence')
         self._backward_and_update(total)

@@ -1,7 +1,7 @@
 """After-forward chart queries: the one launcher of their C entries, and the one host walk of their restatements.
 
 Every question asked of a chart after its forward -- the best tree of a padded chart, the posteriors, the K best trees, samples, the
-constrained forms, the bracket gradient, the expectation, the margin loss -- is one C entry of include/cliora_chart.h that starts
+constrained forms, the bracket gradient, the expectation, the margin loss, the divergence from a second chart -- is one C entry of include/cliora_chart.h that starts
 (plan, forward workspace, ...) and ends (..., status, stream), called once per forward workspace of the chart module on that
 workspace's B sentences.  ``ChartQuery`` is what such a call reads of the module, the checks of the per-sentence arguments and the
 loop over the workspaces; a query is its checks, its output allocations, one ``launch`` and its result tuple.
@@ -40,6 +40,17 @@ class per_workspace(object):
         return C.c_void_p(self.t.data_ptr() + self.t.element_size() * i * self.count)
 
 
+class workspace_of(object):
+    """The forward workspace of a SECOND chart among a launch's arguments (``ChartQuery.second``): workspace i of its holder."""
+    __slots__ = ('q',)
+
+    def __init__(self, q):
+        self.q = q
+
+    def at(self, i, sl):
+        return C.c_void_p(self.q.parts[i][0].data_ptr())
+
+
 class ChartQuery(object):
     """What an after-forward query reads of a chart module (anything that carries `_plan` and `_wss`): plan, parts -- per forward
     workspace (workspace, the slice of its B sentences in the module's outputs) --, nws, rows = B * nws, dev, and holder, the module's
@@ -51,6 +62,15 @@ class ChartQuery(object):
         B = plan.B
         self.plan, self.holder, self.nws, self.rows, self.dev = plan, wss, len(wss), B * len(wss), wss[0].device
         self.parts = [(ws, slice(i * B, (i + 1) * B)) for i, ws in enumerate(wss)]
+
+    def second(self, other, who):
+        """The arguments that name a second chart in this query's launch: -> (its plan handle, ``workspace_of`` it).  The two charts
+        must agree in B, L, the number of workspaces and the device -- then their slices agree too; refused before any device call."""
+        a, b = self.plan, other.plan
+        if (a.B, a.L, self.nws, self.dev) != (b.B, b.L, other.nws, other.dev):
+            raise ValueError('%s: the two charts differ: B %d L %d, %d workspace(s) on %s against B %d L %d, %d workspace(s) on %s'
+                             % (who, a.B, a.L, self.nws, self.dev, b.B, b.L, other.nws, other.dev))
+        return b.handle, workspace_of(other)
 
     def lengths_or_holders(self, lengths):
         """The default of the structured queries: the lengths of a padded training chart of mixed lengths, each sentence's own triangle."""
@@ -119,11 +139,11 @@ class ChartQuery(object):
 
     def launch(self, entry, *args, status=None):
         """The loop over the workspaces: `entry`(plan, workspace i, *args, [status word i,] stream) under the chart's device.  args,
-        in the entry's ABI order: ``per_sentence(t)`` a per-sentence tensor, ``per_workspace(t, count)``, a tensor as it is (scratch: NULL
-        for None and for an empty one), anything else a plain scalar."""
+        in the entry's ABI order: ``per_sentence(t)`` a per-sentence tensor, ``per_workspace(t, count)``, ``workspace_of(q)`` (a second
+        chart: ``second``), a tensor as it is (scratch: NULL for None and for an empty one), anything else a plain scalar."""
         with torch.cuda.device(self.dev):
             for i, (ws, sl) in enumerate(self.parts):
-                call = [a.at(i, sl) if isinstance(a, (per_sentence, per_workspace)) else _p(a) if torch.is_tensor(a) else a for a in args]
+                call = [a.at(i, sl) if isinstance(a, (per_sentence, per_workspace, workspace_of)) else _p(a) if torch.is_tensor(a) else a for a in args]
                 if status is not None:
                     call.append(C.c_void_p(status[i:i + 1].data_ptr()))
                 _lib.call(entry, self.plan.handle, C.c_void_p(ws.data_ptr()), *call, _stream())

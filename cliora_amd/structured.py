@@ -32,6 +32,10 @@ expected value of a per-cell cost and the entropy of the distribution over trees
 
 The third part is the max-margin family over the same potentials (cliora_bracket_margin): structured hinge,
 perceptron and ramp losses, ``bracket_hinge``, whose subgradient -- a difference of two trees -- takes the same hand-off.
+
+The fourth part compares TWO charts over the same sentences (cliora_tree_kl): the divergence KL(p || q) between
+their distributions over trees and the cross-entropy, ``parse_kl`` / ``parse_divergence``, whose two gradients take the hand-off of
+each chart's own forward.
 """
 import collections
 
@@ -569,3 +573,184 @@ def bracket_margin_numpy(pair_s, lengths, brackets, margin, penalty, weights=Non
             G[level][b] *= weights[b]
             G[level][b][G[level][b] == 0] = 0.0       # +0 whatever the weight
     return BracketMargin(G, loss, aug, ref, viol, feasible, sp_a, sp_r, status)
+
+
+# ---- two charts: the divergence between their parse distributions (cliora_tree_kl) -----------------------------
+# Teacher p and student q are two chart modules after a forward on the same sentences (same B and L; width, regions, weight sharing,
+# soft or hard may differ: only the split scores are read).  kl = KL(p || q) = sum_T p(T) log(p(T) / q(T)), cross_entropy =
+# -sum_T p(T) log q(T), entropy_p their difference.  The student's gradient is a difference of edge marginals, the teacher's a
+# covariance under p (csrc/kl_kernels.hpp); each reaches its own chart through the slot of that chart's forward, into which it ADDS.
+#
+#     teacher.eval(); with torch.no_grad(): teacher(x_span)               # any forward: eval, no_grad, hard, CLIORA, another width
+#     net.diora(x_span, x_word)                                            # the student's training forward
+#     loss = recon + 0.5 * net.diora.parse_divergence(teacher)             # or parse_divergence(teacher, net.diora)
+#
+# d_split_p (None without teacher_grad), d_split_q (cliora_plan_split_score_count * workspaces,) fp32; kl, cross_entropy, entropy_p,
+# log_z_p, log_z_q (B,) fp32; status (number of workspaces,) int32.  Device tensors; nothing is synchronised.  (tree_kl_numpy: the
+# same fields as numpy arrays, the gradients {level: (B, L - level, level)} and the scalars in fp64, status an int.)
+TreeKL = collections.namedtuple('TreeKL', 'd_split_p d_split_q kl cross_entropy entropy_p log_z_p log_z_q status')
+
+
+def tree_kl(teacher, student, w_kl=None, w_ce=None, lengths=None, teacher_grad=False, student_grad=True):
+    """cliora_tree_kl on two chart modules after their forwards (any forward: this call needs no backward state).  w_kl: fp32 (B,)
+    or None = 1; w_ce: fp32 (B,) or None = 0; lengths: int32 (B,) or None = the lengths of the student's padded training chart, else
+    of the teacher's.  d_split_q = d (w_kl kl + w_ce cross_entropy) / d s^q, d_split_p the same with respect to s^p -- formed only
+    with teacher_grad (student_grad) --, one buffer per workspace, back to back.  -> TreeKL of device tensors; nothing is synchronised."""
+    _refuse_no_forward(teacher, 'tree_kl (teacher)')
+    _refuse_no_forward(student, 'tree_kl (student)')
+    q, qs = ChartQuery(teacher), ChartQuery(student)
+    handle, ws = q.second(qs, 'tree_kl')
+    if lengths is None:
+        lengths = qs.lengths_or_holders(None)
+        lengths = q.lengths_or_holders(None) if lengths is None else lengths
+    q.check_int32('lengths', lengths)
+    q.check_weights('w_kl', w_kl)
+    q.check_weights('w_ce', w_ce)
+    p_arg, d_split_p = q.split_buffer() if teacher_grad else (None, None)
+    q_arg, d_split_q = q.split_buffer() if student_grad else (None, None)
+    kl, ce, ent, lzp, lzq = (q.empty(torch.float32) for _ in range(5))
+    status = q.status()
+    q.launch('cliora_tree_kl', handle, ws, per_sentence(q.moved(lengths)), per_sentence(q.moved_weights(w_kl)),
+             per_sentence(q.moved_weights(w_ce)), p_arg, q_arg, per_sentence(kl), per_sentence(ce), per_sentence(ent), per_sentence(lzp),
+             per_sentence(lzq), status=status)
+    return TreeKL(d_split_p, d_split_q, kl, ce, ent, lzp, lzq, status)
+
+
+def _keeps_backward_state(diora):
+    """Whether the last forward of `diora` can take a cotangent on its split scores: what ``_trainable`` demands, as a question."""
+    plan, holder = diora._plan, getattr(diora, '_wss', None)
+    return (plan is not None and plan.L <= _lib.MAX_L and getattr(diora, 'plan_arch', 0) == 0 and holder is not None and len(holder) == 1
+            and getattr(holder, 'split_cot', None) is not None and diora.chart.inside_s.requires_grad)
+
+
+class _ParseKL(torch.autograd.Function):
+    """(kl, cross_entropy) as functions of the two charts (formally: of the inside_s of each chart that kept backward state, as
+    _BracketLogProb).  in_p / in_q: that chart's inside_s, or None for a chart that takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, teacher, student, in_p, in_q):
+        ctx.charts = _ChartView(teacher._plan, teacher._wss), _ChartView(student._plan, student._wss)
+        ctx.shapes = tuple(None if t is None else t.shape for t in (in_p, in_q))
+        ctx.set_materialize_grads(False)
+        res = tree_kl(teacher, student, student_grad=False)
+        return res.kl, res.cross_entropy
+
+    @staticmethod
+    def backward(ctx, g_kl, g_ce):
+        some = g_kl if g_kl is not None else g_ce
+        if some is None:
+            return None, None, None, None
+        zeros = torch.zeros_like(some)
+        res = tree_kl(*ctx.charts, w_kl=zeros if g_kl is None else g_kl, w_ce=zeros if g_ce is None else g_ce,
+                      teacher_grad=ctx.shapes[0] is not None, student_grad=ctx.shapes[1] is not None)
+        out = []
+        for chart, shape, d in zip(ctx.charts, ctx.shapes, (res.d_split_p, res.d_split_q)):
+            if shape is None:
+                out.append(None)
+                continue
+            slot = chart._wss.split_cot
+            slot[0] = d if slot[0] is None else slot[0] + d
+            out.append(torch.zeros(shape, dtype=torch.float32, device=d.device))
+        return (None, None) + tuple(out)
+
+
+def _kl_node(p, q):
+    """(kl, cross_entropy) of KL(p || q) in the graph of every one of the two charts that kept backward state (at least one does)."""
+    ins = [m.chart.inside_s if _keeps_backward_state(m) else None for m in (p, q)]
+    return _ParseKL.apply(p, q, *ins)
+
+
+def parse_kl(teacher, student):
+    """(kl, cross_entropy), two (B,) fp32 tensors in the autograd graph of the last forward of `student` -- and of `teacher`, when
+    its forward kept backward state too: KL(p || q) and -sum_T p(T) log q(T), p the teacher's distribution over trees, q the
+    student's.  One node; its backward launches the kernel once with the cotangents as weights and ADDS each gradient into the slot of
+    its own chart's forward, so the loss sums with ``bracket_log_prob``, ``tree_objective``, ``bracket_hinge`` and a second call.  The
+    student's refusals are ``bracket_log_prob``'s; the teacher may be any chart with a forward of the same B and L."""
+    _refuse_no_forward(teacher, 'parse_kl (teacher)')
+    _trainable(student, 'parse_kl', 'divergence', 'tree_kl gives the values alone')
+    return _kl_node(teacher, student)
+
+
+def parse_divergence(teacher, student, direction='forward', reduction='mean'):
+    """The divergence between the two parse distributions over the batch, a 0-d tensor in the graph: its mean ('mean') or sum ('sum').
+    direction 'forward': KL(teacher || student), what distillation minimises; 'reverse': KL(student || teacher), the roles swapped
+    (mode seeking); 'symmetric': their sum, in two launches.  The refusals are ``parse_kl``'s, for the student in every direction."""
+    if direction not in ('forward', 'reverse', 'symmetric'):
+        raise ValueError("direction must be 'forward', 'reverse' or 'symmetric'")
+    _check_reduction(reduction)
+    _refuse_no_forward(teacher, 'parse_divergence (teacher)')
+    _trainable(student, 'parse_divergence', 'divergence', 'tree_kl gives the values alone')
+    total = None
+    for p, q in {'forward': ((teacher, student),), 'reverse': ((student, teacher),),
+                 'symmetric': ((teacher, student), (student, teacher))}[direction]:
+        kl = _kl_node(p, q)[0]
+        total = kl if total is None else total + kl
+    return _reduce(total, reduction)
+
+
+def tree_kl_numpy(pair_s_p, pair_s_q, lengths, w_kl=None, w_ce=None):
+    """cliora_tree_kl restated in fp64 from the definitions (tests): `pair_s_p[level]`, `pair_s_q[level]` (B, L - level, level[, 1])
+    the per-split inside scores of the teacher's and the student's (padded) chart, sentence b its first lengths[b] words; w_kl (B,) or
+    None = 1; w_ce (B,) or None = 0.  -> TreeKL of numpy arrays, both gradients given, zeros for a bad length (counted in status).
+
+    In another form than the kernel, as ``tree_expectation_numpy``: the linear domain, with no logarithm but the two log_z.  Under p a
+    cell carries the pair (Z, Zv) of the expectation semiring with the edge value v = w_kl r^p - (w_kl + w_ce) r^q, under q the plain
+    Z; the outside values (O, Ov) and O_q are pushed from every parent to its two children."""
+    lengths, Bn, L, _ = _sentences(pair_s_p, lengths)
+    w_kl = np.ones(Bn) if w_kl is None else np.asarray(w_kl, dtype=np.float64)
+    w_ce = np.zeros(Bn) if w_ce is None else np.asarray(w_ce, dtype=np.float64)
+    Gp, Gq = ({level: np.zeros((Bn, L - level, level)) for level in range(1, L)} for _ in range(2))
+    kl, ce, ent, lzp, lzq, status = np.zeros(Bn), np.zeros(Bn), np.zeros(Bn), np.zeros(Bn), np.zeros(Bn), 0
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= L:
+            status += 1
+            continue
+        wk, wsum = w_kl[b], w_kl[b] + w_ce[b]
+        sp, sq, rp, rq, wp, wq, v = {}, {}, {}, {}, {}, {}, {}
+        for level in range(1, n):
+            sp[level] = np.asarray(pair_s_p[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
+            sq[level] = np.asarray(pair_s_q[level][b], dtype=np.float64).reshape(-1, level)[:n - level]
+            rp[level] = sp[level] - sp[level].max(axis=1, keepdims=True)
+            rq[level] = sq[level] - sq[level].max(axis=1, keepdims=True)
+            wp[level], wq[level] = np.exp(rp[level]), np.exp(rq[level])
+            v[level] = wk * rp[level] - wsum * rq[level]
+        Z, Zv, Y = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))          # Y: the student's Z
+        Z[0, :n], Y[0, :n] = 1.0, 1.0
+        edge, edge_v, edge_q = {}, {}, {}
+        for level in range(1, n):
+            k, pos = np.arange(level)[None, :], np.arange(n - level)[:, None]
+            left, right = (k, pos), (level - k - 1, pos + k + 1)
+            edge[level] = Z[left] * Z[right] * wp[level]
+            edge_v[level] = (Zv[left] * Z[right] + Z[left] * Zv[right]) * wp[level] + edge[level] * v[level]
+            edge_q[level] = Y[left] * Y[right] * wq[level]
+            Z[level, :n - level], Zv[level, :n - level] = edge[level].sum(axis=1), edge_v[level].sum(axis=1)
+            Y[level, :n - level] = edge_q[level].sum(axis=1)
+        O, Ov, Oq = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
+        O[n - 1, 0] = Oq[n - 1, 0] = 1.0
+        for level in range(n - 1, 0, -1):
+            k = np.arange(level)
+            for pos in range(n - level):
+                left, right = (k, pos), (level - k - 1, pos + k + 1)
+                o = O[level, pos] * wp[level][pos]
+                ov = Ov[level, pos] * wp[level][pos] + o * v[level][pos]
+                oq = Oq[level, pos] * wq[level][pos]
+                O[left], Ov[left], Oq[left] = O[left] + o * Z[right], Ov[left] + ov * Z[right] + o * Zv[right], Oq[left] + oq * Y[right]
+                O[right], Ov[right], Oq[right] = O[right] + o * Z[left], Ov[right] + ov * Z[left] + o * Zv[left], Oq[right] + oq * Y[left]
+        total, total_q = Z[n - 1, 0], Y[n - 1, 0]
+        mean_v = Zv[n - 1, 0] / total
+        lzp[b], lzq[b] = np.log(total), np.log(total_q)
+        mean_rp = mean_rq = 0.0
+        for level in range(1, n):
+            o, ov, oq = O[level, :n - level, None], Ov[level, :n - level, None], Oq[level, :n - level, None]
+            nu, nu_q = o * edge[level] / total, oq * edge_q[level] / total_q
+            dp = (ov * edge[level] + o * edge_v[level]) / total - nu * mean_v
+            dq = wsum * (nu_q - nu)
+            mean_rp += float((nu * rp[level]).sum())
+            mean_rq += float((nu * rq[level]).sum())
+            rows = np.arange(n - level)
+            dp[rows, np.argmax(sp[level], axis=1)] -= dp.sum(axis=1)
+            dq[rows, np.argmax(sq[level], axis=1)] -= dq.sum(axis=1)
+            Gp[level][b, :n - level], Gq[level][b, :n - level] = dp, dq
+        ent[b], ce[b] = lzp[b] - mean_rp, lzq[b] - mean_rq
+        kl[b] = ce[b] - ent[b]
+    return TreeKL(Gp, Gq, kl, ce, ent, lzp, lzq, status)

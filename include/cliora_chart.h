@@ -658,6 +658,40 @@ int cliora_bracket_margin(cliora_plan* plan, void* fwd_workspace, const int32_t*
                           float penalty, const float* weights, float* d_split, float* loss_out, float* aug_score_out,
                           float* ref_score_out, int32_t* violations_out, int32_t* feasible_out, int32_t* spans_aug, int32_t* spans_ref,
                           int32_t* status, void* stream);
+/* The divergence between TWO charts' distributions over binary trees, with both gradients.  Teacher P =
+ * (plan_p, fwd_workspace_p) with split scores s^p, student Q = (plan_q, fwd_workspace_q) with s^q: two plans of the same B and L whose
+ * forward has run; D, R, weight sharing, soft or hard, MLP or TreeLSTM may differ -- only the split scores are read.  With
+ * r^x[cell, k] = s^x[cell, k] - max_k s^x[cell, .], a tree weighing exp(sum of r^x over its internal cells) under chart x, R^x(T) that sum:
+ *   entropy_p     = -sum_T p(T) log p(T) = log_z_p - E_p[R^p]
+ *   cross_entropy = -sum_T p(T) log q(T) = log_z_q - E_p[R^q]
+ *   kl            = cross_entropy - entropy_p = KL(p || q) >= 0 (to rounding)
+ *   J             = w_kl[b] * kl + w_ce[b] * cross_entropy
+ *   d_split_q = dJ / d s^q:  G_q[e] = (w_kl + w_ce) * (nu^q[e] - nu^p[e])
+ *   d_split_p = dJ / d s^p:  G_p[e] = nu^p[e] * (E_p[V | e in T] - E_p[V]),  v[e] = w_kl * r^p[e] - (w_kl + w_ce) * r^q[e], V(T) its sum
+ *   d_split_x[cell, k] = G_x[cell, k] - [k == k*_x] * sum_k G_x[cell, .],  k*_x the first maximum of chart x's OWN row
+ * nu^x the edge marginal of chart x, as cliora_bracket_grad has it: every row of both gradients sums to zero.  Log-space inside and
+ * outside tables of both charts and, for d_split_p, cliora_tree_expectation's pair of mean tables under p, all in fp64, sums in a fixed
+ * order; the outputs are fp32.  nu^p and nu^q are formed by one expression: the same workspace as both charts gives d_split_q == 0
+ * exactly, kl == 0 exactly and d_split_p at rounding level.
+ *   w_kl (B) fp32 device or NULL = 1; w_ce (B) fp32 device or NULL = 0: in a backward, the cotangents of kl and cross_entropy.
+ *   d_split_p, d_split_q: each NULL or cliora_plan_split_score_count floats in the layout cliora_bracket_grad writes, in which EVERY
+ *     element is written (no memset is needed); cells beyond a sentence's triangle get zeros.  d_split_p NULL (a detached teacher, the
+ *     common case): the two mean tables are neither formed nor carved, and d_split_q has the bits of the call with d_split_p.  Both
+ *     NULL: evaluation only.
+ *   kl_out, cross_entropy_out, entropy_p_out, log_z_p_out, log_z_q_out (B) fp32, all required; none depends on the weights.  log_z_p and
+ *     log_z_q have cliora_span_posteriors' bits, entropy_p has cliora_tree_expectation's.  One word: all zeros.  Two words: kl =
+ *     cross_entropy = entropy_p = 0 and both gradients are exactly 0.
+ *   lengths (B) int32 device or NULL, one array for both charts; status: an int32 on the device, zeroed by the call, always required: it
+ *     counts the lengths outside [1, L].  Such a sentence gets zero gradients and zero scalars; its weights and scores are not read.
+ *     With every length equal to L the outputs are bitwise those of the lengths == NULL call.
+ * One workgroup per sentence, a wavefront per cell, each element written by one lane, no floating-point atomics: two calls give equal
+ * bits, and a sentence of a padded chart gets the bits it gets alone.  The tables fit the LDS (56 C + 4 L + 128 bytes with d_split_p,
+ * 40 C + 4 L + 128 without: 114.1 / 81.6 KiB at L 64): no scratch.  TreeLSTM plans are taken.  Refused with CLIORA_EINVAL and a message
+ * that starts with the entry's name, before any launch: either plan long (L > 64); plans whose B or L differ; a NULL plan, workspace,
+ * scalar output or status; a plan that has not run a forward. */
+int cliora_tree_kl(cliora_plan* plan_p, void* fwd_workspace_p, cliora_plan* plan_q, void* fwd_workspace_q, const int32_t* lengths,
+                   const float* w_kl, const float* w_ce, float* d_split_p, float* d_split_q, float* kl_out, float* cross_entropy_out,
+                   float* entropy_p_out, float* log_z_p_out, float* log_z_q_out, int32_t* status, void* stream);
 /* Both passes for sentences of DIFFERENT lengths run as one batch, each padded on the right to the plan's L (inference only).  The
  * arguments of cliora_chart_forward, plus
  *   lengths (B) int32 device; root_levels: bit t set iff some sentence has lengths[b] - 1 == t (the caller holds the lengths on the
